@@ -31,6 +31,7 @@ Prints ONE JSON line on rank 0.
   cpu_baseline the UNMODIFIED reference Quadrotor.step, one single-env worker process per host core (kind "reference":
                imported from oracle/_ref, the byte-compiled copy oracle/make_ref.py builds and ships); the C port of it
                (oracle/) beside it as cpu_port — and alone (kind "port") only if oracle/_ref is missing
+  dump_outputs with --dump-outputs DIR: where the last timed step's outputs were written (DIR/<name>.npy) and their shapes
 """
 import argparse
 import ctypes
@@ -911,6 +912,42 @@ class MazeShard:
         self.env.step(self.actions[i % 4])
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(path, quad, maze=None):
+    """--dump-outputs: what a caller of the timed env.step() holds after its last call, written as `path`/<name>.npy — the
+    quadrotor's obs, reward, the float64 `reward64`, done and info["failed"], and for the mixed workload the maze's frames, reward,
+    reward64 and done. Integer and bool outputs are written as float32 (exact: frame values are small integers), reward64 as
+    float64. When the batch's rows would exceed 64 MB in all, a fixed seeded sample of env rows (the same rows in every file) is
+    written instead. Returns the record for the JSON line."""
+    e = quad.env
+    arrays = [("quadrotor_obs", e._obs, torch.float32), ("quadrotor_reward", e._reward, torch.float32),
+              ("quadrotor_reward64", e.reward64, torch.float64), ("quadrotor_done", e._done, torch.float32),
+              ("quadrotor_failed", e._failed, torch.float32)]
+    if maze is not None:
+        m = maze.env
+        arrays += [("maze3d_obs", m._obs, torch.float32), ("maze3d_reward", m._reward, torch.float32),
+                   ("maze3d_reward64", m.reward64, torch.float64), ("maze3d_done", m._done, torch.float32)]
+    n = quad.n
+    assert all(t.shape[0] == n for _, t, _ in arrays)
+    row_bytes = sum(t[0].numel() * torch.empty(0, dtype=dt).element_size() for _, t, dt in arrays)
+    rows = None
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        rows_t = torch.as_tensor(rows, device=e.device)
+    os.makedirs(path, exist_ok=True)
+    files = {}
+    for name, t, dt in arrays:
+        a = (t if rows is None else t.index_select(0, rows_t)).to(dt).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        files[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return {"dir": os.path.abspath(path), "files": files, "envs": n,
+            "rows": "all" if rows is None else {"sampled": int(len(rows)), "seed": DUMP_SAMPLE_SEED},
+            "step": "the last timed env.step() (with two timed regions, the second one's)"}
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -973,7 +1010,13 @@ def main(argv=None):
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--plan-only", action="store_true",
                     help="rendezvous + shard plans only, on CPU (what tests/test_distributed_cpu.py drives); no GPU work")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed env.step() returned (rank 0's shard) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all (a fixed seeded sample of env rows beyond that); the inputs "
+                         "depend on the arguments only, so two builds can be compared output for output")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_spawn(argv, args.gpus)     # bare `python bench.py --gpus N`: spawn the N ranks ourselves
@@ -1116,6 +1159,8 @@ def main(argv=None):
             other = that
         if auto:
             other["chosen_by"] = "--launch auto: higher whole-job throughput of the two timed regions"
+    # the outputs of the last timed step, before anything below steps the batch again
+    dumped = dump_outputs(args.dump_outputs, quad, maze) if (args.dump_outputs and rank == 0) else None
 
     # What a short timed region pays on top of its kernels: the same env.step() launches as hipGraphs of K and
     # of 10 K steps, each replayed a few times between synchronisations; T(K) = a + b K gives the per-step cost b of a long run and
@@ -1176,6 +1221,8 @@ def main(argv=None):
             "data": "synthetic",
         }
         out.update(scaling_fields(value, world, envs_per_rank, args.steps, rank_walls, solo_wall, args.single_gpu_value))
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if not mixed:
             achieved = BYTES_PER_ENV_STEP * n / launch_s / 1e9
             out["config"] = {"workload": "Quadrotor hovering_control, %d envs/GPU, dt=0.01 (10 Euler sub-steps), "

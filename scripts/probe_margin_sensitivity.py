@@ -6,8 +6,9 @@ output (one sub-step in 220), which bounds what a GPU-vs-oracle comparison of si
 
     python scripts/probe_margin_sensitivity.py  >  profiles/r06/walker_margin_sensitivity.txt
 """
-import sys, numpy as np, copy
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, numpy as np, copy
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import abd
 from urdf_fixture import A1_LIKE_TOES, a1_like_urdf
 from metagym_amd.quadrupedal import load_urdf, MOTOR_NAMES

@@ -16,7 +16,7 @@ import pytest
 from oracle import abd
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "walker_rules.npz")
-ASSETS = os.path.join(os.environ.get("METAGYM_REFERENCE", "/root/reference"), "metagym", "metalocomotion", "envs", "assets")
+WORLD = os.path.join(os.path.dirname(__file__), "golden", "walker_world.json")
 OBS_TOL, REW_TOL = 1e-6, 1e-9
 
 
@@ -89,21 +89,24 @@ def test_goldens_exercise_the_rules():
     assert cases[0]["obs"].shape[1] == 44 and cases[-1]["obs"].shape[1] == 28
 
 
-@pytest.mark.skipif(not os.path.isdir(ASSETS), reason="reference tree not present (build container only)")
-def test_parser_joint_order_is_what_addToScene_enumerates():
+def test_parser_joint_order_is_what_addToScene_enumerates(tmp_path):
     """mjcf.py's joint / body order against the link enumeration the PyBullet stand-in derives from the XML on its
     own (document order, intermediates for multi-joint bodies, `jointfix*` for joint-less ones) and the
-    reference's filter on it (robot_bases.py:82-95: skip `ignore*` and `jointfix*`), for every shipped file."""
+    reference's filter on it (robot_bases.py:82-95: skip `ignore*` and `jointfix*`), for every 16th shipped file
+    (tests/golden/walker_assets.tar.xz, recorded from the reference by oracle/gen_golden_walker_world.py)."""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "refstubs"))
     import pybullet
+    from walker_fixtures import extract_assets
     from metagym_amd.metalocomotion import variants
     from metagym_amd.metalocomotion.mjcf import load_mjcf
+    assets = str(tmp_path)
+    listing = extract_assets(assets)
     for robot, sub in (("humanoid", "humanoids"), ("ant", "ants")):
-        files = sorted(f for f in os.listdir(os.path.join(ASSETS, sub)) if f.endswith(".xml"))
+        files = listing[sub]
         assert len(files) == 385
         for f in files[::16] + ["%s.xml" % robot]:
-            path = os.path.join(ASSETS, sub, f)
+            path = os.path.join(assets, sub, f)
             _, base, links = pybullet.enumerate_links(path)
             ordered = [L["joint"] for L in links if not L["joint"].startswith(("jointfix", "ignore"))]
             m = load_mjcf(path, foot_names=variants.FEET[robot])
@@ -114,30 +117,24 @@ def test_parser_joint_order_is_what_addToScene_enumerates():
             assert all(foot in named for foot in variants.FEET[robot])
 
 
-@pytest.mark.skipif(not os.path.isdir(ASSETS), reason="reference tree not present (build container only)")
 def test_world_parameters_are_what_the_reference_sets():
     """L1: the unmodified Scene / StadiumScene / env code (scene_bases.py:52-56, stadium.py:19-25, env_bases.py:47-48) runs
-    on the PyBullet stand-in, which records what it is told; those values are the product's."""
+    on the PyBullet stand-in, which records what it is told (tests/golden/walker_world.json, recorded by
+    oracle/gen_golden_walker_world.py); those values are the product's."""
     import inspect
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for p in (root, os.path.join(root, "oracle", "refstubs"), os.environ.get("METAGYM_REFERENCE", "/root/reference")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    np.int = int
-    import gym
-    import metagym.metalocomotion  # noqa: F401
+    import json
+    from types import SimpleNamespace
     from metagym_amd import registration
     from metagym_amd.metalocomotion import walker_env
+    with open(WORLD) as f:
+        recorded = json.load(f)
     for env_id, task in (("meta-humanoid-v0", "humanoid.xml"), ("meta-ant-v0", "ant.xml")):
-        env = gym.make(env_id, enable_render=False)
-        env.set_task(task)
-        env.reset()
-        w = env._p._world
+        w = SimpleNamespace(**recorded[env_id])
+        assert w.task == task
         kw = registration.registry[env_id][1]
         defaults = inspect.signature(walker_env.WalkerBatchEnv.__init__).parameters
         assert w.gravity == walker_env.GRAVITY and w.contact_erp == walker_env.CONTACT_ERP
         assert w.sub_steps == kw["frame_skip"] and w.fixed_time_step == kw["time_step"] * kw["frame_skip"]
         assert w.solver_iterations == defaults["solver_iterations"].default
-        floors = [b for b in w.bodies if type(b).__name__ == "_Floor"]
-        assert floors and all(f.friction == walker_env.GROUND_FRICTION for f in floors)
+        floors = w.floor_frictions
+        assert floors and all(f == walker_env.GROUND_FRICTION for f in floors)

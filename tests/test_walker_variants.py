@@ -3,16 +3,15 @@ regenerates the reference's 2 x 384 shipped body variants (metagym_amd/metalocom
 spec + the edits of gen_variant_humanoids.py:33-76 / gen_variant_ants.py:33-56 + the recovered patterns).
 Every regenerated model must equal the parse of the shipped MJCF file: checked through sha256 digests of the
 parsed arrays committed by oracle/extract_variant_patterns.py (tests/golden/walker_variant_digests.json), and
-array for array against the files themselves when the reference tree is present. CPU-only."""
+array for array against every 7th shipped file itself (tests/golden/walker_assets.tar.xz, recorded by
+oracle/gen_golden_walker_world.py). CPU-only."""
 import hashlib
 import json
 import os
 
 import numpy as np
-import pytest
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-ASSETS = os.path.join(os.environ.get("METAGYM_REFERENCE", "/root/reference"), "metagym", "metalocomotion", "envs", "assets")
 
 DIGEST_KEYS = ("body_parent", "body_pos", "body_rot", "body_mass", "body_com", "body_inertia", "joint_body",
                "joint_anchor", "joint_axis", "joint_lo", "joint_hi", "joint_armature", "joint_damping",
@@ -45,17 +44,19 @@ def test_all_768_variants_equal_the_shipped_files():
     assert n == 768 and len(want) == 770
 
 
-@pytest.mark.skipif(not os.path.isdir(ASSETS), reason="reference tree not present (build container only)")
-def test_variants_equal_the_reference_files_array_for_array():
+def test_variants_equal_the_reference_files_array_for_array(tmp_path):
+    from walker_fixtures import extract_assets
     from metagym_amd.metalocomotion import variants
     from metagym_amd.metalocomotion.mjcf import load_mjcf
+    assets = str(tmp_path)
+    listing = extract_assets(assets)
     for robot, sub in (("humanoid", "humanoids"), ("ant", "ants")):
-        listed = sorted(f for f in os.listdir(os.path.join(ASSETS, sub)) if f.startswith(robot + "_var_"))
+        listed = sorted(f for f in listing[sub] if f.startswith(robot + "_var_"))
         ours = sorted(variants.task_names(robot, "TRAIN") + variants.task_names(robot, "TEST") + variants.task_names(robot, "OOD"))
         assert listed == ours                                     # same task names as meta_humanoids_env.py:18-27 lists
         for name in ours[::7] + ["%s.xml" % robot]:
             for preset in ("bullet", "mujoco"):
-                ref = load_mjcf(os.path.join(ASSETS, sub, name), foot_names=variants.FEET[robot], preset=preset).to_dict()
+                ref = load_mjcf(os.path.join(assets, sub, name), foot_names=variants.FEET[robot], preset=preset).to_dict()
                 mine = variants.model_from_task_name(name, preset=preset).to_dict()
                 assert set(ref) == set(mine)
                 for k in ref:
