@@ -290,8 +290,8 @@ typedef struct mg_maze_view {
     double uniform_cell_size;      /* (ABI 5) > 0: the caller vouches that EVERY task of the table has exactly this cell_size (tasks
                                       of one sampler configuration do). The library then evaluates the renderer's power-of-two
                                       conditions once, on the host, and runs its specialised kernel when they all hold (cell size,
-                                      texture size and resolution powers of two, int32 frames: the stock set-up) — same frames bit
-                                      for bit. 0: unknown, the general kernel decides per env. (ABI 6) The promise is CHECKED, not trusted:
+                                      text_size and tex_size powers of two, cells at least one texture wide: the stock set-up; int32
+                                      and uint8 frames both have stock kernels) — same frames bit for bit. 0: unknown, the general kernel decides per env. (ABI 6) The promise is CHECKED, not trusted:
                                       see mg_maze_check_uniform_cell_size — a wrong value is MG_ERR_BAD_CONFIG, never wrong frames. */
 } mg_maze_view;
 
@@ -310,8 +310,9 @@ int mg_maze_check_uniform_cell_size(const mg_maze_tasks *tasks, double uniform_c
  * ALLOCATOR-REUSE HAZARD: the memory of a checked pair is keyed by address; a caching allocator (torch's, a pool) readily hands
  * the address of a freed table to the next one. A binding must call this BEFORE it frees a task table or rewrites its cell
  * sizes in place — the next mg_maze3d_step on that address then re-reads the rows (or refuses under capture) instead of
- * trusting a check made on other contents. The Python layer calls it from DeviceTaskTable's finaliser and re-checks at every
- * set_task. Host-only, never fails on an unknown table. */
+ * trusting a check made on other contents. The Python layer ties the call to the life of the TABLE, not of an env (envs may share
+ * one table): a weakref.finalize on the tensor holding the scalar rows (metamaze/maze_task.py, forget_when_freed) calls it when
+ * the table is freed, and set_task re-checks. Host-only, never fails on an unknown table. */
 int mg_maze_forget_tasks(const mg_maze_tasks *tasks);
 
 /* Host helper: the per-column tables of ray_caster_utils.py:82-90 (tan_hp accumulated column by

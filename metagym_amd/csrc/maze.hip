@@ -1311,6 +1311,8 @@ extern "C" int mg_maze3d_step(const mg_maze_tasks *T, const mg_maze_view *view, 
     // up to 64x64 one wave per env is fastest (32x32: 0.52 vs 0.60 ms with two at 65 536 envs, 64x64: 0.91 vs 0.95 — no
     // workgroup barrier partners, more independent envs resident per CU), 84x84 runs best with two, from 128x128 up with four.
     // 32-column slabs beat 64 everywhere (half the overlay-record LDS, more workgroups per CU).
+    // (tests/maze_routes.py maze3d_route() restates the route choice below — waves, slab, REC, SMALL, STOCK, the uint8 store —
+    // and the route tests check their case lists reach every route through it: change both together.)
     const long frame_px = (long)vk.H * vk.V;
     int n_waves = frame_px <= 64L * 64L ? 1 : (frame_px < 128L * 128L ? 2 : MZ_WAVES);
     vk.slab = SLAB;

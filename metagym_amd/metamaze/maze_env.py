@@ -22,7 +22,7 @@ import torch
 
 from .. import _lib
 from ..spaces import Box, Discrete
-from .maze_task import MAZE_TASK_MANAGER, DeviceTaskTable, TaskConfig  # noqa: F401  (TaskConfig re-exported like the reference's maze_env)
+from .maze_task import MAZE_TASK_MANAGER, DeviceTaskTable, TaskConfig, forget_when_freed  # noqa: F401  (TaskConfig re-exported like the reference's maze_env)
 
 PI = 3.1415926                      # dynamics.py:6
 DISCRETE_ACTIONS = [(-1, 0), (1, 0), (0, -1), (0, 1)]   # maze_env.py:14
@@ -53,13 +53,6 @@ class _MazeBatch(object):
         self._done = torch.zeros(N, dtype=torch.bool, device=dev)
 
     # ------------------------------------------------------------------ tasks
-    def __del__(self):
-        try:
-            if self._tasks_c is not None:
-                self._lib.mg_maze_forget_tasks(self._tasks_c)
-        except Exception:
-            pass
-
     def set_task(self, task_config, task_ids=None):
         """task_config: one TaskConfig, a list of T TaskConfigs (uploaded once), or a DeviceTaskTable from
         `MazeTaskManager.sample_tasks_device` (already on the GPU). Env e plays task task_ids[e]
@@ -94,16 +87,15 @@ class _MazeBatch(object):
                                      t.step_reward, t.goal_reward, 0.0] for t in tasks], np.float64))
             assert int(host["texts"].max()) < MAZE_TASK_MANAGER.n_texts, "cell_texts refers to a missing texture"
             self._task_t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in host.items()}
+            forget_when_freed(self._task_t["scalars"])       # this env's own upload: forgotten when it is freed
             self.tasks = tasks
             self._min_cell_size = min(float(t.cell_size) for t in tasks)
             sizes = set(float(t.cell_size) for t in tasks)
             self._uniform_cell_size = sizes.pop() if len(sizes) == 1 else 0.0   # mg_maze_view.uniform_cell_size: 0 = tasks differ
         nn = n * n
         self.n = n
-        if self._tasks_c is not None:
-            # the table this env held goes away (its tensors are released below): the library's address-keyed memory of a
-            # checked (table, uniform_cell_size) pair must not outlive it — torch's caching allocator reuses the address
-            self._lib.mg_maze_forget_tasks(self._tasks_c)
+        # (the library's address-keyed memory of a checked (table, uniform_cell_size) pair is dropped when the table's scalar rows
+        # are freed — forget_when_freed, registered where the table is created — never by an env: envs may share a table)
         c = _lib.MazeTasks()
         c.n, c.n_tasks = n, T
         for k in host:

@@ -12,6 +12,7 @@ directory with the same naming rule (file names containing 'ground' / 'wall' / '
 without one, deterministic procedural textures of the same shape are generated.
 """
 import os
+import weakref
 from collections import namedtuple
 
 import numpy as np
@@ -19,6 +20,19 @@ import numpy as np
 TaskConfig = namedtuple("TaskConfig", ["start", "goal", "cell_walls", "cell_texts", "cell_size", "wall_height",
                                        "agent_height", "initial_life", "max_life", "step_reward", "goal_reward",
                                        "food_rewards", "food_interval"])
+
+
+def forget_when_freed(scalars):
+    """Tie `mg_maze_forget_tasks` to the life of a task table: when the tensor holding its [T][8] scalar rows is collected, the
+    library drops what it remembers about that address (the checked uniform_cell_size pair, include/metagym_hip.h) — before a
+    caching allocator can hand the address to another table. Envs sharing the table keep their checked pair as long as the
+    table lives, whatever happens to the other envs."""
+    from .. import _lib
+    lib = _lib.load()
+    c = _lib.MazeTasks()
+    c.scalars = scalars.data_ptr()
+    f = weakref.finalize(scalars, lib.mg_maze_forget_tasks, c)
+    f.atexit = False
 
 
 class DeviceTaskTable(object):
@@ -32,6 +46,7 @@ class DeviceTaskTable(object):
         self.cell_size = float(cell_size)      # uniform over the table (a sampler parameter)
         self.tensors = tensors
         self.n_tasks = int(tensors["start"].shape[0])
+        forget_when_freed(tensors["scalars"])
 
     def __len__(self):
         return self.n_tasks

@@ -670,11 +670,12 @@ def test_maze3d_uint8_fast_path_is_the_clamped_reference_frame():
 @pytest.mark.parametrize("ident,res", [("meta-maze-discrete-3D-v0", (40, 100)), ("meta-maze-discrete-3D-v0", (24, 30)),
                                        ("meta-maze-discrete-3D-v0", (64, 64)), ("meta-maze-continuous-3D-v0", (32, 132)),
                                        ("meta-maze-discrete-3D-v0", (20, 256)), ("meta-maze-continuous-3D-v0", (33, 7))])
-def test_maze3d_uint8_packed_store_shapes(ident, res):
-    """The uint8 frames' packed store (round 6: a quad of lanes writes its 12 bytes as one dwordx3, csrc/maze.hip flush()) over
-    the shapes that decide its path: res_v a multiple of 4 with a ragged last 64-row chunk (100, 132), one chunk exactly (64),
-    four chunks (256), and heights that are not a multiple of 4 (30, 7: the byte-store path) — every byte equals
-    min(int32 frame, 255), discrete and continuous, small-frame and four-wave kernels."""
+def test_maze3d_uint8_byte_store_shapes_equal_clamped_int32(ident, res):
+    """The uint8 frames' default byte stores (three buffer_store_byte per pixel, csrc/maze.hip flush(); the packed dwordx3 store
+    runs only under MG_MAZE3D_U8_PACKED and is checked against the oracle by tests/test_maze3d_routes_gpu.py) over frame shapes
+    with a ragged last 64-row chunk (100, 132), one chunk exactly (64), four chunks (256) and heights that are not a multiple of 4
+    (30, 7), on the one- and two-wave stock uint8 kernels, discrete and continuous: every byte of the GPU's uint8 frame equals
+    min(the GPU's int32 frame, 255). GPU against GPU — the oracle comparison of these routes is in test_maze3d_routes_gpu.py."""
     import metagym_amd
     from metagym_amd.metamaze import MazeTaskSampler
     tasks = [MazeTaskSampler(n=9, allow_loops=False, food_density=0.08, food_interval=4, seed=170 + s) for s in range(3)]

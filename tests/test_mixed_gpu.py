@@ -100,3 +100,88 @@ def test_north_star_batch_sampled_against_oracle(n):
             assert np.array_equal(fin[k][..., e].cpu().numpy(), o[kk][0]), (k, e)
         assert int(fin["ct"][e]) == int(ct[0]) and int(fin["episode"][e]) == int(epo[0])
     assert collided > 0
+
+
+def test_c5_per_gpu_size_sampled_against_both_oracles():
+    """C5 at its per-GPU size: 65 536 quadrotors + 65 536 MetaMazeDiscrete3D envs (9x9, 64x64 int32 frames: the SMALL kernel over a
+    grid of 65 536 workgroups, envs rotated over the XCDs by mg::env_of_block) through bench.MixedStep, with short episodes so both
+    families restart inside the 12 compared steps. 128 sampled envs of each family, env 0 and env n-1 among them, replayed with the
+    shards' resident action batches: quadrotors on oracle/quadrotor.py's auto-reset step (final state, clock and episode
+    bit-exact), mazes on oracle/maze.py (reward, done, the whole per-env state and every pixel of every step bit-exact)."""
+    from metagym_amd.metamaze import MAZE_TASK_MANAGER
+    from oracle import maze as mo
+    dev = torch.device(DEV)
+    n, nt, max_steps, T = 65536, 5, 4, 12
+    plan = bench.shard_plan(0, 1, n, "mixed")
+    quad = bench.QuadrotorShard(dev, plan, n, nt=nt)
+    maze = bench.MazeShard(dev, plan, n, res=64, max_steps=max_steps)
+    torch.cuda.synchronize()
+    step = bench.MixedStep(dev, quad, maze)
+    rs = np.random.RandomState(65536)
+    qs = np.sort(rs.choice(np.arange(1, n - 1), 126, replace=False))
+    ms = np.sort(rs.choice(np.arange(1, n - 1), 126, replace=False))
+    qs, ms = np.concatenate([[0], qs, [n - 1]]), np.concatenate([[0], ms, [n - 1]])
+    qs_t, ms_t = torch.as_tensor(qs, device=DEV), torch.as_tensor(ms, device=DEV)
+
+    # quadrotor: the sampled envs' state after the shard's pre-roll, and the action rows they will get
+    sd = quad.env.state_dict()
+    st0 = {k: sd[k][..., qs_t].cpu().numpy() for k in ("pos", "vel", "omega", "propw", "rot", "ct", "episode")}
+    q_act = [quad.action_list[i % bench.N_ACTION_BATCHES][qs_t].cpu().numpy() for i in range(T)]
+    # maze: the sampled envs start from reset() (checked against the oracle's reset state and frame)
+    tasks = bench.maze_tasks()
+    ids = maze.env.task_id.cpu().numpy()
+    assert np.array_equal(ids, plan["maze_task_ids"])
+    otasks = [mo.Task(**t._asdict()) for t in tasks]
+    tt = mo.SURVIVAL
+    states = {int(e): mo.State(otasks[ids[e]]) for e in ms}
+    for e in ms:
+        mo.reset(otasks[ids[e]], tt, states[int(e)])
+    view = mo.View(MAZE_TASK_MANAGER.grounds.astype(np.uint8), MAZE_TASK_MANAGER.ceil, 64, 64)
+    m_act = [maze.actions[i % 4][ms_t].cpu().numpy() for i in range(T)]
+
+    def maze_matches(label):
+        ob = maze.env._obs[ms_t].cpu().numpy()
+        grid, steps, life = (maze.env.grid[:, ms_t].cpu().numpy(), maze.env.steps[ms_t].cpu().numpy(),
+                             maze.env.life[ms_t].cpu().numpy())
+        oidx = maze.env.ori_idx[ms_t].cpu().numpy()
+        food, wait, rev = (x[ms_t].cpu().numpy() for x in (maze.env.cur_food, maze.env.wait_refresh, maze.env.revival))
+        for k, e in enumerate(ms):
+            s = states[int(e)]
+            assert (grid[0, k], grid[1, k], steps[k], oidx[k]) == (s.c.grid[0], s.c.grid[1], s.c.steps, s.c.ori_idx), (label, e)
+            assert life[k] == s.c.life, (label, e)
+            assert np.array_equal(food[k], s.cur_food) and np.array_equal(wait[k], s.wait) and np.array_equal(rev[k], s.revival), (label, e)
+            ref = mo.observe_3d(otasks[ids[e]], tt, view, s, 0)
+            d = int((ob[k] != ref).sum())
+            assert d == 0, "%s env %d: %d pixel values differ" % (label, e, d)
+
+    maze_matches("reset")
+    m_ends = 0
+    for i in range(T):
+        step(i)
+        torch.cuda.synchronize()
+        r64, d = maze.env.reward64[ms_t].cpu().numpy(), maze.env._done[ms_t].cpu().numpy()
+        for k, e in enumerate(ms):
+            s, task = states[int(e)], otasks[ids[e]]
+            r, dd = mo.step_disc3d(task, tt, max_steps, s, int(m_act[i][k]))
+            assert r == r64[k] and dd == bool(d[k]), (i, e)
+            if dd:                                          # fused auto-reset
+                mo.reset(task, tt, s)
+                m_ends += 1
+        maze_matches("step %d" % i)
+    assert m_ends >= 2 * len(ms), m_ends
+
+    fin = quad.env.state_dict()
+    c = qo.default_consts(nt=nt)
+    q_ends = 0
+    for j, e in enumerate(qs):
+        st = qo.make_states(st0["pos"].T[[j]], st0["vel"].T[[j]], st0["omega"].T[[j]], st0["propw"].T[[j]], st0["rot"].T[[j]])
+        ct, epo = st0["ct"][[j]].astype(np.int32), st0["episode"][[j]].astype(np.int64).astype(np.uint32)
+        ar = qo.default_autoreset(seed=plan["job_seed"], env_id_base=plan["env_id_base"] + int(e))
+        for i in range(T):
+            out = qo.batch_env_step_autoreset(c, ar, st, ct, epo, q_act[i][[j]])
+            q_ends += int(out[2][0] != 0)
+        o = qo.states_to_arrays(st)
+        for k, kk in (("pos", "pos"), ("vel", "vel"), ("omega", "omega"), ("propw", "propw"), ("rot", "R")):
+            assert np.array_equal(fin[k][..., e].cpu().numpy(), o[kk][0]), (k, e)
+        assert int(fin["ct"][e]) == int(ct[0]) and (int(fin["episode"][e]) & 0xFFFFFFFF) == int(epo[0]), e
+    assert q_ends >= 2 * len(qs), q_ends
