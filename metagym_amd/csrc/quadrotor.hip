@@ -20,6 +20,8 @@
 // restatement this kernel is tested against). The translation unit is compiled with
 // -ffp-contract=off so no a*b+c is fused — NumPy never fuses — which makes this kernel bit-identical
 // to the CPU oracle for everything except atan2f (OCML vs glibc, <= 2 ulp).
+#include <cstdlib>
+
 #include "mg_common.h"
 #include "mg_philox.h"
 
@@ -157,7 +159,9 @@ __device__ __forceinline__ void inv3(const float *Af, float *Ainv, double *A) { 
 // needing ~40 fewer scalar constants and ~70 fewer VALU ops per sub-step.
 // want_power: self.power (:139,:188) is overwritten by every sub-step and read only by the reward
 // after the last one (env.py:217), so the four f32 divisions behind it run in the last sub-step only.
-template <bool SIMPLE>
+// RECIP: the host has established k.quality_recip_exact (stock quality 0.5), so f / quality is the multiply
+// by its exact reciprocal with no test in the sub-step.
+template <bool SIMPLE, bool RECIP = false>
 __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *eff32, bool want_power) {
     float prop_force_z = 0.0f;
     float prop_torque[3] = {0.0f, 0.0f, 0.0f};
@@ -246,7 +250,7 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
         const float pf = (c == 2) ? prop_force_z : 0.0f;
         double f_all = (double)(pf + f_grav[c]) + f_drag[c];
         t_all[c] = (double)(SIMPLE ? prop_torque[c] : prop_torque[c] + t_grav_neg[c]) + t_drag[c];
-        body_acc[c] = k.quality_recip_exact ? f_all * k.inv_quality : f_all / k.quality;
+        body_acc[c] = (RECIP || k.quality_recip_exact) ? f_all * k.inv_quality : f_all / k.quality;
     }
 #pragma unroll
     for (int r = 0; r < 3; ++r)   // mv_f32f64(s.R, body_acc, acc) on the already widened matrix
@@ -291,12 +295,12 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
     s.nw = norm3(s.w);
 }
 
-// quadrotorsim.py:212-221
+// quadrotorsim.py:212-221. A select chain, not early returns: all three tests are cheap and the early returns
+// compiled into a divergent branch per test. Precedence as in the reference: range, velocity, body rate.
 __device__ __forceinline__ int failure_code(const QuadK &k, const Lane &s) {
-    if (sumsq3(s.p) > k.fail_range_sq32) return 1;   // == sqrtf(sumsq) > fail_range32, see fold_config
-    if (s.nv > k.fail_velocity) return 2;
-    if (s.nw > k.fail_w) return 3;
-    return 0;
+    const int c3 = (s.nw > k.fail_w) ? 3 : 0;
+    const int c2 = (s.nv > k.fail_velocity) ? 2 : c3;
+    return (sumsq3(s.p) > k.fail_range_sq32) ? 1 : c2;   // sumsq > S == sqrtf(sumsq) > fail_range32, see fold_config
 }
 
 // quadrotorsim.py:260-293, :111-120; env.py:193-209
@@ -432,22 +436,44 @@ __global__ void quadrotor_targets_kernel(QuadK k, int nt, const float *actions, 
 
 // ---- SoA load / store ----------------------------------------------------------------------------
 
-__device__ __forceinline__ void load_lane(const mg_quadrotor_state &st, int n, int e, Lane &s, int &ct) {
+// ROT_FIRST: issue rot, vel and omega ahead of the rest, in the order the derived values below consume them
+template <bool ROT_FIRST = false>
+__device__ __forceinline__ void load_state(const mg_quadrotor_state &st, int n, int e, Lane &s, int &ct) {
+    if (ROT_FIRST) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) s.p[c] = st.pos[(size_t)c * n + e];
+        for (int c = 0; c < 9; ++c) s.R[c] = st.rot[(size_t)c * n + e];
+    }
+    if (!ROT_FIRST) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s.p[c] = st.pos[(size_t)c * n + e];
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) s.v[c] = st.vel[(size_t)c * n + e];
 #pragma unroll
     for (int c = 0; c < 3; ++c) s.w[c] = st.omega[(size_t)c * n + e];
+    if (ROT_FIRST) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s.p[c] = st.pos[(size_t)c * n + e];
+    }
 #pragma unroll
     for (int c = 0; c < 4; ++c) s.pw[c] = st.propw[(size_t)c * n + e];
+    if (!ROT_FIRST) {
 #pragma unroll
-    for (int c = 0; c < 9; ++c) s.R[c] = st.rot[(size_t)c * n + e];
+        for (int c = 0; c < 9; ++c) s.R[c] = st.rot[(size_t)c * n + e];
+    }
     ct = st.ct[e];
+}
+
+__device__ __forceinline__ void derive_lane(Lane &s) {
     inv3(s.R, s.Ri, s.Rd);
     s.nv = norm3(s.v);
     s.nw = norm3(s.w);
     s.power = 0.0f;
+}
+
+__device__ __forceinline__ void load_lane(const mg_quadrotor_state &st, int n, int e, Lane &s, int &ct) {
+    load_state(st, n, e, s, ct);
+    derive_lane(s);
 }
 
 // Every output of a step is written once and next read by a later launch (or by the caller), never by
@@ -504,7 +530,13 @@ __device__ __forceinline__ void store_obs_wave(float *tile, const float *obs, fl
 
 // QuadrotorSim.reset quadrotorsim.py:239-258 with the noise drawn on the device:
 // value = base + noisy * U[0,1) * (+1 if U' > 0.5 else -1), per component.
-__device__ __forceinline__ void reset_lane_random(const QuadK &k, Lane &s, int e, uint32_t episode) {
+// The draw depends on the seed, the env id and the episode counter only, so it can be made before the
+// sub-steps (reset_draw) and applied after them (reset_apply).
+struct ResetDraw {
+    double v[3], w[3], nv, nw;
+};
+
+__device__ __forceinline__ ResetDraw reset_draw(const QuadK &k, int e, uint32_t episode) {
     // two Philox blocks = 8 words: six 32-bit magnitudes and one word of sign bits (the reset sits on the
     // critical path of every wave that holds a finished env, so a third block is worth avoiding).
     // counter = (global env id lo, hi, episode, block), key = seed: the k-th auto-reset of a given env draws
@@ -513,17 +545,29 @@ __device__ __forceinline__ void reset_lane_random(const QuadK &k, Lane &s, int e
     uint32_t r[8];
     const uint64_t gid = k.env_id_base + (uint64_t)e;
 #pragma unroll
-    for (int d = 0; d < 2; ++d)
-        philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), episode, (uint32_t)d, (uint32_t)k.seed,
-                      (uint32_t)(k.seed >> 32), &r[4 * d]);
+    for (int b = 0; b < 2; ++b)
+        philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), episode, (uint32_t)b, (uint32_t)k.seed,
+                      (uint32_t)(k.seed >> 32), &r[4 * b]);
     const double inv32 = 1.0 / 4294967296.0;
+    ResetDraw d;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double sv = ((r[6] >> c) & 1u) ? 1.0 : -1.0;
+        const double sw = ((r[6] >> (3 + c)) & 1u) ? 1.0 : -1.0;
+        d.v[c] = (double)k.init_v_base[c] + (k.init_v_noisy * ((double)r[c] * inv32)) * sv;
+        d.w[c] = (double)k.init_w_base[c] + (k.init_w_noisy * ((double)r[3 + c] * inv32)) * sw;
+    }
+    d.nv = norm3(d.v);
+    d.nw = norm3(d.w);
+    return d;
+}
+
+__device__ __forceinline__ void reset_apply(Lane &s, const ResetDraw &d) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         s.p[c] = 0.0f;
-        const double sv = ((r[6] >> c) & 1u) ? 1.0 : -1.0;
-        const double sw = ((r[6] >> (3 + c)) & 1u) ? 1.0 : -1.0;
-        s.v[c] = (double)k.init_v_base[c] + (k.init_v_noisy * ((double)r[c] * inv32)) * sv;
-        s.w[c] = (double)k.init_w_base[c] + (k.init_w_noisy * ((double)r[3 + c] * inv32)) * sw;
+        s.v[c] = d.v[c];
+        s.w[c] = d.w[c];
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) s.pw[c] = 0.0f;
@@ -533,8 +577,8 @@ __device__ __forceinline__ void reset_lane_random(const QuadK &k, Lane &s, int e
         s.Ri[c] = s.R[c];
         s.Rd[c] = (double)s.R[c];
     }
-    s.nv = norm3(s.v);
-    s.nw = norm3(s.w);
+    s.nv = d.nv;
+    s.nw = d.nw;
     s.power = 0.0f;
 }
 
@@ -559,9 +603,31 @@ __device__ __forceinline__ KArgsC *kernargs_fresh() {
     return p;
 }
 
-template <bool SIMPLE>
+// Forms of the step kernel (launch_plan picks one per launch):
+//   STEP_GENERIC       every configuration: k.times sub-steps in a loop, each guarded by the failure freeze.
+//   STEP_STOCK         the stock configuration, resolved on the host: SIMPLE, quality a power of two,
+//                      times == 10, fused auto-reset. The ten sub-steps are straight-line code (no branch):
+//                      with auto-reset a failed env restarts in the same launch, so its state after the failing
+//                      sub-step is never stored, observed or rewarded, and the sub-steps can run unconditionally.
+//                      A failed lane's later sub-steps may reach inf / NaN; nothing converts them to an integer or
+//                      an address (collision() runs only for fail == 0) and the reset overwrites them.
+//   STEP_STOCK_SHADOW  STEP_STOCK for one-step launches of at most one wave per SIMD: the lane's reset draw is made
+//                      for every lane while the prologue loads are in flight, so the restart only moves values.
+//                      With more than one wave per SIMD the VALU is busy during the loads, and ~150 extra VALU on
+//                      every wave would cost more than the branch it saves.
+enum StepForm { STEP_GENERIC = 0, STEP_STOCK = 1, STEP_STOCK_SHADOW = 2 };
+constexpr int STOCK_TIMES = 10;
+#ifndef MG_QUAD_SUBSTEP_UNROLL
+#define MG_QUAD_SUBSTEP_UNROLL 9   // of the first nine stock sub-steps (the tenth is peeled): 9 = straight-line, 1 = rolled
+#endif
+
+template <bool SIMPLE, int FORM>
 __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadrotor_state st, StepIO io,
-                                                               int n, int n_steps) {
+                                                               int n, int n_steps_arg) {
+    constexpr bool STOCK = FORM != STEP_GENERIC;
+    constexpr bool SHADOW = FORM == STEP_STOCK_SHADOW;
+    static_assert(!STOCK || SIMPLE, "the stock forms are SIMPLE");
+    const int n_steps = SHADOW ? 1 : n_steps_arg;
     __shared__ float tiles[WAVES_PER_BLOCK][mg::WAVE * (OBS_DIM + 1)];
     const int e = blockIdx.x * BLOCK + threadIdx.x;
     const bool live = e < n;
@@ -580,15 +646,34 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
             touch |= ka[line * 16];
         asm volatile("" ::"s"(touch));
     }
-    float4 a_next = reinterpret_cast<const float4 *>(io.action)[el];
-    __builtin_amdgcn_sched_barrier(0);   // keep this load ahead of the state loads (it would be sunk to its first use)
-
+    float4 a_next;
     Lane s;
     int ct;
     uint32_t episode = 0;
-    if (k.auto_reset) episode = st.episode[el];
+    ResetDraw rd;
+    if (SHADOW) {
+        // Loads in the order of their use: the episode counter (the reset draw needs nothing else), the action,
+        // then rot / vel / omega (inv3 and the norms), then the rest. The VALU would otherwise idle through the
+        // ~2-3 k cycles of the prologue burst; the draw and the derived values fill it, each behind a partial
+        // vmcnt wait. The sched_barriers keep the compiler from sinking the work to its first use.
+        episode = st.episode[el];
+        a_next = reinterpret_cast<const float4 *>(io.action)[el];
+        load_state<true>(st, n, el, s, ct);
+        __builtin_amdgcn_sched_barrier(0);
+        rd = reset_draw(k, el, episode);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) asm volatile("" : "+v"(rd.v[c]), "+v"(rd.w[c]));   // not sunk into the restart branch
+        asm volatile("" : "+v"(rd.nv), "+v"(rd.nw));
+        __builtin_amdgcn_sched_barrier(0);
+        derive_lane(s);
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
+        a_next = reinterpret_cast<const float4 *>(io.action)[el];
+        __builtin_amdgcn_sched_barrier(0);   // keep this load ahead of the state loads (it would be sunk to its first use)
+        if (STOCK || k.auto_reset) episode = st.episode[el];
+        load_lane(st, n, el, s, ct);
+    }
     const uint32_t episode_in = episode;
-    load_lane(st, n, el, s, ct);
     // All prologue loads land here (vmcnt = 0), not at their first use inside the step loop: there the wait
     // would be re-executed by every later step of a rollout and would also drain that step's freshly issued
     // action prefetch and the previous step's stores (2.5 us per step at K > 1; free at K = 1).
@@ -612,10 +697,22 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         const double old_pos[3] = {(double)s.p[0] + k.xoff, (double)s.p[1] + k.yoff,
                                    (double)(s.p[2] + k.zoff32)};            // env.py:131-133
         int fail = 0;
-        for (int it = 0; it < k.times; ++it) {                              // quadrotorsim.py:302-304
-            if (fail == 0) {      // a failed env freezes at the failing sub-step (reference raises)
-                substep<SIMPLE>(k, s, eff32, it == k.times - 1);
-                fail = failure_code(k, s);
+        if (STOCK) {             // straight-line sub-steps (see StepForm); the first failure code is kept
+#pragma unroll MG_QUAD_SUBSTEP_UNROLL
+            for (int it = 0; it < STOCK_TIMES - 1; ++it) {
+                substep<SIMPLE, true>(k, s, eff32, false);
+                const int code = failure_code(k, s);
+                fail = fail ? fail : code;
+            }
+            substep<SIMPLE, true>(k, s, eff32, true);
+            const int code = failure_code(k, s);
+            fail = fail ? fail : code;
+        } else {
+            for (int it = 0; it < k.times; ++it) {                          // quadrotorsim.py:302-304
+                if (fail == 0) {  // a failed env freezes at the failing sub-step (reference raises)
+                    substep<SIMPLE>(k, s, eff32, it == k.times - 1);
+                    fail = failure_code(k, s);
+                }
             }
         }
         // The reward / observation constants and the output pointers are used only from here on. Held in
@@ -675,8 +772,9 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         // optional in-place reset: stepped state for running envs, and — vector-env convention — the first
         // observation of the next episode for the envs that just finished.
         int tn = tn_step;
-        if (ke.auto_reset && done) {
-            reset_lane_random(ke, s, el, episode);
+        if ((STOCK || ke.auto_reset) && done) {
+            if (SHADOW) reset_apply(s, rd);
+            else reset_apply(s, reset_draw(ke, el, episode));
             episode += 1;
             tn = ct < ke.nt - 1 ? ct : ke.nt - 1;
         }
@@ -855,6 +953,8 @@ int check_state(const mg_quadrotor_state *s) {
 struct Plan {
     uint32_t magic;
     int32_t n, device, simple;
+    int32_t stock;   // STEP_STOCK applies (see StepForm)
+    int32_t simds;   // SIMDs of the device (0: unknown, STEP_STOCK_SHADOW is not used)
     QuadK k;
     mg_quadrotor_state st;
 };
@@ -883,6 +983,15 @@ int make_plan(Plan *p, const mg_quadrotor_config *cfg, const mg_quadrotor_autore
     p->n = n;
     p->device = mg::device_of(state->pos);
     p->simple = (config_is_simple(cfg) && cfg->task != MG_QUADROTOR_TASK_VELOCITY_CONTROL) ? 1 : 0;
+    // MG_QUAD_GENERIC=1 forces the generic kernel (A/B timing and tests); read per plan, so one process can hold both
+    const bool force_generic = getenv("MG_QUAD_GENERIC") != nullptr;
+    p->stock = (!force_generic && p->simple && p->k.quality_recip_exact && p->k.times == STOCK_TIMES && p->k.auto_reset) ? 1 : 0;
+    p->simds = 0;
+    int cus = 0;
+    if (p->device >= 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess)
+        p->simds = 4 * cus;
+    else
+        (void)hipGetLastError();
     p->st = *state;
     return MG_OK;
 }
@@ -896,12 +1005,13 @@ int launch_plan(const Plan *p, int32_t n_steps, const float *action, float *obs,
     mg::DeviceGuard guard(p->device);
     StepIO io{action, obs, reward, reward64, done, failed};
     const int n = p->n, grid = (n + BLOCK - 1) / BLOCK;
-    if (p->simple)
-        hipLaunchKernelGGL(quadrotor_step_kernel<true>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, p->k, p->st,
-                           io, n, n_steps);
-    else
-        hipLaunchKernelGGL(quadrotor_step_kernel<false>, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, p->k, p->st,
-                           io, n, n_steps);
+    const int waves = (n + mg::WAVE - 1) / mg::WAVE;
+    decltype(&quadrotor_step_kernel<false, STEP_GENERIC>) kern;
+    if (p->stock && n_steps == 1 && waves <= p->simds) kern = quadrotor_step_kernel<true, STEP_STOCK_SHADOW>;
+    else if (p->stock) kern = quadrotor_step_kernel<true, STEP_STOCK>;
+    else if (p->simple) kern = quadrotor_step_kernel<true, STEP_GENERIC>;
+    else kern = quadrotor_step_kernel<false, STEP_GENERIC>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, p->k, p->st, io, n, n_steps);
     return mg::check_launch("quadrotor_step_kernel");
 }
 
