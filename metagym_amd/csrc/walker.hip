@@ -16,11 +16,9 @@
 // iterated in velocity space (u += M^-1 J_r^T dlambda). oracle/abd.py is the independent numpy
 // restatement it is tested against; both are checked by physical invariants.
 //
-// Mapping: one lane per env, float64. The per-env work set (M: n^2, constraint Jacobians and their
-// M^-1 images: 2 * rows * n doubles, n = 6 + joints = 23 for the humanoid) lives in private memory;
-// the backend interleaves private arrays across the lanes of a wave, so every lane touching the
-// same element index is a coalesced access. This is a first, correctness-oriented mapping
-// (DESIGN.md §3.5 lists what a wave-per-env LDS version would change).
+// Two mappings (mg_walker_params.mapping), float64. Wave (the default): one wavefront per env, work set in LDS, walker_step_wave_kernel
+// instantiated per robot shape or dof count (wave_plan picks one). Lane: one lane per env, work set in private memory, walker_step_kernel,
+// the cross-check and the route for robots the wave scratch cannot hold. mg_walker_reset runs walker_reset_kernel (lane per env) for both.
 #include "mg_common.h"
 #include "mg_philox.h"
 
@@ -662,7 +660,7 @@ __global__ __launch_bounds__(WK_BLOCK) void walker_reset_kernel(mg_walker_topolo
 // ======================================================================================================
 // Wave-per-env mapping (default). One 64-lane wavefront owns one env; its whole work set lives in LDS
 // (18.3 KB for the humanoid: kinematics, packed M, h, the whitened constraint rows Jh = J L^-T, the scan tables; blocks whose
-// lifetimes do not overlap share storage, see carve()), so eight envs are resident per CU (two waves per SIMD, the register
+// lifetimes do not overlap share storage, see wave_layout()), so eight envs are resident per CU (two waves per SIMD, the register
 // file's cap too) and nothing spills to scratch in the sub-step loop. Serial, branchy sections are what cost time here
 // (DESIGN.md 3.4): every phase is written as a few lane-parallel passes. Lanes are dealt
 //   * hops (a body's fixed offset or one joint's rotation) for the kinematics and the velocity-product frames: scans over the
@@ -692,9 +690,9 @@ constexpr int W_MAXCAND = 48;       // contact candidates recorded per sub-step 
 // instruction. Computed at run time they were ~40 LDS pointers and 18 table pointers held in SGPRs for the whole
 // sub-step: 413 SGPR spills to VGPR lanes in the humanoid kernel (v_writelane / v_readlane on the hot path).
 // DMP = 1: the tuned kernel also carries btMultiBody's body velocity damping (the `preset="bullet"` world of the MetaLocomotion
-// envs): the frames keep v_ref (15 instead of 12 doubles per body), everything else is the tuned kernel.
+// envs): the frames keep v_ref (fd = 15 instead of 12 doubles per body), everything else is the tuned kernel.
 template <int B, int J, int S, int G, int OVL, int DMP = 0>
-struct Shape { static constexpr int nb = B, nj = J, ns = S, ng = G, overlay = OVL, damp = DMP; };
+struct Shape { static constexpr int nb = B, nj = J, ns = S, ng = G, overlay = OVL, damp = DMP, fd = (B == 0 || DMP != 0) ? 15 : 12; };
 using ShapeAny = Shape<0, 0, 0, 0, -1>;
 // shape-generic, but with the joint count fixed (= every slot of the NMAX-slot register arrays in use): the `slot < n`
 // tests of the unrolled Cholesky / substitution code fold away (a scalar compare + branch each otherwise)
@@ -802,26 +800,39 @@ __device__ unsigned long long mg_walker_phase_cycles[16];
 #define PHASE(i) do { } while (0)
 #endif
 
-struct WaveLds {   // pointers into the env's LDS slab
-    double *R, *o, *c, *p, *a;               // kinematics
-    double *fw, *fal, *fxr, *far_;           // frames after each body's joints
-    double *fvr;                             // (shape-generic kernels) velocity of the frame's reference point, for body damping
-    double *M, *h, *idg;                     // joint-space inertia (then its packed Cholesky factor), bias, 1/diag(L)
+struct WavePlan {   // what wave_plan() decides for a launch of the wave kernel beyond the topology
+    int maxr;       // constraint rows: 3 per kept contact + one per joint
+    bool overlay;   // the velocity-product frames sit at the end of the Jh block
+    int fd;         // doubles per body of velocity-product frames: the kernel's SH::fd
+    int rh, jr;     // rounds of the kinematics scans: 2^rh >= the longest chain of hops, 2^jr >= the longest chain of joints
+    int tail;       // byte offset of the model-constant tail: the slab's size
+};
+
+// The blocks of an env's LDS slab: pointers (WaveLds) or element offsets (doubles from the slab's start, ints from dend)
+template <class D, class I>
+struct WaveBlocks {
+    D R, o, c, p, a;                         // kinematics
+    D fw, fal, fxr, far_;                    // frames after each body's joints
+    D fvr;                                   // (fd == 15) velocity of the frame's reference point, for body damping
+    D M, h, idg;                             // joint-space inertia (then its packed Cholesky factor), bias, 1/diag(L)
                                              // vector, reciprocal Cholesky diagonal
-    double *q, *qd, *tau;
-    double *base;                            // pos[3] rot[9] vel[3] omega[3]
-    double *J, *bias, *diag, *lam;            // J: constraint rows, whitened in place (Jh = J L^-T)
-    double *cx;                              // per contact: ground (x, y, depth) or self (point xc, normal)
-    int *mask, *depth, *jstart, *jcount, *kids, *kind, *partner, *csphere, *misc, *dbody;
-    int *parent, *sbody, *sfoot;             // topology tables copied out of the kernarg segment: body_parent, sphere_body, sphere_foot
+    D q, qd, tau;
+    D base;                                  // pos[3] rot[9] vel[3] omega[3]
+    D J, bias, diag, lam;                    // J: constraint rows, whitened in place (Jh = J L^-T)
+    D cx;                                    // per contact: ground (x, y, depth) or self (point xc, normal)
+    D dend;                                  // end of the doubles
+    I mask, depth, jstart, jcount, kids, kind, partner, csphere, misc, dbody;
+    I parent, sbody, sfoot;                  // topology tables copied out of the kernarg segment: body_parent, sphere_body, sphere_foot
     // scan tables of the kinematics pass (wave_kinematics): a "hop" is one rigid transform of the chain — the fixed
     // offset of body b (hop b) or the rotation of joint j (hop nb + j)
-    int *hanc;                               // [rh][nb + nj]: the 2^r-th ancestor hop, -1 past the root
-    int *janc;                               // [jr][nj]: the 2^r-th ancestor JOINT of a joint (r = 0: the previous joint on the chain)
-    int *bjoint;                             // [nb]: last joint on the chain from the base to body b inclusive, -1 for none
-    int *hbody;                              // [nb + nj]: body whose final frame this hop is, -1 for none
-    int rh, jr;                              // rounds of the two scans (host: scan_rounds())
+    I hanc;                                  // [rh][nb + nj]: the 2^r-th ancestor hop, -1 past the root
+    I hbody;                                 // [nb + nj]: body whose final frame this hop is, -1 for none
+    I janc;                                  // [jr][nj]: the 2^r-th ancestor JOINT of a joint (r = 0: the previous joint on the chain)
+    I bjoint;                                // [nb]: last joint on the chain from the base to body b inclusive, -1 for none
+    I iend;                                  // end of the ints
+    int rh, jr;                              // rounds of the two scans (WavePlan)
 };
+using WaveLds = WaveBlocks<double *, int *>;
 
 // LDS layout. The solver works in Cholesky-whitened velocities y = L^T u (M = L L^T): with Jh = J L^-T
 //     J M^-1 J^T = Jh Jh^T,   J u = Jh y,   u += M^-1 J^T dl  <=>  y += Jh^T dl,
@@ -831,57 +842,56 @@ struct WaveLds {   // pointers into the env's LDS slab
 //    kinematics pass (12 doubles per hop), then the composite-rigid-body tables (16 doubles per body, 12 per generalized
 //    coordinate), then the capsules' world end points of the self-collision pass, all from its start; the velocity-
 //    product frames (fw/fal/fxr/far: 12 doubles per body, + v_ref in the shape-generic kernels) at its end
-//    (`overlay` says whether the frames fit too; mg_walker_step computes it from the topology);
+//    (`overlay` says whether the frames fit too; wave_plan decides it from the topology);
 //  * the solver's reciprocal diagonals and multipliers (diag, lam: 2 maxr doubles) are first written after the
 //    constraint rows are complete, when the body frames R / o / c (15 doubles per body) are dead until the
 //    next kinematics pass;
 //  * M and its Cholesky factor are only ever touched in the lower triangle: packed.
 // Humanoid: 33.2 KB in the first layout (4 envs per CU) -> 18.3 KB with the scan tables; the register file (2 waves per
 // SIMD) then caps the kernel at 8 envs per CU.
-__host__ __device__ inline bool wave_lds_alias2(int nb, int maxr) { return 2 * (size_t)maxr <= 15 * (size_t)nb; }
-// fd: doubles per body of velocity-product frames — 12 (w, alpha, x_ref, a_ref), 15 in the shape-generic kernels (+ v_ref)
-__host__ __device__ inline size_t wave_lds_doubles(int nb, int nj, int maxr, bool overlay, int fd = 12) {
-    const int n = 6 + nj;
-    return (size_t)nb * 15 + (size_t)nj * 6 + (overlay ? 0 : fd * (size_t)nb) + (size_t)n * (n + 1) / 2 + 2 * (size_t)n +
-           3 * (size_t)nj + 18 + (size_t)maxr * n + (wave_lds_alias2(nb, maxr) ? 1 : 3) * (size_t)maxr +
-           6 * (size_t)W_MAXC;
-}
-__host__ __device__ inline size_t wave_lds_ints(int nb, int nj, int ns, int maxr, int rh, int jr) {
-    return 6 * (size_t)nb + 2 * (size_t)ns + 2 * (size_t)maxr + 2 * W_MAXC + 8 + ND +
-           (size_t)(rh + 1) * (nb + nj) + (size_t)jr * nj + nb;      // scan tables: hanc, hbody, janc, bjoint
-}
 // doubles of a model row that precede the collision proxies: body frames, masses, inertias, joint anchors / axes / limits / ...
 __host__ __device__ inline size_t wave_model_doubles(int nb, int nj) { return 25 * (size_t)nb + 12 * (size_t)nj; }
-// doubles of the Jh block the kinematics pass uses as scratch: one 3x4 transform per hop (then the velocity scans)
-__host__ __device__ inline size_t wave_scan_doubles(int nb, int nj) { return 12 * (size_t)(nb + nj); }
-// doubles of the Jh block the M / h assembly uses as scratch (composite tables; + the frames when overlaid)
-__host__ __device__ inline size_t wave_assembly_doubles(int nb, int nj) { return 16 * (size_t)nb + 12 * (size_t)(6 + nj); }
 
-__device__ __forceinline__ WaveLds carve(unsigned char *smem, int nb, int nj, int ns, int maxr, bool overlay, int fd, int rh, int jr) {
-    const int n = 6 + nj;
-    WaveLds L;
-    double *d = reinterpret_cast<double *>(smem);
+// The layout, stated once. From the slab's base pointer it carves the slab (the kernel); from offset 0 it gives the host the
+// slab's size and the place of every block the phases borrow scratch from.
+__host__ __device__ inline int *wave_ints_at(double *d) { return reinterpret_cast<int *>(d); }
+__host__ __device__ inline int wave_ints_at(int) { return 0; }
+template <class D>
+__host__ __device__ __forceinline__ auto wave_layout(D d, int nb, int nj, int ns, WavePlan pl) {
+    const int n = 6 + nj, maxr = pl.maxr;
+    WaveBlocks<D, decltype(wave_ints_at(d))> L;
     L.R = d; d += 9 * nb; L.o = d; d += 3 * nb; L.c = d; d += 3 * nb; L.p = d; d += 3 * nj; L.a = d; d += 3 * nj;
-    double *ne = d;                       // Newton-Euler temporaries: own block, or the tail of the Jh block
-    if (!overlay) d += fd * nb;
+    D ne = d;                             // Newton-Euler temporaries: own block, or the tail of the Jh block
+    if (!pl.overlay) d += pl.fd * nb;
     L.M = d; d += n * (n + 1) / 2; L.h = d; d += n; L.idg = d; d += n;
     L.q = d; d += nj; L.qd = d; d += nj; L.tau = d; d += nj;
     L.base = d; d += 18;
     L.J = d; d += (size_t)maxr * n;       // constraint rows, whitened in place (Jh)
-    if (overlay) ne = d - fd * nb;
+    if (pl.overlay) ne = d - pl.fd * nb;
     L.fw = ne; ne += 3 * nb; L.fal = ne; ne += 3 * nb; L.fxr = ne; ne += 3 * nb; L.far_ = ne; ne += 3 * nb;
     L.fvr = ne;                           // only touched when fd == 15
     L.bias = d; d += maxr;
-    if (wave_lds_alias2(nb, maxr)) { L.diag = L.R; L.lam = L.R + maxr; }
+    if (2 * (size_t)maxr <= 15 * (size_t)nb) { L.diag = L.R; L.lam = L.R + maxr; }      // (R / o / c hold them)
     else { L.diag = d; d += maxr; L.lam = d; d += maxr; }
     L.cx = d; d += 6 * W_MAXC;
-    int *i = reinterpret_cast<int *>(d);
+    L.dend = d;
+    auto i = wave_ints_at(d);
     L.mask = i; i += nb; L.depth = i; i += nb; L.jstart = i; i += nb; L.jcount = i; i += nb; L.kids = i; i += nb;
     L.kind = i; i += maxr; L.partner = i; i += maxr; L.csphere = i; i += 2 * W_MAXC; L.misc = i; i += 8; L.dbody = i; i += ND;
     L.parent = i; i += nb; L.sbody = i; i += ns; L.sfoot = i; i += ns;
-    L.hanc = i; i += rh * (nb + nj); L.hbody = i; i += nb + nj; L.janc = i; i += jr * nj; L.bjoint = i; i += nb;
-    L.rh = rh; L.jr = jr;
+    L.hanc = i; i += pl.rh * (nb + nj); L.hbody = i; i += nb + nj; L.janc = i; i += pl.jr * nj; L.bjoint = i; i += nb;
+    L.iend = i;
+    L.rh = pl.rh; L.jr = pl.jr;
     return L;
+}
+
+// A WavePlan travels to the kernel as two ints, the kernarg layout the tuned kernels are tuned with: rows = maxr, negated when
+// overlay; scan = rh | jr << 8 | tail / 16 << 16. unpack() takes the fields a tuned shape fixes from SH, so they are literals there.
+struct WavePlanArgs { int rows, scan; };
+inline WavePlanArgs pack(const WavePlan &p) { return {p.overlay ? -p.maxr : p.maxr, p.rh | (p.jr << 8) | ((p.tail / 16) << 16)}; }
+template <class SH> __device__ __forceinline__ WavePlan unpack(int rows, int scan) {
+    return WavePlan{SH::nb ? 3 * W_MAXC + SH::nj : (rows < 0 ? -rows : rows), SH::overlay >= 0 ? SH::overlay != 0 : rows < 0, SH::fd,
+                    scan & 0xff, (scan >> 8) & 0xff, (scan >> 16) * 16};
 }
 
 __device__ __forceinline__ V3 ldv(const double *p, int i) { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
@@ -1343,7 +1353,7 @@ __device__ __forceinline__ void wave_substep(const mg_walker_topology &tp, const
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const int nchunk = GENERIC ? (ns + WV - 1) / WV : 1;
     const bool own_mu = GENERIC && prm.sphere_friction != nullptr;
-    const int cand_cap = min(W_MAXCAND, (maxr * n - 8 * m.ng) / 9);       // (mg_walker_step: = W_MAXCAND, or every possible candidate fits)
+    const int cand_cap = min(W_MAXCAND, (maxr * n - 8 * m.ng) / 9);       // (wave_plan: = W_MAXCAND, or every possible candidate fits)
     double *cand = L.J + 8 * m.ng;                                        // [cand_cap][8]
     int *cand_id = reinterpret_cast<int *>(cand + 8 * cand_cap);          // [cand_cap][2]
     int ncand = 0;
@@ -1841,19 +1851,20 @@ __device__ __forceinline__ void wave_substep(const mg_walker_topology &tp, const
 #ifndef MG_WALKER_A1_WAVES
 #define MG_WALKER_A1_WAVES 2      // ... and the 12-hinge quadruped's (<18, ShapeDof<12>>)
 #endif
+// Shape-generic kernels of robots with up to 12 joints (the A1) copy the row's body / joint constants into LDS behind the slab
+// (WavePlan::tail) once per launch: an exposed trip to L2 for each read before, 1 - 2.5 % of the A1's 13-sub-step launch. Larger
+// robots and the tuned kernels keep reading the table (their LDS decides how many envs fit a CU).
+template <int NMAX, class SH> constexpr bool WAVE_MODEL_IN_LDS = SH::nb == 0 && NMAX <= 18;
 template <int NMAX, class SH>
 __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 && SH::nb != 0) ? 3 : (SH::nb != 0 ? MG_WALKER_HUM_WAVES : ((NMAX == 18 && SH::nj == 12) ? MG_WALKER_A1_WAVES : 2))))) void walker_step_wave_kernel(mg_walker_topology tp, mg_walker_models ms,
                                                               mg_walker_params prm, mg_walker_state st, int n_envs,
-                                                              int maxr_flags, int scan_rounds, const float *action, float *obs,
+                                                              int plan_rows, int plan_scan, const float *action, float *obs,
                                                               float *reward, float *rewards5, uint8_t *done) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int e = mg::env_of_block(blockIdx.x, n_envs), lane = threadIdx.x;
     const int nb = SH::nb ? SH::nb : tp.n_bodies, nj = SH::nj ? SH::nj : tp.n_joints, ns = SH::nb ? SH::ns : tp.n_spheres;
     const int nf = tp.n_feet, obs_dim = 8 + 2 * nj + nf;
     const double *row = ms.table + (size_t)st.task_id[e] * ms.model_stride;
-    // sign of the row-count argument: assembly scratch overlaid on Jh
-    const bool overlay = SH::overlay >= 0 ? SH::overlay != 0 : maxr_flags < 0;
-    const int maxr = SH::nb ? 3 * W_MAXC + SH::nj : (maxr_flags < 0 ? -maxr_flags : maxr_flags);
     // The slab's base goes through a VGPR the optimiser cannot see into: every LDS access below is then
     // `ds_* v_base offset:<literal>`. Left as the symbol `smem`, each distinct constant address (hundreds in the
     // unrolled Cholesky / whitening loops) was materialised in its own SGPR, hoisted, and spilled to VGPR lanes.
@@ -1861,15 +1872,12 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
     asm volatile("" : "+v"(slab_off));
     unsigned char *slab = smem + slab_off;
     constexpr bool GENERIC = SH::nb == 0;      // shape-generic instantiation: terrain, > 64 proxies, per-proxy friction
-    constexpr bool VELF = GENERIC || SH::damp != 0;     // frames keep v_ref: body velocity damping available
-    const WaveLds L = carve(slab, nb, nj, ns, maxr, overlay, VELF ? 15 : 12, scan_rounds & 0xff, (scan_rounds >> 8) & 0xff);
-    // Shape-generic kernels of robots with up to 12 joints (the A1) copy the row's body / joint constants into LDS once per launch
-    // (behind the slab; its size arrives in the launch argument): every sub-step read them from global memory before — a wave runs
-    // latency-bound, and each of those loads was an exposed trip to L2. Worth 1 - 2.5 % of the A1's 13-sub-step launch; larger
-    // robots and the tuned kernels keep reading the table (their LDS decides how many envs fit a CU).
+    constexpr bool VELF = SH::fd == 15;        // frames keep v_ref: body velocity damping available
+    const WavePlan plan = unpack<SH>(plan_rows, plan_scan);
+    const WaveLds L = wave_layout(reinterpret_cast<double *>(slab), nb, nj, ns, plan);
     const double *mconst = row;
-    if (GENERIC && NMAX <= 18) {
-        double *mc = reinterpret_cast<double *>(slab + (size_t)(scan_rounds >> 16) * 16);
+    if (WAVE_MODEL_IN_LDS<NMAX, SH>) {
+        double *mc = reinterpret_cast<double *>(slab + plan.tail);
         for (int i = lane; i < (int)wave_model_doubles(nb, nj); i += WV) mc[i] = row[i];
         mconst = mc;
     }
@@ -1988,7 +1996,7 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
     }
     for (int it = 0; it < prm.frame_skip; ++it) {
         double *log_row = prm.substep_log ? prm.substep_log + ((size_t)it * (3 * nj + 7)) * n_envs + e : nullptr;
-        wave_substep<NMAX, GENERIC, VELF>(tp, m, prm, L, lane, maxr, touch, act, log_row, n_envs,
+        wave_substep<NMAX, GENERIC, VELF>(tp, m, prm, L, lane, plan.maxr, touch, act, log_row, n_envs,
                                     (st.foot_force != nullptr && it == prm.frame_skip - 1) ? st.foot_force + e : nullptr, nf,
                                     (GENERIC && prm.ext_wrench != nullptr && it == 0) ? prm.ext_wrench + e : nullptr, terrain, gvec, foot_mu);
     }
@@ -2138,7 +2146,6 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
     }
 }
 
-inline size_t ndof_of(const mg_walker_topology *tp) { return 6 + (size_t)tp->n_joints; }
 
 int check_walker(const mg_walker_topology *tp, const mg_walker_models *ms, const mg_walker_params *prm,
                  const mg_walker_state *st, int n) {
@@ -2169,6 +2176,96 @@ int check_walker(const mg_walker_topology *tp, const mg_walker_models *ms, const
         return mg::set_error(MG_ERR_NULL_POINTER, "mg_walker_state has a NULL array");
     if (!(prm->time_step > 0) || prm->frame_skip < 1 || prm->solver_iterations < 0)
         return mg::set_error(MG_ERR_BAD_CONFIG, "walker params");
+    return MG_OK;
+}
+
+// One launch of the wave kernel: the instantiation, its plan and its dynamic LDS (the slab, + the model-constant tail)
+struct WaveLaunch { decltype(&walker_step_wave_kernel<ND, ShapeAny>) kernel; bool model_in_lds; WavePlan plan; size_t lds; };
+template <int NMAX, class SH>
+void wave_use(WaveLaunch *w) { w->kernel = walker_step_wave_kernel<NMAX, SH>; w->model_in_lds = WAVE_MODEL_IN_LDS<NMAX, SH>; w->plan.fd = SH::fd; }
+
+// Every decision of a wave-mapping step, made on the host before anything is launched.
+int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const mg_walker_state *st, WaveLaunch *w) {
+    const int nb = tp->n_bodies, nj = tp->n_joints, ns = tp->n_spheres, ndof = 6 + nj;
+    if (ns > 128 || ndof > 64)
+        return mg::set_error(MG_ERR_BAD_SIZE, "wave mapping needs <= 128 collision proxies and <= 58 joints");
+    if (prm->foot_friction_env != nullptr && prm->sphere_friction == nullptr)
+        return mg::set_error(MG_ERR_BAD_CONFIG, "walker: foot_friction_env needs sphere_friction (per-proxy friction)");
+    WavePlan &p = w->plan;   // (the scan rounds are set below: they move only the ints, which the Jh checks do not read)
+    p = WavePlan{3 * W_MAXC + nj, false, 0, 0, 0, 0};
+    // the velocity-product frames take the tail of the Jh block when they fit behind the assembly scratch at its head
+    const int need = 16 * nb + 12 * ndof;      // composite-rigid-body tables: 16 doubles per body, 12 per coordinate
+    auto overlays = [&](int fd) {
+        const auto l = wave_layout(0, nb, nj, ns, WavePlan{p.maxr, true, fd, p.rh, p.jr, 0});
+        return l.J + need <= l.fw;
+    };
+    // The two robots MetaLocomotion ships run instantiations of their own, compiled for the overlay: the whole robot shape is
+    // then a literal in every LDS address and model-table offset. Terrain boxes, per-proxy friction and > 64 proxies (and the
+    // other options below) are compiled into the shape-generic instantiations only: the tuned kernels keep their registers.
+    using Humanoid = Shape<13, 17, 29, 17, 1>;
+    using Ant = Shape<13, 8, 25, 13, 1>;
+    using HumanoidDamped = Shape<13, 17, 29, 17, 1, 1>;     // + body velocity damping (the "bullet" preset, the envs' default)
+    using AntDamped = Shape<13, 8, 25, 13, 1, 1>;
+    const bool damped = prm->body_linear_damping != 0.0 || prm->body_angular_damping != 0.0;
+    const bool generic_only = prm->n_terrain_boxes != 0 || prm->sphere_friction != nullptr || prm->gravity_env != nullptr ||
+                              st->foot_force != nullptr || prm->actuation == 3 ||
+                              prm->pd_kp_env != nullptr || prm->pd_kd_env != nullptr || prm->ext_wrench != nullptr;
+    auto tuned = [&](auto shape) {
+        using S = decltype(shape);
+        return !generic_only && (S::damp != 0) == damped && nb == S::nb && nj == S::nj && ns == S::ns && tp->n_geoms == S::ng &&
+               overlays(S::fd);
+    };
+    // Any other robot: the substitution keeps its vector in registers, so the dof count is a template parameter (14 = ant,
+    // 18 = quadruped, 23 = humanoid, 30 = the ABI maximum), exact where the joint count fills the slots
+    if (tuned(Humanoid())) wave_use<23, Humanoid>(w);
+    else if (tuned(HumanoidDamped())) wave_use<23, HumanoidDamped>(w);
+    else if (tuned(Ant())) wave_use<14, Ant>(w);
+    else if (tuned(AntDamped())) wave_use<14, AntDamped>(w);
+    else if (ndof == 14) wave_use<14, ShapeDof<8>>(w);
+    else if (ndof < 14) wave_use<14, ShapeAny>(w);
+    else if (ndof == 18) wave_use<18, ShapeDof<12>>(w);       // a quadruped: 6 + 12 (the A1)
+    else if (ndof < 18) wave_use<18, ShapeAny>(w);
+    else if (ndof == 23) wave_use<23, ShapeDof<17>>(w);
+    else if (ndof < 23) wave_use<23, ShapeAny>(w);
+    else wave_use<ND, ShapeAny>(w);                           // (a 30-dof exact instantiation spills VGPRs)
+    p.overlay = overlays(p.fd);
+    auto lay = wave_layout(0, nb, nj, ns, p);
+    const int jh = lay.bias - lay.J;       // doubles of the Jh block
+    if (need > jh)
+        return mg::set_error(MG_ERR_UNSUPPORTED, "walker topology needs %zu scratch doubles for the mass-matrix "
+                             "assembly, the wave mapping has %zu: use mapping = lane", (size_t)need, (size_t)jh);
+    // the detection pass records its contact candidates in the Jh block behind the capsules' end points (9 doubles each):
+    // either W_MAXCAND of them fit, or every candidate this topology can produce does — the oracle's cap is then never reached
+    const size_t seg = 8 * (size_t)tp->n_geoms, cap = (size_t)jh > seg ? ((size_t)jh - seg) / 9 : 0;
+    const size_t possible = (size_t)ns * (prm->n_terrain_boxes > 0 ? 2 : 1) + (prm->self_collision ? (size_t)tp->n_pairs : 0);
+    if (cap < (size_t)W_MAXCAND && cap < possible)
+        return mg::set_error(MG_ERR_UNSUPPORTED, "walker topology: %zu contact candidates possible, the wave mapping has scratch for %zu "
+                             "(< %d): use mapping = lane", possible, cap, W_MAXCAND);
+    // rounds of the kinematics scans: 2^rh >= the longest chain of hops (body offsets + joints), 2^jr >= of joints
+    int hops[NB], joints[NB], j = 0;      // per body: hops / joints on the chain from the base, inclusive
+    for (int b = 0; b < nb; ++b) {
+        const int pb = tp->body_parent[b];
+        if (pb >= b) return mg::set_error(MG_ERR_BAD_CONFIG, "walker topology: body %d has parent %d (parents come first)", b, pb);
+        int cnt = 0;
+        while (j < nj && tp->joint_body[j] == b) { ++j; ++cnt; }
+        hops[b] = (pb < 0 ? 0 : hops[pb]) + 1 + cnt;
+        joints[b] = (pb < 0 ? 0 : joints[pb]) + cnt;
+        while ((1 << p.rh) < hops[b]) ++p.rh;
+        while ((1 << p.jr) < joints[b]) ++p.jr;
+    }
+    if (nj > 0 && p.jr < 1) p.jr = 1;     // round 0 of the joint table is also the "previous joint" table: always there
+    lay = wave_layout(0, nb, nj, ns, p);
+    // the kinematics scan borrows the head of the Jh block (one 3x4 transform per hop) while the frames it computes fill the tail
+    const int scan = 12 * (nb + nj), room = (p.overlay ? lay.fw : lay.bias) - lay.J;
+    if (scan > room)
+        return mg::set_error(MG_ERR_UNSUPPORTED, "walker topology: the kinematics scan needs %zu scratch doubles, the wave "
+                             "mapping has %zu: use mapping = lane", (size_t)scan, (size_t)room);
+    p.tail = (int)((lay.dend * sizeof(double) + lay.iend * sizeof(int) + 15) & ~size_t(15));
+    w->lds = p.tail + (w->model_in_lds ? wave_model_doubles(nb, nj) * sizeof(double) : 0);
+#ifdef MG_WALKER_LDS_FLOOR      /* timing experiment only (scripts/walker_occupancy_probe.py): fewer resident envs per CU */
+    if (const char *fl = getenv("MG_WALKER_LDS_FLOOR")) { const size_t f = (size_t)atol(fl); if (f > w->lds && f <= 64 * 1024) w->lds = f; }
+#endif
+    if (w->lds > 64 * 1024) return mg::set_error(MG_ERR_BAD_SIZE, "walker needs %zu B of LDS (> 64 KiB)", w->lds);
     return MG_OK;
 }
 
@@ -2224,108 +2321,10 @@ extern "C" int mg_walker_step(const mg_walker_topology *tp, const mg_walker_mode
                            (hipStream_t)stream, *tp, *ms, *prm, *st, n, action, obs, reward, rewards5, done);
         return mg::check_launch("walker_step_kernel");
     }
-    if (tp->n_spheres > 128 || 6 + tp->n_joints > 64)
-        return mg::set_error(MG_ERR_BAD_SIZE, "wave mapping needs <= 128 collision proxies and <= 58 joints");
-    const int maxr = 3 * W_MAXC + tp->n_joints;
-    using Humanoid = Shape<13, 17, 29, 17, 1>;
-    using Ant = Shape<13, 8, 25, 13, 1>;
-    using HumanoidDamped = Shape<13, 17, 29, 17, 1, 1>;     // + body velocity damping (the "bullet" preset, the envs' default)
-    using AntDamped = Shape<13, 8, 25, 13, 1, 1>;
-    // (terrain boxes, per-proxy friction and > 64 proxies are compiled into the shape-generic instantiations only: the
-    // tuned kernels keep their registers)
-    const bool damped = prm->body_linear_damping != 0.0 || prm->body_angular_damping != 0.0;
-    if (prm->foot_friction_env != nullptr && prm->sphere_friction == nullptr)
-        return mg::set_error(MG_ERR_BAD_CONFIG, "walker: foot_friction_env needs sphere_friction (per-proxy friction)");
-    const bool generic_only = prm->n_terrain_boxes != 0 || prm->sphere_friction != nullptr || prm->gravity_env != nullptr ||
-                              st->foot_force != nullptr || prm->actuation == 3 ||
-                              prm->pd_kp_env != nullptr || prm->pd_kd_env != nullptr || prm->ext_wrench != nullptr;
-    auto shape_is = [&](int b, int j, int s, int g) {
-        return !generic_only && tp->n_bodies == b && tp->n_joints == j && tp->n_spheres == s && tp->n_geoms == g;
-    };
-    bool tuned = shape_is(Humanoid::nb, Humanoid::nj, Humanoid::ns, Humanoid::ng) || shape_is(Ant::nb, Ant::nj, Ant::ns, Ant::ng);
-    int fd = (tuned && !damped) ? 12 : 15;           // velocity-product frame doubles per body (wave_lds_doubles)
-    // scratch use of the Jh block during the M / h assembly: the composite-rigid-body tables from the front and, when
-    // they also fit, the 12 doubles per body of velocity-product frames from the back
-    bool overlay = false;
-    {
-        const size_t block = (size_t)maxr * ndof_of(tp), need = wave_assembly_doubles(tp->n_bodies, tp->n_joints);
-        if (need > block)
-            return mg::set_error(MG_ERR_UNSUPPORTED, "walker topology needs %zu scratch doubles for the mass-matrix "
-                                 "assembly, the wave mapping has %zu: use mapping = lane", need, block);
-        overlay = need + fd * (size_t)tp->n_bodies <= block;
-        if (tuned && !overlay) {        // (cannot happen for the two shipped shapes; keeps host and kernel layouts in step)
-            tuned = false;
-            fd = 15;
-            overlay = need + fd * (size_t)tp->n_bodies <= block;
-        }
-    }
-    {   // the detection pass records its contact candidates in the Jh block behind the capsules' end points (9 doubles each):
-        // either W_MAXCAND of them fit, or every candidate this topology can produce does — the oracle's cap is then never reached
-        const size_t block = (size_t)maxr * ndof_of(tp), seg = 8 * (size_t)tp->n_geoms;
-        const size_t cap = block > seg ? (block - seg) / 9 : 0;
-        const size_t possible = (size_t)tp->n_spheres * (prm->n_terrain_boxes > 0 ? 2 : 1) + (prm->self_collision ? (size_t)tp->n_pairs : 0);
-        if (cap < (size_t)W_MAXCAND && cap < possible)
-            return mg::set_error(MG_ERR_UNSUPPORTED, "walker topology: %zu contact candidates possible, the wave mapping has scratch for %zu "
-                                 "(< %d): use mapping = lane", possible, cap, W_MAXCAND);
-    }
-    // rounds of the kinematics scans: 2^rh >= longest chain of hops (body offsets + joints), 2^jr >= longest chain of joints
-    int rh = 0, jr = 0;
-    {
-        int hops[NB], joints[NB], max_h = 0, max_j = 0, j = 0;      // per body: hops / joints on the chain from the base, inclusive
-        for (int b = 0; b < tp->n_bodies; ++b) {
-            const int pb = tp->body_parent[b];
-            if (pb >= b) return mg::set_error(MG_ERR_BAD_CONFIG, "walker topology: body %d has parent %d (parents come first)", b, pb);
-            int cnt = 0;
-            while (j < tp->n_joints && tp->joint_body[j] == b) { ++j; ++cnt; }
-            hops[b] = (pb < 0 ? 0 : hops[pb]) + 1 + cnt;
-            joints[b] = (pb < 0 ? 0 : joints[pb]) + cnt;
-            max_h = hops[b] > max_h ? hops[b] : max_h;
-            max_j = joints[b] > max_j ? joints[b] : max_j;
-        }
-        while ((1 << rh) < max_h) ++rh;
-        while ((1 << jr) < max_j) ++jr;
-        if (tp->n_joints > 0 && jr < 1) jr = 1;     // round 0 of the joint table is also the "previous joint" table: always there
-        if (wave_scan_doubles(tp->n_bodies, tp->n_joints) + (overlay ? fd * (size_t)tp->n_bodies : 0) > (size_t)maxr * ndof_of(tp))
-            return mg::set_error(MG_ERR_UNSUPPORTED, "walker topology: the kinematics scan needs %zu scratch doubles, the wave "
-                                 "mapping has %zu: use mapping = lane", wave_scan_doubles(tp->n_bodies, tp->n_joints),
-                                 (size_t)maxr * ndof_of(tp) - (overlay ? fd * (size_t)tp->n_bodies : 0));
-    }
-    size_t lds = wave_lds_doubles(tp->n_bodies, tp->n_joints, maxr, overlay, fd) * sizeof(double) +
-                 wave_lds_ints(tp->n_bodies, tp->n_joints, tp->n_spheres, maxr, rh, jr) * sizeof(int);
-    lds = (lds + 15) & ~size_t(15);
-    // shape-generic kernels of robots with <= 12 joints keep the body and joint constants of the env's model row in LDS for the whole
-    // launch (wave_model_doubles; the instantiations with NMAX <= 18)
-    const size_t lds_slab = lds;
-    if (!tuned && 6 + tp->n_joints <= 18) lds += wave_model_doubles(tp->n_bodies, tp->n_joints) * sizeof(double);
-#ifdef MG_WALKER_LDS_FLOOR      /* timing experiment only (scripts/walker_occupancy_probe.py): fewer resident envs per CU */
-    if (const char *fl = getenv("MG_WALKER_LDS_FLOOR")) { const size_t f = (size_t)atol(fl); if (f > lds && f <= 64 * 1024) lds = f; }
-#endif
-    const int maxr_flags = overlay ? -maxr : maxr;
-    if (lds > 160 * 1024) return mg::set_error(MG_ERR_BAD_SIZE, "walker needs %zu B of LDS", lds);
-    if (lds > 64 * 1024) return mg::set_error(MG_ERR_BAD_SIZE, "walker needs %zu B of LDS (> 64 KiB)", lds);
-    const int ndof = 6 + tp->n_joints;
-    // the substitution keeps its vector in registers, so the dof count is a template parameter:
-    // 14 = ant, 18 = quadruped, 23 = humanoid, 30 = the ABI maximum
-    // ... and so is the whole robot shape for the two robots MetaLocomotion ships (LDS addresses and model-table
-    // offsets become literals); any other topology runs the shape-generic instantiations
-    auto is_shape = [&](int b, int j, int s, int g) { return tuned && shape_is(b, j, s, g); };
-#define MG_WALKER_LAUNCH(NMAX_, SHAPE_)                                                                                  \
-    hipLaunchKernelGGL((walker_step_wave_kernel<NMAX_, SHAPE_>), dim3(n), dim3(WV), lds, (hipStream_t)stream, *tp, *ms, \
-                       *prm, *st, n, maxr_flags, rh | (jr << 8) | ((int)(lds_slab / 16) << 16), action, obs, reward, rewards5, done)
-    if (is_shape(Humanoid::nb, Humanoid::nj, Humanoid::ns, Humanoid::ng)) {
-        if (damped) MG_WALKER_LAUNCH(23, HumanoidDamped);
-        else MG_WALKER_LAUNCH(23, Humanoid);
-    } else if (is_shape(Ant::nb, Ant::nj, Ant::ns, Ant::ng)) {
-        if (damped) MG_WALKER_LAUNCH(14, AntDamped);
-        else MG_WALKER_LAUNCH(14, Ant);
-    }
-    else if (ndof == 14) MG_WALKER_LAUNCH(14, ShapeDof<8>);
-    else if (ndof < 14) MG_WALKER_LAUNCH(14, ShapeAny);
-    else if (ndof == 18) MG_WALKER_LAUNCH(18, ShapeDof<12>);  // a quadruped: 6 + 12 (the A1)
-    else if (ndof < 18) MG_WALKER_LAUNCH(18, ShapeAny);
-    else if (ndof == 23) MG_WALKER_LAUNCH(23, ShapeDof<17>);
-    else if (ndof < 23) MG_WALKER_LAUNCH(23, ShapeAny);
-    else MG_WALKER_LAUNCH(ND, ShapeAny);                      // (a 30-dof exact instantiation spills VGPRs)
-#undef MG_WALKER_LAUNCH
+    WaveLaunch w;
+    if (int rc = wave_plan(tp, prm, st, &w)) return rc;
+    const WavePlanArgs a = pack(w.plan);
+    hipLaunchKernelGGL(w.kernel, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan, action, obs,
+                       reward, rewards5, done);
     return mg::check_launch("walker_step_wave_kernel");
 }
