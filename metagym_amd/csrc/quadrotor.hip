@@ -161,14 +161,30 @@ __device__ __forceinline__ void inv3(const float *Af, float *Ainv, double *A) { 
 // after the last one (env.py:217), so the four f32 divisions behind it run in the last sub-step only.
 // RECIP: the host has established k.quality_recip_exact (stock quality 0.5), so f / quality is the multiply
 // by its exact reciprocal with no test in the sub-step.
-template <bool SIMPLE, bool RECIP = false>
+// XF: the host has established the stock X frame (config_is_xframe): prop_coord[i] = (sx_i c, sy_i c, 0) with signs
+// (+,+), (-,+), (-,-), (+,-) and one c > 0, so every lm[i] is the same. IEEE products are sign-symmetric
+// (x*(-c) == -(x*c) bit for bit), so the eight products of the four cz collapse to A = w0*c and B = w1*c, and the
+// eight torque products to the four T_i*c. The sums are written as the reference's own: w0*pc1 - w1*pc0 is A - B,
+// A - (-B) = A + B, (-A) - (-B) = B - A and (-A) - B, never a negated sum (-(A-B) differs from B-A in the sign of
+// a zero result).
+template <bool SIMPLE, bool RECIP = false, bool XF = false>
 __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *eff32, bool want_power) {
+    static_assert(!XF || SIMPLE, "the X frame is a SIMPLE configuration");
     float prop_force_z = 0.0f;
     float prop_torque[3] = {0.0f, 0.0f, 0.0f};
     float me[4], pp[4];
 
     // :147-148 body_velocity = Rinv @ v is identical for all four propellers; only [2] is used
     const double bvz = dot_row_f32f64(&s.Ri[6], s.v);
+    double xcz[4];
+    if (XF) {
+        const double c = (double)k.pc[1];
+        const double A = s.w[0] * c, B = s.w[1] * c;
+        xcz[0] = A - B;
+        xcz[1] = A + B;
+        xcz[2] = B - A;
+        xcz[3] = (-A) - B;
+    }
 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -180,8 +196,8 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
         float w_m = s.pw[i] + k.prec32 * d_prop_w;               // :144-145
         const float *pc = &k.pc[3 * i];
         // :149-151 (omega x coord)[2] * l_m, f64
-        double cz = s.w[0] * (double)pc[1] - s.w[1] * (double)pc[0];
-        double v_1 = bvz + cz * (double)k.lm[i];
+        double cz = XF ? xcz[i] : s.w[0] * (double)pc[1] - s.w[1] * (double)pc[0];
+        double v_1 = bvz + cz * (double)(XF ? k.lm[0] : k.lm[i]);
         float t0 = (k.ct0_32 * w_m) * w_m;                       // :154 f32 chain
         double t1 = (double)(k.ct1_32 * w_m) * v_1;              // :155 f32 product, widened
         double thrust = (double)t0 + t1;
@@ -192,7 +208,11 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
         s.pw[i] = w_m;                                           // :158
         prop_force_z = (float)((double)prop_force_z + thrust);   // :159 f64 add, f32 store
         const float T = (float)thrust;                           // :160-162 cross(-[0,0,T], coord)
-        if (SIMPLE) {
+        if (XF) {                                                // T*(+-c) = +-(T*c), the sums as above
+            const float Tc = T * k.pc[1];
+            prop_torque[0] = (i < 2) ? prop_torque[0] + Tc : prop_torque[0] - Tc;
+            prop_torque[1] = (i == 1 || i == 2) ? prop_torque[1] + Tc : prop_torque[1] - Tc;
+        } else if (SIMPLE) {
             prop_torque[0] += T * pc[1];
             prop_torque[1] += (-T) * pc[0];
         } else {
@@ -436,32 +456,72 @@ __global__ void quadrotor_targets_kernel(QuadK k, int nt, const float *actions, 
 
 // ---- SoA load / store ----------------------------------------------------------------------------
 
+// Every output of a step is written once and next read by a later launch (or by the caller), never by
+// this one: streaming (nontemporal) stores let the bytes leave through the fabric as they are issued
+// instead of waiting in L2 for the end-of-kernel write-back (-2..3 % at 65 536 envs).
+template <typename T> __device__ __forceinline__ void st_stream(T *p, T v) { __builtin_nontemporal_store(v, p); }
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+// BUF: element c of lane e in a [comps][n] array through a buffer resource over the whole array. The lane's byte
+// offset e*sizeof(T) is one VGPR per element size and the component's c*n*sizeof(T) a scalar soffset, so an access
+// costs no VALU; a flat address is two 64-bit VALU ops per access (v_mad_u64_u32 / v_lshl_add_u64), ~120 per step
+// on the prologue's and the epilogue's critical paths. Offsets are 32-bit: launch_plan picks BUF only when the
+// largest array of the launch (the [n][16] observation of a one-step launch) spans less than 2^31 bytes. Stores carry
+// aux = 2 (nt), the streaming policy of st_stream.
+constexpr int AUX_NT = 2;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void *base, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)bytes, 0x00020000);
+}
+template <typename T> __device__ __forceinline__ T buf_ld(__amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so) {
+    if constexpr (sizeof(T) == 4) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
+    else if constexpr (sizeof(T) == 8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
+    else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0));
+}
+template <int AUX, typename T> __device__ __forceinline__ void buf_st(T v, __amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so) {
+    if constexpr (sizeof(T) == 1) __builtin_amdgcn_raw_buffer_store_b8(__builtin_bit_cast(uint8_t, v), r, vo, so, AUX);
+    else if constexpr (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, vo, so, AUX);
+    else if constexpr (sizeof(T) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), r, vo, so, AUX);
+    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, vo, so, AUX);
+}
+template <bool BUF, typename T> __device__ __forceinline__ T ld_soa(const T *a, int comps, int n, int c, int e) {
+    if (!BUF) return a[(size_t)c * n + e];
+    return buf_ld<T>(rsrc_of(a, (uint32_t)comps * (uint32_t)n * sizeof(T)), (uint32_t)e * sizeof(T),
+                     (uint32_t)c * (uint32_t)n * sizeof(T));
+}
+template <bool BUF, typename T> __device__ __forceinline__ void st_soa(T *a, int comps, int n, int c, int e, T v) {
+    if (!BUF) return st_stream(&a[(size_t)c * n + e], v);
+    buf_st<AUX_NT>(v, rsrc_of(a, (uint32_t)comps * (uint32_t)n * sizeof(T)), (uint32_t)e * sizeof(T),
+                   (uint32_t)c * (uint32_t)n * sizeof(T));
+}
+
 // ROT_FIRST: issue rot, vel and omega ahead of the rest, in the order the derived values below consume them
-template <bool ROT_FIRST = false>
+template <bool ROT_FIRST = false, bool BUF = false>
 __device__ __forceinline__ void load_state(const mg_quadrotor_state &st, int n, int e, Lane &s, int &ct) {
     if (ROT_FIRST) {
 #pragma unroll
-        for (int c = 0; c < 9; ++c) s.R[c] = st.rot[(size_t)c * n + e];
+        for (int c = 0; c < 9; ++c) s.R[c] = ld_soa<BUF>(st.rot, 9, n, c, e);
     }
     if (!ROT_FIRST) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) s.p[c] = st.pos[(size_t)c * n + e];
+        for (int c = 0; c < 3; ++c) s.p[c] = ld_soa<BUF>(st.pos, 3, n, c, e);
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) s.v[c] = st.vel[(size_t)c * n + e];
+    for (int c = 0; c < 3; ++c) s.v[c] = ld_soa<BUF>(st.vel, 3, n, c, e);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) s.w[c] = st.omega[(size_t)c * n + e];
+    for (int c = 0; c < 3; ++c) s.w[c] = ld_soa<BUF>(st.omega, 3, n, c, e);
     if (ROT_FIRST) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) s.p[c] = st.pos[(size_t)c * n + e];
+        for (int c = 0; c < 3; ++c) s.p[c] = ld_soa<BUF>(st.pos, 3, n, c, e);
     }
 #pragma unroll
-    for (int c = 0; c < 4; ++c) s.pw[c] = st.propw[(size_t)c * n + e];
+    for (int c = 0; c < 4; ++c) s.pw[c] = ld_soa<BUF>(st.propw, 4, n, c, e);
     if (!ROT_FIRST) {
 #pragma unroll
-        for (int c = 0; c < 9; ++c) s.R[c] = st.rot[(size_t)c * n + e];
+        for (int c = 0; c < 9; ++c) s.R[c] = ld_soa<BUF>(st.rot, 9, n, c, e);
     }
-    ct = st.ct[e];
+    ct = ld_soa<BUF>(st.ct, 1, n, 0, e);
 }
 
 __device__ __forceinline__ void derive_lane(Lane &s) {
@@ -471,36 +531,34 @@ __device__ __forceinline__ void derive_lane(Lane &s) {
     s.power = 0.0f;
 }
 
+template <bool BUF = false>
 __device__ __forceinline__ void load_lane(const mg_quadrotor_state &st, int n, int e, Lane &s, int &ct) {
-    load_state(st, n, e, s, ct);
+    load_state<false, BUF>(st, n, e, s, ct);
     derive_lane(s);
 }
 
-// Every output of a step is written once and next read by a later launch (or by the caller), never by
-// this one: streaming (nontemporal) stores let the bytes leave through the fabric as they are issued
-// instead of waiting in L2 for the end-of-kernel write-back (-2..3 % at 65 536 envs).
-template <typename T> __device__ __forceinline__ void st_stream(T *p, T v) { __builtin_nontemporal_store(v, p); }
-typedef float v4f __attribute__((ext_vector_type(4)));
-
+template <bool BUF = false>
 __device__ __forceinline__ void store_lane(const mg_quadrotor_state &st, int n, int e, const Lane &s, int ct) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) st_stream(&st.pos[(size_t)c * n + e], s.p[c]);
+    for (int c = 0; c < 3; ++c) st_soa<BUF>(st.pos, 3, n, c, e, s.p[c]);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) st_stream(&st.vel[(size_t)c * n + e], s.v[c]);
+    for (int c = 0; c < 3; ++c) st_soa<BUF>(st.vel, 3, n, c, e, s.v[c]);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) st_stream(&st.omega[(size_t)c * n + e], s.w[c]);
+    for (int c = 0; c < 3; ++c) st_soa<BUF>(st.omega, 3, n, c, e, s.w[c]);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) st_stream(&st.propw[(size_t)c * n + e], s.pw[c]);
+    for (int c = 0; c < 4; ++c) st_soa<BUF>(st.propw, 4, n, c, e, s.pw[c]);
 #pragma unroll
-    for (int c = 0; c < 9; ++c) st_stream(&st.rot[(size_t)c * n + e], s.R[c]);
-    st_stream(&st.ct[e], ct);
+    for (int c = 0; c < 9; ++c) st_soa<BUF>(st.rot, 9, n, c, e, s.R[c]);
+    st_soa<BUF>(st.ct, 1, n, 0, e, ct);
 }
 
 // Transpose the wave's 64 x 16 observation rows through LDS and store them as 4 coalesced
 // dwordx4 sweeps (each wave instruction writes 1 KiB contiguous). Rows are padded to 17 floats so
 // the per-lane row writes hit distinct banks; a partial last wave falls back to per-row stores.
+// BUF (STEP_STOCK_SHADOW, where obs_dim is 16): the same stores through a buffer resource over the step's n rows.
+template <bool BUF = false>
 __device__ __forceinline__ void store_obs_wave(float *tile, const float *obs, float *out, int n, int e, int obs_dim) {
-    if (obs_dim != OBS_DIM) {   // velocity_control rows (19 floats) are not 16-byte aligned: plain row stores
+    if (!BUF && obs_dim != OBS_DIM) {   // velocity_control rows (19 floats) are not 16-byte aligned: plain row stores
         if (e < n)
             for (int c = 0; c < obs_dim; ++c) out[(size_t)e * obs_dim + c] = obs[c];
         return;
@@ -513,18 +571,26 @@ __device__ __forceinline__ void store_obs_wave(float *tile, const float *obs, fl
         for (int c = 0; c < OBS_DIM; ++c) tile[lane * (OBS_DIM + 1) + c] = obs[c];
         __builtin_amdgcn_wave_barrier();
         float4 *dst = reinterpret_cast<float4 *>(out + (size_t)wave_base * OBS_DIM);
+        const __amdgpu_buffer_rsrc_t r = rsrc_of(out, (uint32_t)n * (OBS_DIM * 4));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int q = j * mg::WAVE + lane;      // float4 index inside the wave's 4 KiB block
             const int row = q >> 2, col = (q & 3) * 4;
             const float *src = &tile[row * (OBS_DIM + 1) + col];
-            st_stream(reinterpret_cast<v4f *>(dst + q), v4f{src[0], src[1], src[2], src[3]});
+            const v4f v{src[0], src[1], src[2], src[3]};
+            if (BUF) buf_st<AUX_NT>(v, r, (uint32_t)(wave_base * OBS_DIM + 4 * lane) * 4 + j * (mg::WAVE * 16), 0);
+            else st_stream(reinterpret_cast<v4f *>(dst + q), v);
         }
         __builtin_amdgcn_wave_barrier();
     } else if (e < n) {
         float4 *dst = reinterpret_cast<float4 *>(out + (size_t)e * OBS_DIM);
+        const __amdgpu_buffer_rsrc_t r = rsrc_of(out, (uint32_t)n * (OBS_DIM * 4));
 #pragma unroll
-        for (int j = 0; j < 4; ++j) dst[j] = make_float4(obs[4 * j], obs[4 * j + 1], obs[4 * j + 2], obs[4 * j + 3]);
+        for (int j = 0; j < 4; ++j) {
+            const v4f v{obs[4 * j], obs[4 * j + 1], obs[4 * j + 2], obs[4 * j + 3]};
+            if (BUF) buf_st<0>(v, r, (uint32_t)e * (OBS_DIM * 4) + j * 16, 0);
+            else dst[j] = make_float4(v.x, v.y, v.z, v.w);
+        }
     }
 }
 
@@ -615,18 +681,26 @@ __device__ __forceinline__ KArgsC *kernargs_fresh() {
 //                      for every lane while the prologue loads are in flight, so the restart only moves values.
 //                      With more than one wave per SIMD the VALU is busy during the loads, and ~150 extra VALU on
 //                      every wave would cost more than the branch it saves.
+// Two options, also resolved on the host:
+//   XF   (both stock forms) the stock X frame of propellers (config_is_xframe, substep<>); any other SIMPLE layout
+//        keeps XF = false.
+//   BUF  (STEP_STOCK_SHADOW) state, action and outputs addressed through buffer resources (ld_soa / st_soa) when
+//        every array of the launch spans less than 2^31 bytes. Not in STEP_STOCK: there the step loop keeps the resources
+//        live across the sub-steps and the scalar file spills (14 / 36 SGPR spills with / without XF).
 enum StepForm { STEP_GENERIC = 0, STEP_STOCK = 1, STEP_STOCK_SHADOW = 2 };
 constexpr int STOCK_TIMES = 10;
 #ifndef MG_QUAD_SUBSTEP_UNROLL
 #define MG_QUAD_SUBSTEP_UNROLL 9   // of the first nine stock sub-steps (the tenth is peeled): 9 = straight-line, 1 = rolled
 #endif
 
-template <bool SIMPLE, int FORM>
+template <bool SIMPLE, int FORM, bool XF = false, bool BUF = false>
 __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadrotor_state st, StepIO io,
                                                                int n, int n_steps_arg) {
     constexpr bool STOCK = FORM != STEP_GENERIC;
     constexpr bool SHADOW = FORM == STEP_STOCK_SHADOW;
     static_assert(!STOCK || SIMPLE, "the stock forms are SIMPLE");
+    static_assert(STOCK || !XF, "XF is an option of the stock forms");
+    static_assert(SHADOW || !BUF, "BUF is an option of STEP_STOCK_SHADOW");
     const int n_steps = SHADOW ? 1 : n_steps_arg;
     __shared__ float tiles[WAVES_PER_BLOCK][mg::WAVE * (OBS_DIM + 1)];
     const int e = blockIdx.x * BLOCK + threadIdx.x;
@@ -656,9 +730,9 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         // then rot / vel / omega (inv3 and the norms), then the rest. The VALU would otherwise idle through the
         // ~2-3 k cycles of the prologue burst; the draw and the derived values fill it, each behind a partial
         // vmcnt wait. The sched_barriers keep the compiler from sinking the work to its first use.
-        episode = st.episode[el];
-        a_next = reinterpret_cast<const float4 *>(io.action)[el];
-        load_state<true>(st, n, el, s, ct);
+        episode = ld_soa<BUF>(st.episode, 1, n, 0, el);
+        a_next = ld_soa<BUF>(reinterpret_cast<const float4 *>(io.action), 1, n, 0, el);
+        load_state<true, BUF>(st, n, el, s, ct);
         __builtin_amdgcn_sched_barrier(0);
         rd = reset_draw(k, el, episode);
 #pragma unroll
@@ -700,11 +774,11 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         if (STOCK) {             // straight-line sub-steps (see StepForm); the first failure code is kept
 #pragma unroll MG_QUAD_SUBSTEP_UNROLL
             for (int it = 0; it < STOCK_TIMES - 1; ++it) {
-                substep<SIMPLE, true>(k, s, eff32, false);
+                substep<SIMPLE, true, XF>(k, s, eff32, false);
                 const int code = failure_code(k, s);
                 fail = fail ? fail : code;
             }
-            substep<SIMPLE, true>(k, s, eff32, true);
+            substep<SIMPLE, true, XF>(k, s, eff32, true);
             const int code = failure_code(k, s);
             fail = fail ? fail : code;
         } else {
@@ -786,19 +860,26 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         // observation arithmetic so that they drain behind it instead of after it.
         if (t == n_steps - 1 && live) {
             const mg_quadrotor_state &ste = *(const mg_quadrotor_state *)&kae->st;
-            store_lane(ste, n, e, s, ct);
-            if (episode != episode_in) st_stream(&ste.episode[e], episode);   // rare: only lanes that restarted
+            store_lane<BUF>(ste, n, e, s, ct);
+            if (episode != episode_in) st_soa<BUF>(ste.episode, 1, n, 0, e, episode);   // rare: only lanes that restarted
         }
         __builtin_amdgcn_sched_barrier(0);   // pure arithmetic would otherwise be hoisted above the stores
         float obs[OBS_DIM + 3];
         observe(ke, s, obs);
         if (vel_task) { obs[16] = ke.vtargets[3 * tn]; obs[17] = ke.vtargets[3 * tn + 1]; obs[18] = ke.vtargets[3 * tn + 2]; }
-        store_obs_wave(tile, obs, ioe.obs + off * ke.obs_dim, n, e, ke.obs_dim);
+        store_obs_wave<BUF>(tile, obs, ioe.obs + off * ke.obs_dim, n, e, ke.obs_dim);
         if (live) {
-            if (ioe.reward) st_stream(&ioe.reward[off + e], (float)reward);
-            if (ioe.reward64) st_stream(&ioe.reward64[off + e], reward);
-            st_stream(&ioe.done[off + e], (uint8_t)done);
-            if (ioe.failed) st_stream(&ioe.failed[off + e], (uint8_t)fail);
+            if (BUF) {   // one-step form: off == 0
+                if (ioe.reward) st_soa<true>(ioe.reward + off, 1, n, 0, e, (float)reward);
+                if (ioe.reward64) st_soa<true>(ioe.reward64 + off, 1, n, 0, e, reward);
+                st_soa<true>(ioe.done + off, 1, n, 0, e, (uint8_t)done);
+                if (ioe.failed) st_soa<true>(ioe.failed + off, 1, n, 0, e, (uint8_t)fail);
+            } else {
+                if (ioe.reward) st_stream(&ioe.reward[off + e], (float)reward);
+                if (ioe.reward64) st_stream(&ioe.reward64[off + e], reward);
+                st_stream(&ioe.done[off + e], (uint8_t)done);
+                if (ioe.failed) st_stream(&ioe.failed[off + e], (uint8_t)fail);
+            }
         }
     }
 }
@@ -942,6 +1023,18 @@ bool config_is_simple(const mg_quadrotor_config *c) {
     return c->ct2 == 0.0;
 }
 
+// the stock X frame of substep<XF>: prop_coord[i] = (sx_i c, sy_i c, 0), signs (+,+), (-,+), (-,-), (+,-), one c > 0
+// (then every lm[i] is the same number: the same three products summed in the same order)
+bool config_is_xframe(const mg_quadrotor_config *cfg) {
+    const float *pc = cfg->prop_coord;
+    const float c = pc[1];
+    const float sx[4] = {1.0f, -1.0f, -1.0f, 1.0f}, sy[4] = {1.0f, 1.0f, -1.0f, -1.0f};
+    if (!(c > 0.0f && c < INFINITY)) return false;
+    for (int i = 0; i < 4; ++i)
+        if (pc[3 * i] != sx[i] * c || pc[3 * i + 1] != sy[i] * c || pc[3 * i + 2] != 0.0f) return false;
+    return true;
+}
+
 int check_state(const mg_quadrotor_state *s) {
     if (!s->pos || !s->vel || !s->omega || !s->propw || !s->rot || !s->ct)
         return mg::set_error(MG_ERR_NULL_POINTER, "mg_quadrotor_state has a NULL array");
@@ -954,6 +1047,7 @@ struct Plan {
     uint32_t magic;
     int32_t n, device, simple;
     int32_t stock;   // STEP_STOCK applies (see StepForm)
+    int32_t xframe;  // ... with the X-frame option (see StepForm)
     int32_t simds;   // SIMDs of the device (0: unknown, STEP_STOCK_SHADOW is not used)
     QuadK k;
     mg_quadrotor_state st;
@@ -986,6 +1080,7 @@ int make_plan(Plan *p, const mg_quadrotor_config *cfg, const mg_quadrotor_autore
     // MG_QUAD_GENERIC=1 forces the generic kernel (A/B timing and tests); read per plan, so one process can hold both
     const bool force_generic = getenv("MG_QUAD_GENERIC") != nullptr;
     p->stock = (!force_generic && p->simple && p->k.quality_recip_exact && p->k.times == STOCK_TIMES && p->k.auto_reset) ? 1 : 0;
+    p->xframe = (p->stock && config_is_xframe(cfg)) ? 1 : 0;
     p->simds = 0;
     int cus = 0;
     if (p->device >= 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess)
@@ -1006,11 +1101,20 @@ int launch_plan(const Plan *p, int32_t n_steps, const float *action, float *obs,
     StepIO io{action, obs, reward, reward64, done, failed};
     const int n = p->n, grid = (n + BLOCK - 1) / BLOCK;
     const int waves = (n + mg::WAVE - 1) / mg::WAVE;
+    // BUF: 32-bit buffer offsets; the [n][16] f32 observation is the largest array a one-step launch touches
+    const bool buf = (uint64_t)n * (OBS_DIM * sizeof(float)) < (1ull << 31);
+    constexpr int SH = STEP_STOCK_SHADOW;
     decltype(&quadrotor_step_kernel<false, STEP_GENERIC>) kern;
-    if (p->stock && n_steps == 1 && waves <= p->simds) kern = quadrotor_step_kernel<true, STEP_STOCK_SHADOW>;
-    else if (p->stock) kern = quadrotor_step_kernel<true, STEP_STOCK>;
-    else if (p->simple) kern = quadrotor_step_kernel<true, STEP_GENERIC>;
-    else kern = quadrotor_step_kernel<false, STEP_GENERIC>;
+    if (p->stock && n_steps == 1 && waves <= p->simds) {
+        if (p->xframe) kern = buf ? quadrotor_step_kernel<true, SH, true, true> : quadrotor_step_kernel<true, SH, true, false>;
+        else kern = buf ? quadrotor_step_kernel<true, SH, false, true> : quadrotor_step_kernel<true, SH, false, false>;
+    } else if (p->stock) {
+        kern = p->xframe ? quadrotor_step_kernel<true, STEP_STOCK, true> : quadrotor_step_kernel<true, STEP_STOCK>;
+    } else if (p->simple) {
+        kern = quadrotor_step_kernel<true, STEP_GENERIC>;
+    } else {
+        kern = quadrotor_step_kernel<false, STEP_GENERIC>;
+    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, p->k, p->st, io, n, n_steps);
     return mg::check_launch("quadrotor_step_kernel");
 }
