@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 7
+#define MG_ABI_VERSION 8
 
 #define MG_OK 0
 #define MG_ERR_NULL_POINTER (-1001)
@@ -810,6 +810,36 @@ int mg_a1_action_filter(const mg_a1_filter_config *cfg, int32_t n_envs, double *
  * Every output may be NULL. pose [3][N], rot_mat [9][N], footposition [12][N], joint_angle [12][N], drpy [3][N], energy [N]. */
 int mg_a1_info(const mg_a1_actuator_config *cfg, int32_t n_envs, const mg_a1_actuator_state *state, double *pose,
                double *rot_mat, double *footposition, double *joint_angle, double *drpy, double *energy, void *stream);
+
+/* ========================================================================================
+ * MetaLM — replaces metagym/metalm/metalm.py data_generator / batch_generator (ABI 8)
+ * ======================================================================================== */
+
+/* MetaLM(V, n, l, e, L) with its mask_ratio attribute (0.30 in the reference). */
+typedef struct mg_metalm_params {
+    int32_t V;          /* vocabulary: tokens 1..V-1, separator V+1, mask 0 */
+    int32_t n;          /* elements per row */
+    int32_t L;          /* row length */
+    double l;           /* mean element length (Poisson) */
+    double e;           /* noise ratio */
+    double mask_ratio;  /* share of the noised tokens that become 0 */
+} mg_metalm_params;
+
+/* `batch` rows of data_generator(): features[b][0..L) and labels[b][0..L) (DEVICE int32 [batch][L]), bit for bit what the
+ * reference draws from numpy's legacy MT19937 stream.
+ *   mt_state == NULL (seeded):  row t comes from numpy.random.seed(s_t) with s_t = seeds[t] (DEVICE u32 [batch]) or
+ *                               seed_base + t when seeds is NULL; rows are independent and run in parallel.
+ *   mt_state != NULL (chained): DEVICE u32 [625] = the 624 key words and pos of numpy.random.get_state(); rows 0..batch-1
+ *                               come one after another from that stream (= numpy.random.set_state(st);
+ *                               batch_generator(batch)) and the stream is written back. seeds must be NULL.
+ * element_capacity bounds the tokens of one row's n elements (sum of max(3, poisson(l))), >= 3 n; the LDS it takes,
+ * 2496 + 8 (n + element_capacity) bytes, must fit 160 KiB (MG_ERR_UNSUPPORTED otherwise). A row whose elements need more is
+ * not generated: *overflow_row (DEVICE int32, written by this call) receives the smallest such row, INT32_MAX when there
+ * is none. In chained mode nothing after the first overflowing row is generated and mt_state is left unchanged.
+ * Reference asserts (n > 1, V > 1, l > 1, 0 < e < 1, L > 1) and V + 1 < 2^31 are checked: MG_ERR_BAD_CONFIG. */
+int mg_metalm_generate(const mg_metalm_params *params, int32_t batch, uint32_t seed_base, const uint32_t *seeds,
+                       uint32_t *mt_state, int32_t element_capacity, int32_t *features, int32_t *labels,
+                       int32_t *overflow_row, void *stream);
 
 #ifdef __cplusplus
 }

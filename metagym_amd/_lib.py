@@ -8,7 +8,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 MG_OK = 0
 
@@ -221,6 +221,12 @@ class A1FilterConfig(C.Structure):
                 ("b", (C.c_double * (A1_FILTER_MAX_HIST + 1)) * A1_NUM_MOTORS)]
 
 
+class MetaLMParams(C.Structure):
+    """mg_metalm_params"""
+    _fields_ = [("V", C.c_int32), ("n", C.c_int32), ("L", C.c_int32), ("l", C.c_double), ("e", C.c_double),
+                ("mask_ratio", C.c_double)]
+
+
 # symbol -> (restype, argtypes); tests/test_abi.py checks this list against include/metagym_hip.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -274,6 +280,7 @@ SIGNATURES = {
     "mg_a1_action_filter": (C.c_int, [C.POINTER(A1FilterConfig), C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "mg_a1_reward_step": (C.c_int, [C.POINTER(A1RewardConfig), C.c_int32, C.POINTER(A1RewardState), _P, _P, _P, _P, _P,
                                     _P, _P, _P, _P, _P, _P, _P]),
+    "mg_metalm_generate": (C.c_int, [C.POINTER(MetaLMParams), C.c_int32, C.c_uint32, _P, _P, C.c_int32, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 """Id -> constructor table mirroring the reference's gym.register calls
-(metagym/quadrotor/__init__.py:20-32, metagym/metamaze/__init__.py:21-54)."""
+(metagym/quadrotor/__init__.py:20-32, metagym/metamaze/__init__.py:21-54, metagym/metalm/__init__.py:18-27)."""
 import importlib
 
 registry = {}
@@ -46,3 +46,6 @@ register("meta-ant-v0", "metagym_amd.metalocomotion:MetaAntEnv",
 register("quadrupedal-v0", "metagym_amd.quadrupedal:A1GymEnv",
          kwargs={"action_limit": (0.75, 0.75, 0.75), "render": False, "on_rack": False, "random_dynamic": False, "ETG": 0, "ETG_T": 0.5,
                  "ETG_H": 20, "ETG_path": "", "task": "plane", "dynamic_param": {}})
+
+# metagym/metalm/__init__.py:18-27
+register("meta-lm-v0", "metagym_amd.metalm:MetaLM", kwargs={"V": 64, "n": 10, "l": 64, "e": 0.10, "L": 2048})
