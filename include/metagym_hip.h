@@ -222,7 +222,8 @@ typedef struct mg_maze_tasks {
      * hold food — those with food_interval > 0 or food_rewards > 1e-2 — in ascending order. Every other cell's
      * wait flag, counter and food value never change (maze_base.py:83-88 only acts on cells whose counter
      * drops below 0 after a wait flag was set), so visiting just this list is exact. */
-    const int16_t *food_cells;     /* [T][max_food] */
+    const int16_t *food_cells;     /* [T][max_food]; int16 cell indices: only for n*n <= 32768 (n <= 181), a list (or cell_slot)
+                                    * on a larger table is MG_ERR_BAD_SIZE — pass NULL there and the SURVIVAL arrays by cell */
     const int32_t *n_food;         /* [T] */
     int32_t max_food;
     /* (ABI 5) The same list once more, laid out for the lane-per-env 2-D kernel whose neighbouring lanes run DIFFERENT tasks
@@ -284,7 +285,10 @@ typedef struct mg_maze_view {
     int32_t max_ray_records;       /* optional bound on translucent records per ray (0 = 2n+1). A ray crosses
                                       at most 2*floor(max_vision / min cell_size) + 4 cells before it stops.
                                       Hard limit 127 (the count travels in 7 bits between the two render passes):
-                                      larger values, and 2n+1 > 127, are clamped to it */
+                                      an effective bound min(2n+1, max_ray_records) above 127 is MG_ERR_UNSUPPORTED
+                                      (clamping would drop the farthest cells of a long ray and change its pixels).
+                                      The launch's LDS must also fit 160 KiB (MG_ERR_BAD_SIZE naming the bytes): at
+                                      cell size 2 and a 32 x 32 frame that is n <= 124 */
     int32_t obs_format;            /* 0: int32 [N][res_h][res_v][3], the reference's dtype (values exceed 255);
                                       1: uint8 with saturation at 255 — a non-parity fast path (4x fewer HBM bytes) */
     double uniform_cell_size;      /* (ABI 5) > 0: the caller vouches that EVERY task of the table has exactly this cell_size (tasks

@@ -1100,6 +1100,11 @@ int check_tasks(const mg_maze_tasks *T, int task_type) {
         return mg::set_error(MG_ERR_NULL_POINTER, "SURVIVAL needs food_rewards and food_interval");
     if (task_type != MG_MAZE_SURVIVAL && task_type != MG_MAZE_ESCAPE)
         return mg::set_error(MG_ERR_BAD_CONFIG, "task_type %d", task_type);
+    // food_cells / cell_slot hold int16 cell indices: past 32 768 cells they would wrap negative and the kernels would index
+    // the food arrays out of bounds
+    if ((T->food_cells || T->cell_slot) && T->n * T->n > 32768)
+        return mg::set_error(MG_ERR_BAD_SIZE, "maze n=%d has %d cells: mg_maze_tasks.food_cells / cell_slot index at most 32 768 "
+                             "(n <= 181); pass NULL lists and the SURVIVAL arrays by cell", T->n, T->n * T->n);
     return MG_OK;
 }
 
@@ -1303,10 +1308,13 @@ extern "C" int mg_maze3d_step(const mg_maze_tasks *T, const mg_maze_view *view, 
     // at least one cell per step and stops at max_vision or at the maze border.
     vk.t_max = 2 * T->n + 1;
     if (view->max_ray_records > 0 && view->max_ray_records < vk.t_max) vk.t_max = view->max_ray_records;
-    // column_pass hands the record count to pixel_pass in 7 bits of the packed span word (span | n_tr << 24):
-    // more than 127 translucent cells on one ray needs n > 63 AND a vision range spanning them; capped, documented
-    // in metagym_hip.h (mg_maze_view.max_ray_records)
-    if (vk.t_max > 127) vk.t_max = 127;
+    // column_pass hands the record count to pixel_pass in 7 bits of the packed span word (span | n_tr << 24). A bound above
+    // 127 is refused: capping it would drop the farthest translucent cells of a long ray, and a far cell whose overlay
+    // strength differs from the nearer ones' changes the pixel (tests/test_maze_large_gpu.py renders one)
+    if (vk.t_max > 127)
+        return mg::set_error(MG_ERR_UNSUPPORTED, "maze n=%d: up to %d translucent cells per ray (min(2n+1, max_ray_records = %d)) "
+                             "but the renderer keeps at most 127; use a larger cell size or a shorter max_vision",
+                             T->n, vk.t_max, view->max_ray_records);
     // Waves per env (measured on MI355X, profiles/r04/maze3d_small_frames.txt; 256x256: profiles/r03/maze3d_waves_sweep.txt):
     // up to 64x64 one wave per env is fastest (32x32: 0.52 vs 0.60 ms with two at 65 536 envs, 64x64: 0.91 vs 0.95 — no
     // workgroup barrier partners, more independent envs resident per CU), 84x84 runs best with two, from 128x128 up with four.

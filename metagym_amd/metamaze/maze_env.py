@@ -15,6 +15,13 @@ Batched extensions
     construct the env with `auto_reset=True` (finished envs restart inside the same launch and the
     returned observation is the first one of the next episode).
   * rendering (`enable_render`, pygame god-view) is out of scope; the argument is accepted and ignored.
+
+Size limits (include/metagym_hip.h)
+  * 3 <= n <= 255 for every env. Above n = 181 (more than 32 768 cells) the int16 SURVIVAL food list cannot index the table:
+    the env passes none and MetaMaze2D keeps its SURVIVAL arrays by cell instead of by slot (exact, slower).
+  * 3-D: a ray keeps at most 127 translucent cells; min(2n+1, 2 * int(max_vision_range / cell size) + 5) above 127 (n >= 64 with
+    a cell size <= max_vision_range / 62) raises ValueError at set_task. The renderer's LDS must fit 160 KiB (n <= 124 at cell
+    size 2 and a small frame), else the first launch raises MetaGymHipError naming the bytes.
 """
 
 import numpy as np
@@ -27,6 +34,44 @@ from .maze_task import MAZE_TASK_MANAGER, DeviceTaskTable, TaskConfig, forget_wh
 PI = 3.1415926                      # dynamics.py:6
 DISCRETE_ACTIONS = [(-1, 0), (1, 0), (0, -1), (0, 1)]   # maze_env.py:14
 TASK_TYPES = {"ESCAPE": 0, "SURVIVAL": 1}
+MAX_RAY_RECORDS = 127              # translucent cells one ray of the 3-D renderer can record (mg_maze_view.max_ray_records)
+
+
+FOOD_LIST_MAX_CELLS = 32768        # mg_maze_tasks.food_cells / cell_slot hold int16 cell indices: n * n <= 32 768 (n <= 181)
+
+
+def food_lists(food_rewards, food_interval, by_slot):
+    """The optional SURVIVAL accelerator of mg_maze_tasks (include/metagym_hip.h) for a [T, n*n] task table, built with tensor ops
+    on the table's own device: `food_cells` (per task, the cells that can ever hold food — interval > 0 or food > 1e-2 — in
+    ascending order, int16 [T, max_food]), `n_food` (int32 [T]), `max_food`, and with `by_slot` the slot layout of the 2-D kernel:
+    `cell_slot` (int16 [T, n*n], the inverse map) and the listed cells' values slot-major, `slot_food` / `slot_interval`
+    ([max_food, T]). None when the table has more than FOOD_LIST_MAX_CELLS cells: int16 cannot index them (the library refuses
+    such lists), and the kernels sweep every cell instead — exact, only slower."""
+    import torch
+    T, nn = food_rewards.shape
+    if nn > FOOD_LIST_MAX_CELLS:
+        return None
+    dev = food_rewards.device
+    can = (food_interval > 0) | (food_rewards > 1.0e-2)                                      # [T, nn]
+    n_food = can.sum(dim=1).to(torch.int32)
+    max_food = max(1, int(n_food.max().item()))
+    order = torch.argsort((~can).to(torch.int8), dim=1, stable=True)[:, :max_food]   # food cells first, ascending
+    out = dict(food_cells=order.to(torch.int16).contiguous(), n_food=n_food.contiguous(), max_food=max_food)
+    if by_slot:
+        # the list once more for the lane-per-env kernel (mg_maze_tasks.cell_slot / slot_food / slot_interval): the inverse
+        # map cell -> slot, and the listed cells' task values slot-major, [max_food][T]
+        listed = torch.arange(max_food, device=dev).unsqueeze(0) < n_food.unsqueeze(1)              # [T, max_food]
+        # cells outside the list: -1 when the task's value there is exactly 0.0 (the kernel then reads nothing for them), -2 when
+        # it is a nonzero value <= 1e-2 (never eaten, never renewed, but part of the 2-D observation: read from the task)
+        slot = torch.where(food_rewards != 0.0, torch.full((T, nn), -2, dtype=torch.int16, device=dev),
+                           torch.full((T, nn), -1, dtype=torch.int16, device=dev))
+        ks = torch.arange(max_food, device=dev, dtype=torch.int16).unsqueeze(0).expand(T, max_food)
+        # only the LISTED entries of a row are written: a task with n_food < max_food has non-food cells in the tail of its
+        # `order` row, and those keep their -1 / -2 (ADVICE r4: a -1 there would hide a nonzero crumb from the observation)
+        slot.scatter_(1, order, torch.where(listed, ks, slot.gather(1, order)))        # (a row of `order` holds distinct cells)
+        out.update(cell_slot=slot.contiguous(), slot_food=torch.gather(food_rewards, 1, order).t().contiguous(),
+                   slot_interval=torch.gather(food_interval, 1, order).t().contiguous())
+    return out
 
 
 class _MazeBatch(object):
@@ -62,6 +107,7 @@ class _MazeBatch(object):
             n, T = task_config.n, task_config.n_tasks
             assert all(v.device == dev or (v.device.type == dev.type and (v.device.index or 0) == (dev.index or 0))
                        for v in task_config.tensors.values()), "task table lives on another device"
+            self._check_table(n, float(task_config.cell_size))       # before anything of this env changes
             self._task_t = task_config.tensors
             self.tasks = task_config
             self._min_cell_size = float(task_config.cell_size)
@@ -76,6 +122,7 @@ class _MazeBatch(object):
                 assert np.shape(t.cell_walls) == (n, n), "all tasks of one batch must have the same size"
                 assert 0 < t.agent_height < t.wall_height, "the agent height must be > 0 and < wall height"
                 assert np.shape(t.cell_walls) == np.shape(t.cell_texts), "the dimension of walls must be equal to textures"
+            self._check_table(n, min(float(t.cell_size) for t in tasks))   # before anything of this env changes
             host = dict(
                 start=np.asarray([t.start for t in tasks], np.int32).reshape(T, 2),
                 goal=np.asarray([t.goal for t in tasks], np.int32).reshape(T, 2),
@@ -101,31 +148,17 @@ class _MazeBatch(object):
         for k in host:
             setattr(c, k, self._task_t[k].data_ptr())
         # compact list of the cells that can ever hold food (exact shortcut for the SURVIVAL sweeps, see
-        # include/metagym_hip.h); built with device ops so a DeviceTaskTable never visits the host
-        tt_food, tt_int = self._task_t["food_rewards"], self._task_t["food_interval"]
-        can = (tt_int > 0) | (tt_food > 1.0e-2)                                  # [T, nn]
-        n_food = can.sum(dim=1).to(torch.int32)
-        max_food = max(1, int(n_food.max().item()))
-        order = torch.argsort((~can).to(torch.int8), dim=1, stable=True)[:, :max_food]   # food cells first, ascending
-        self._food_cells_t = order.to(torch.int16).contiguous()
-        self._n_food_t = n_food.contiguous()
-        c.food_cells, c.n_food, c.max_food = self._food_cells_t.data_ptr(), self._n_food_t.data_ptr(), max_food
-        self._max_food = max_food
-        if self._BY_SLOT:
-            # the list once more for the lane-per-env kernel (mg_maze_tasks.cell_slot / slot_food / slot_interval): the inverse
-            # map cell -> slot, and the listed cells' task values slot-major, [max_food][T]
-            listed = torch.arange(max_food, device=dev).unsqueeze(0) < n_food.unsqueeze(1)              # [T, max_food]
-            # cells outside the list: -1 when the task's value there is exactly 0.0 (the kernel then reads nothing for them), -2 when
-            # it is a nonzero value <= 1e-2 (never eaten, never renewed, but part of the 2-D observation: read from the task)
-            slot = torch.where(tt_food != 0.0, torch.full((T, nn), -2, dtype=torch.int16, device=dev),
-                               torch.full((T, nn), -1, dtype=torch.int16, device=dev))
-            ks = torch.arange(max_food, device=dev, dtype=torch.int16).unsqueeze(0).expand(T, max_food)
-            # only the LISTED entries of a row are written: a task with n_food < max_food has non-food cells in the tail of its
-            # `order` row, and those keep their -1 / -2 (a -1 there would hide a nonzero crumb from the observation)
-            slot.scatter_(1, order, torch.where(listed, ks, slot.gather(1, order)))        # (a row of `order` holds distinct cells)
-            self._cell_slot_t = slot.contiguous()
-            self._slot_food_t = torch.gather(tt_food, 1, order).t().contiguous()
-            self._slot_interval_t = torch.gather(tt_int, 1, order).t().contiguous()
+        # include/metagym_hip.h); built with device ops so a DeviceTaskTable never visits the host. The list and the slot map
+        # hold int16 cell indices: a table with more than 32 768 cells gets neither (the kernels then sweep every cell) and
+        # keeps its SURVIVAL arrays by cell
+        lists = food_lists(self._task_t["food_rewards"], self._task_t["food_interval"], self._BY_SLOT)
+        self._by_slot = lists is not None and "cell_slot" in lists
+        if lists is not None:
+            self._food_cells_t, self._n_food_t, self._max_food = lists["food_cells"], lists["n_food"], lists["max_food"]
+            c.food_cells, c.n_food, c.max_food = self._food_cells_t.data_ptr(), self._n_food_t.data_ptr(), self._max_food
+        if self._by_slot:
+            self._cell_slot_t, self._slot_food_t, self._slot_interval_t = (lists["cell_slot"], lists["slot_food"],
+                                                                           lists["slot_interval"])
             c.cell_slot, c.slot_food, c.slot_interval = (self._cell_slot_t.data_ptr(), self._slot_food_t.data_ptr(),
                                                          self._slot_interval_t.data_ptr())
         self._tasks_c = c
@@ -152,23 +185,28 @@ class _MazeBatch(object):
         if self._tt == TASK_TYPES["SURVIVAL"]:
             # [N, nn] cells for the workgroup-per-env 3-D kernel; [max_food, N] food SLOTS for the lane-per-env 2-D kernel
             # (mg_maze_state.food_by_slot: lane e's k-th access is coalesced whatever task it runs)
-            shape = (self._max_food, N) if self._BY_SLOT else (N, nn)
+            # (above the food-list bound the 2-D env keeps cells in the same lane-per-env order, [nn, N])
+            shape = (self._max_food, N) if self._by_slot else ((nn, N) if self._BY_SLOT else (N, nn))
             self.cur_food = torch.zeros(*shape, dtype=torch.float64, device=dev)
             self.wait_refresh = torch.zeros(*shape, dtype=torch.uint8, device=dev)
             self.revival = torch.zeros(*shape, dtype=torch.int32, device=dev)
             st.cur_food, st.wait_refresh, st.revival = (self.cur_food.data_ptr(), self.wait_refresh.data_ptr(),
                                                         self.revival.data_ptr())
             st.food_env_stride, st.food_cell_stride = (1, N) if self._BY_SLOT else (nn, 1)
-            st.food_by_slot = int(self._BY_SLOT)
+            st.food_by_slot = int(self._by_slot)
         self._state_c = st
         self._on_set_task()
         self.need_set_task = False
         self.need_reset = True
 
+    def _check_table(self, n, min_cell_size):
+        """Refuse a table this env cannot run, before set_task changes anything (a refused set_task leaves the env as it was)."""
+
     def _on_set_task(self):
         pass
 
-    _BY_SLOT = False
+    _BY_SLOT = False      # the class's SURVIVAL layout; _by_slot is the current table's (by cell above FOOD_LIST_MAX_CELLS)
+    _by_slot = False
     _STATE_KEYS = ("grid", "steps", "ori_idx", "ori", "loc", "life", "cur_food", "wait_refresh", "revival")
     _FOOD_KEYS = ("cur_food", "wait_refresh", "revival")
 
@@ -194,7 +232,7 @@ class _MazeBatch(object):
         sd = {}
         for k in self._STATE_KEYS:
             if hasattr(self, k):
-                sd[k] = self._food_by_cell(k) if (self._BY_SLOT and k in self._FOOD_KEYS) else getattr(self, k).clone()
+                sd[k] = self._food_by_cell(k) if (self._by_slot and k in self._FOOD_KEYS) else getattr(self, k).clone()
         if hasattr(self, "task_id"):
             sd["task_id"] = self.task_id.clone()
         return sd
@@ -205,7 +243,7 @@ class _MazeBatch(object):
         for k in self._STATE_KEYS:
             if hasattr(self, k) and k in sd:
                 dst, src = getattr(self, k), torch.as_tensor(sd[k]).to(self.device)
-                if self._BY_SLOT and k in self._FOOD_KEYS:
+                if self._by_slot and k in self._FOOD_KEYS:
                     if tuple(src.shape) != (self.n * self.n, self.num_envs):
                         raise ValueError("state_dict[%r] has shape %s, expected the by-cell view %s" % (k, tuple(src.shape), (self.n * self.n, self.num_envs)))
                     cells = self._food_cells_t[self.task_id.long()].t().long()   # [max_food, N]: the cell behind every slot
@@ -215,7 +253,7 @@ class _MazeBatch(object):
                     raise ValueError("state_dict[%r] has shape %s, this env holds %s (same num_envs and maze size n needed)"
                                      % (k, tuple(src.shape), tuple(dst.shape)))
                 dst.copy_(src.to(dst.dtype))
-        if self._BY_SLOT and hasattr(self, "revival") and all(k in sd for k in ("revival", "wait_refresh")):
+        if self._by_slot and hasattr(self, "revival") and all(k in sd for k in ("revival", "wait_refresh")):
             # the slot kernel never reads the counter of a slot that is not waiting (mg_maze_state.food_by_slot): a state with a
             # negative counter there cannot come out of reset() / step() — refuse it instead of diverging from maze_base.py:83-88
             if bool(((self.revival < 0) & (self.wait_refresh == 0)).any()):
@@ -298,6 +336,18 @@ class _Maze3D(_MazeBatch):
         self._obs = torch.zeros(self.num_envs, H, V, 3, dtype=obs_dtype, device=self.device)
         self._tex_version = None
 
+    def _max_ray_records(self, min_cell_size):
+        return 2 * int(self.max_vision_range / min_cell_size) + 5
+
+    def _check_table(self, n, min_cell_size):
+        # the renderer keeps at most 127 translucent cells per ray and mg_maze3d_step refuses a larger bound; said here, before
+        # set_task replaces the table — a view built for the previous table must never meet this one
+        bound = min(2 * n + 1, self._max_ray_records(min_cell_size))
+        if bound > MAX_RAY_RECORDS:
+            raise ValueError("maze n=%d with cell size %.17g at max_vision_range %g: a ray may cross %d translucent cells, the "
+                             "renderer keeps at most %d (n <= 63, or every cell size above max_vision_range / %d)"
+                             % (n, min_cell_size, self.max_vision_range, bound, MAX_RAY_RECORDS, (MAX_RAY_RECORDS - 5) // 2 + 1))
+
     def _on_set_task(self):
         self._build_view()
 
@@ -327,8 +377,7 @@ class _Maze3D(_MazeBatch):
         # DDA_2D (ray_caster_utils.py:31) stops once hit_dist >= max_vision: a ray crosses at most
         # floor(max_vision / cell_size) + 1 cell boundaries per axis plus the final overshoot, so it can
         # record at most 2*floor(mv/cs) + 4 translucent cells (incl. the start cell) whatever n is
-        min_cs = self._min_cell_size
-        v.max_ray_records = 2 * int(self.max_vision_range / min_cs) + 5
+        v.max_ray_records = self._max_ray_records(self._min_cell_size)
         v.uniform_cell_size = self._uniform_cell_size
         self._view_c = v
         self._tex_version = MAZE_TASK_MANAGER.version

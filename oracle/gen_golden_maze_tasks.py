@@ -28,6 +28,9 @@ CASES = [
     dict(n=11, allow_loops=True, crowd_ratio=0.0),
     dict(n=25, allow_loops=False, food_reward=0.3, food_interval=7),
     dict(n=31, allow_loops=True, crowd_ratio=0.5, step_reward=-0.02),
+    # appended: the device sampler's large sizes (n = 63 is its one launch above 64 KiB of LDS); earlier keys are unchanged
+    dict(n=41, allow_loops=True, crowd_ratio=0.35, food_density=0.3),
+    dict(n=63, allow_loops=False, food_density=0.05),
 ]
 SEEDS = list(range(10)) + [12345, 2 ** 31 - 1]
 

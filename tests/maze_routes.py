@@ -36,11 +36,19 @@ def _parse_waves(value):
     return w, (sl if sl in (32, 64) else SLAB)
 
 
+# sizeof of the kernel's LDS structs (maze.hip): EnvShared (Agent: 4 int + 2 double + 2 float, then reward, done, pos[2], s_ori,
+# c_ori) rounded up to 16, RowRec (3 double + 2 int, 16-aligned), ColRecLds (static_assert'ed 64)
+ENV_SHARED_LDS, ROW_REC, COL_REC_LDS = 96, 32, 64
+LDS_LIMIT = 160 * 1024
+
+
 def maze3d_route(n, res, cell_sizes, text_size=1.0, tex_size=64, obs_dtype="int32", knobs=None, max_vision=12.0,
                  fov=0.6 * PI):
     """The kernel instantiation and launch geometry mg_maze3d_step picks for a batch of n x n mazes whose tasks have the cell
     sizes `cell_sizes`, rendered at res = (res_h, res_v) by the Python env (which passes uniform_cell_size = the one cell size of
-    the table, or 0 when they differ). `knobs`: the process environment's MG_MAZE3D_* variables (name -> value)."""
+    the table, or 0 when they differ). `knobs`: the process environment's MG_MAZE3D_* variables (name -> value).
+    Also the per-ray record bound `t_max` (min(2n+1, the env's max_ray_records); above 127 the launch is refused) and the
+    dynamic LDS bytes `lds` the launch asks for (above LDS_LIMIT it is refused with MG_ERR_BAD_SIZE, naming this number)."""
     knobs = knobs or {}
     H, V = int(res[0]), int(res[1])
     px = H * V
@@ -73,8 +81,11 @@ def maze3d_route(n, res, cell_sizes, text_size=1.0, tex_size=64, obs_dtype="int3
             cbase = gbase + w * eff_slab if col_step == 1 else gbase + w
             ncols = min(eff_slab, H - cbase) if col_step == 1 else min(eff_slab, (H - cbase + n_waves - 1) // n_waves)
             idle += ncols <= 0
+    t_max = min(2 * n + 1, 2 * int(max_vision / min(float(c) for c in cell_sizes)) + 5)
+    lds = (ENV_SHARED_LDS + 8 * n * n + 4 * rec * slab * t_max * n_waves + 2 * ((n * n + 15) & ~15) +
+           ROW_REC * ((V + 63) & ~63) + 32 + (COL_REC_LDS * slab if small else 0))
     return dict(waves=n_waves, slab=slab, rec=rec, stock=stock, small=small, u8=u8, eff_slab=eff_slab,
-                chunks=(V + 63) // 64, idle_wave_groups=idle)
+                chunks=(V + 63) // 64, idle_wave_groups=idle, t_max=t_max, lds=lds)
 
 
 def route_key(r):
