@@ -807,15 +807,23 @@ class A1GymEnv(object):
         if kwargs:
             raise TypeError("step() got unexpected keywords %r (the reference's: d_yaw, donef)" % (sorted(kwargs),))
         m = reset_mask if reset_mask is not None else (self._pending if self.auto_reset else None)
+        obs_d_yaw = d_yaw
         if m is not None:
             m = torch.as_tensor(m, device=self.device).bool()
             at_reset = self._begin_partial_reset(m)
             action = action.masked_fill(m.reshape(-1, 1), 0.0)
-        obs, info = self._env_step(action, d_yaw=d_yaw, filter_init_mask=m)
+            # the hidden step of RewardShaping.reset is the INNER env's step, called without d_yaw (MonitorEnv.py:307): the
+            # restarting robots' yaw entry (ObservationWrapper.step :204-211) is taken against 0, and RewardShaping.step does not
+            # run for them, so the walking direction it keeps (vd2) stays where it was
+            if d_yaw is not None:
+                obs_d_yaw = torch.as_tensor(d_yaw, dtype=torch.float64, device=self.device).expand(self.num_envs).masked_fill(m, 0.0)
+            vd2 = self.shaping._t["vd2"].clone()
+        obs, info = self._env_step(action, d_yaw=obs_d_yaw, filter_init_mask=m)
         reward, done, terms = self.shaping.step(info["base"], info["pose"], info["rot_mat"], info["footposition"],
                                                 info["real_contact"], info["energy"], info["bad"], d_yaw)
         info.update(terms)
         if m is not None:
+            self.shaping._t["vd2"].copy_(torch.where(m, vd2, self.shaping._t["vd2"]))
             self.shaping.reset(*at_reset, mask=m)
             reward, done = reward.masked_fill(m, 0.0), done.masked_fill(m, False)
             info["reset"] = m.clone()       # (m may be the persistent auto-reset buffer, overwritten just below)

@@ -401,6 +401,39 @@ def foot_positions_in_base_frame(angles):
     return out + HIP_OFFSETS
 
 
+def euler_from_quaternion(q):
+    """getEulerFromQuaternion of the scripted Bullet client that recorded a1_env.npz (oracle/gen_golden_a1.py:104-107): no
+    normalisation, the asin argument clamped to [-1, 1]. (PyBullet's own conversion, restated in oracle/refstubs/pybullet,
+    normalises and snaps to pitch +-pi/2 near gimbal lock: DESIGN.md.)"""
+    x, y, z, w = (float(v) for v in q)
+    return np.array([math.atan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y)), math.asin(max(-1.0, min(1.0, 2 * (w * y - z * x)))),
+                     math.atan2(2 * (w * z + x * y), 1 - 2 * (y * y + z * z))])
+
+
+def rot_mat_from_euler(rpy):
+    """GetBaseOrientation (getQuaternionFromEuler of the pose, oracle/gen_golden_a1.py:99-102) and its row-major matrix
+    (getMatrixFromQuaternion, oracle/gen_golden_a1_env.py:69-71)."""
+    r, p, y = (float(v) for v in rpy)
+    cr, sr, cp, sp, cy, sy = math.cos(r / 2), math.sin(r / 2), math.cos(p / 2), math.sin(p / 2), math.cos(y / 2), math.sin(y / 2)
+    x, y, z, w = (sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy)
+    return np.array([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z),
+                     2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)])
+
+
+def info_from_control_obs(co, time_step=0.002, action_repeat=13):
+    """The `info` entries LocomotionGymEnv computes from one robot's delayed control observation [43]
+    (locomotion_gym_env.py:440-455,534-545): pose and rot_mat of its quaternion, foot FK and the wrapped angles of its motor
+    angles, drpy, and the energy of the step (GetEnergyConsumptionPerControlStep minitaur.py:812-820, summed left to right)."""
+    co = np.asarray(co, np.float64)
+    ang = map_to_minus_pi_to_pi(co[:NUM_MOTORS])
+    dot = 0.0
+    for i in range(NUM_MOTORS):
+        dot += co[2 * NUM_MOTORS + i] * co[NUM_MOTORS + i]
+    pose = euler_from_quaternion(co[3 * NUM_MOTORS:3 * NUM_MOTORS + 4])
+    return dict(pose=pose, rot_mat=rot_mat_from_euler(pose), footposition=foot_positions_in_base_frame(ang).reshape(-1),
+                joint_angle=ang, drpy=co[3 * NUM_MOTORS + 4:3 * NUM_MOTORS + 7].copy(), energy=abs(dot) * time_step * action_repeat)
+
+
 class A1Env(object):
     """The composition `A1GymEnv.reset / step` performs (envs/gym_envs/a1_gym_env.py, env_builder.py, MonitorEnv.py:14-25)
     around a physics the caller supplies as recorded world states. One robot. Pinned by tests/golden/a1_env.npz."""
