@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 8
+#define MG_ABI_VERSION 9
 
 #define MG_OK 0
 #define MG_ERR_NULL_POINTER (-1001)
@@ -844,6 +844,69 @@ typedef struct mg_metalm_params {
 int mg_metalm_generate(const mg_metalm_params *params, int32_t batch, uint32_t seed_base, const uint32_t *seeds,
                        uint32_t *mt_state, int32_t element_capacity, int32_t *features, int32_t *labels,
                        int32_t *overflow_row, void *stream);
+
+/* ========================================================================================
+ * Bandits — replaces metagym/bandits/bandits_env.py Bandits (ABI 9)
+ * ======================================================================================== */
+
+/* Task distributions of Bandits.sample_task. The reference's Uniform and Gaussian branches raise; they are defined here
+ * as its docstring intends: Uniform = clip((random_sample(K) - 0.5) * 3.464 + mean, 0, 1), Gaussian =
+ * clip(normal(mean, dev, size=K), 0, 1) with legacy gauss (its cached second value carries into the next call). */
+#define MG_BANDITS_NONE 0
+#define MG_BANDITS_CLASSICAL 1
+#define MG_BANDITS_UNIFORM 2
+#define MG_BANDITS_GAUSSIAN 3
+
+typedef struct mg_bandits_config {
+    int32_t arms;          /* K > 1 */
+    int32_t max_steps;     /* > 1 */
+    int32_t auto_reset;    /* mg_bandits_step: 1 = an env whose episode ends restarts inside the same launch */
+    int32_t distribution;  /* mg_bandits_sample_task: the distribution drawn (MG_BANDITS_NONE is MG_ERR_BAD_CONFIG);
+                              mg_bandits_step with auto_reset: the task an ending env draws before its restart
+                              (MG_BANDITS_NONE = keep the task) */
+    double mean, dev;
+    double classical_lo;   /* Classical only, computed by the caller in numpy's order: with fac = sqrt(K - 1), */
+    double classical_hi;   /* lo = clip(mean - dev / fac, 0, 1) and hi = clip(mean + fac * dev, 0, 1) */
+} mg_bandits_config;
+
+/* Device pointers, per env e of n_envs. The stream record breaks the structure-of-arrays convention on purpose: env e's
+ * numpy legacy stream is mt[e * 625 + 0..624) (the key words of numpy.random.get_state()) and mt[e * 625 + 624] (pos), so
+ * get_state / set_state are plain copies and a refill is one contiguous 2.5 KB block. */
+typedef struct mg_bandits_state {
+    uint32_t *mt;          /* [N][625] */
+    int32_t *has_gauss;    /* [N] the legacy gauss cache: get_state()[3] */
+    double *gauss;         /* [N] get_state()[4] */
+    double *gains;         /* [N][K] the task's expected gains */
+    int32_t *steps;        /* [N] steps of the running episode */
+    uint8_t *over;         /* [N] 1 = the episode is over or the task was set without a reset (the reference's need_reset) */
+} mg_bandits_state;
+
+/* numpy.random.seed(s_e) for every env: s_e = seeds[e] (DEVICE u32 [N]) or seed_base + e when seeds is NULL; pos = 624,
+ * has_gauss = 0, gauss = 0. Touches only mt, has_gauss and gauss. */
+int mg_bandits_seed(int32_t n_envs, uint32_t seed_base, const uint32_t *seeds, const mg_bandits_state *state, void *stream);
+
+/* Bandits.sample_task(cfg->distribution, cfg->mean, cfg->dev) for every env with mask[e] != 0 (mask NULL = all), drawn from
+ * the env's own stream: writes gains_out[e][0..K) (DEVICE f64 [N][K]; may be state->gains). Other envs draw nothing and
+ * their rows are not written. */
+int mg_bandits_sample_task(const mg_bandits_config *cfg, int32_t n_envs, const mg_bandits_state *state,
+                           const uint8_t *mask, double *gains_out, void *stream);
+
+/* Bandits.reset() for every env with mask[e] != 0 (mask NULL = all): steps = 0, over = 0. Draws nothing. */
+int mg_bandits_reset(const mg_bandits_config *cfg, int32_t n_envs, const mg_bandits_state *state, const uint8_t *mask,
+                     void *stream);
+
+/* n_steps >= 1 Bandits.step calls of every env in one launch. actions: DEVICE int32 [n_steps][N] (negative indices count
+ * from the end, as in the reference). Outputs, DEVICE [n_steps][N]: reward f32 (0 / 1, from one legacy double against
+ * gains[a]), done u8, info_steps i32 (steps before the increment), expected_gain f64 (gains[a]) and invalid u8:
+ *   0  the step ran;
+ *   1  the action is outside [-K, K) (the reference's IndexError);
+ *   2  the episode is over, or the task was set without a reset (the reference's "Must reset" exception).
+ * An invalid env draws nothing and keeps its state; its outputs are 0 except invalid and info_steps (its current steps).
+ * With cfg->auto_reset an env whose episode ends restarts in the same launch: with a distribution set it first draws its
+ * next task from its own stream, right after that step's draw (sample_task; set_task; reset), then steps = 0. */
+int mg_bandits_step(const mg_bandits_config *cfg, int32_t n_envs, const mg_bandits_state *state, int32_t n_steps,
+                    const int32_t *actions, float *reward, uint8_t *done, int32_t *info_steps, double *expected_gain,
+                    uint8_t *invalid, void *stream);
 
 #ifdef __cplusplus
 }

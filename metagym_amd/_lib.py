@@ -8,7 +8,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 MG_OK = 0
 
@@ -227,6 +227,18 @@ class MetaLMParams(C.Structure):
                 ("mask_ratio", C.c_double)]
 
 
+class BanditsConfig(C.Structure):
+    """mg_bandits_config"""
+    _fields_ = [("arms", C.c_int32), ("max_steps", C.c_int32), ("auto_reset", C.c_int32), ("distribution", C.c_int32),
+                ("mean", C.c_double), ("dev", C.c_double), ("classical_lo", C.c_double), ("classical_hi", C.c_double)]
+
+
+class BanditsState(C.Structure):
+    """mg_bandits_state (device pointers)"""
+    _fields_ = [("mt", C.c_void_p), ("has_gauss", C.c_void_p), ("gauss", C.c_void_p), ("gains", C.c_void_p),
+                ("steps", C.c_void_p), ("over", C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); tests/test_abi.py checks this list against include/metagym_hip.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -281,6 +293,11 @@ SIGNATURES = {
     "mg_a1_reward_step": (C.c_int, [C.POINTER(A1RewardConfig), C.c_int32, C.POINTER(A1RewardState), _P, _P, _P, _P, _P,
                                     _P, _P, _P, _P, _P, _P, _P]),
     "mg_metalm_generate": (C.c_int, [C.POINTER(MetaLMParams), C.c_int32, C.c_uint32, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "mg_bandits_seed": (C.c_int, [C.c_int32, C.c_uint32, _P, C.POINTER(BanditsState), _P]),
+    "mg_bandits_sample_task": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P, _P]),
+    "mg_bandits_reset": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P]),
+    "mg_bandits_step": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), C.c_int32, _P, _P, _P, _P,
+                                  _P, _P, _P]),
 }
 
 _lib = None

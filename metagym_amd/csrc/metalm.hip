@@ -28,10 +28,13 @@
 #include <cmath>
 
 #include "mg_common.h"
+#include "mg_mt19937.h"
 
 namespace {
 
-constexpr int MTN = 624, MTM = 397, SEG = MTN - MTM;   // SEG = 227
+using mt::MTN;
+using mt::refill;
+using mt::temper;
 constexpr size_t LDS_LIMIT = 160 * 1024;               // gfx950: LDS per CU, the most one workgroup can have
 
 struct MetaLMK {
@@ -45,49 +48,6 @@ struct MetaLMK {
     uint32_t seed_base;
 };
 
-__device__ __forceinline__ uint32_t temper(uint32_t y) {
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= y >> 18;
-    return y;
-}
-
-__device__ __forceinline__ uint32_t twist(uint32_t cur, uint32_t next, uint32_t far) {
-    const uint32_t y = (cur & 0x80000000u) | (next & 0x7fffffffu);
-    return far ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-}
-
-// words [lo, hi) of the new block; every read of the segment happens before any write (barrier), since lane i's
-// `next` word is lane i+1's output
-template <int LO, int HI>
-__device__ __forceinline__ void refill_segment(uint32_t *key, int lane) {
-    constexpr int R = (HI - LO + 63) / 64;
-    uint32_t v[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int i = LO + lane + 64 * r;
-        if (i < HI) {
-            const uint32_t next = key[i + 1 == MTN ? 0 : i + 1];
-            const uint32_t far = key[i + MTM >= MTN ? i + MTM - MTN : i + MTM];
-            v[r] = twist(key[i], next, far);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int i = LO + lane + 64 * r;
-        if (i < HI) key[i] = v[r];
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void refill(uint32_t *key, int lane) {
-    refill_segment<0, SEG>(key, lane);
-    refill_segment<SEG, 2 * SEG>(key, lane);
-    refill_segment<2 * SEG, MTN>(key, lane);
-}
-
 struct Stream {
     uint32_t *key;   // LDS [624]
     int pos;         // wave-uniform; 624 = refill before the next draw
@@ -99,8 +59,8 @@ struct Stream {
         return temper(key[pos++]);
     }
     __device__ __forceinline__ double next_double() {
-        const uint32_t a = next() >> 5, b = next() >> 6;
-        return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+        const uint32_t a = next();
+        return mt::to_double(a, next());
     }
     __device__ __forceinline__ uint32_t bounded(uint32_t rng, uint32_t mask) {
         if (rng == 0) return 0;                   // consumes nothing
@@ -145,13 +105,12 @@ struct Stream {
             refill(key, lane);
             const uint32_t b = temper(key[0]);
             pos = 1;
-            d = ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
+            d = mt::to_double(a, b);
             return 1;
         }
         const int cnt = min(want, min(64, avail >> 1));
         const int j = pos + 2 * min(lane, cnt - 1);
-        const uint32_t a = temper(key[j]) >> 5, b = temper(key[j + 1]) >> 6;
-        d = ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+        d = mt::to_double(temper(key[j]), temper(key[j + 1]));
         pos += 2 * cnt;
         return cnt;
     }
@@ -281,7 +240,7 @@ __global__ __launch_bounds__(64) void metalm_seeded_kernel(MetaLMK k, int batch,
         uint32_t p = seed;
         s.key[0] = p;
         for (int i = 1; i < MTN; ++i) {
-            p = 1812433253u * (p ^ (p >> 30)) + (uint32_t)i;
+            p = mt::seed_step(p, i);
             s.key[i] = p;
         }
     }
@@ -317,11 +276,6 @@ __global__ __launch_bounds__(64) void metalm_chained_kernel(MetaLMK k, int batch
 // generator key, element lengths and offsets, element tokens, chunk scratch (an element is at most `cap` long)
 size_t lds_bytes(int64_t n, int64_t cap) { return sizeof(uint32_t) * MTN + sizeof(int32_t) * (2 * n + 2 * cap); }
 
-uint32_t gen_mask(uint32_t r) {
-    r |= r >> 1; r |= r >> 2; r |= r >> 4; r |= r >> 8; r |= r >> 16;
-    return r;
-}
-
 }  // namespace
 
 extern "C" int mg_metalm_generate(const mg_metalm_params *p, int32_t batch, uint32_t seed_base, const uint32_t *seeds,
@@ -353,8 +307,8 @@ extern "C" int mg_metalm_generate(const mg_metalm_params *p, int32_t batch, uint
 
     MetaLMK k{};
     k.V = p->V; k.n = p->n; k.L = p->L; k.cap = element_capacity;
-    k.rng_tok = (uint32_t)(p->V - 2); k.mask_tok = gen_mask(k.rng_tok);
-    k.rng_idx = (uint32_t)(p->n - 2); k.mask_idx = gen_mask(k.rng_idx);
+    k.rng_tok = (uint32_t)(p->V - 2); k.mask_tok = mt::bound_mask(k.rng_tok);
+    k.rng_idx = (uint32_t)(p->n - 2); k.mask_idx = mt::bound_mask(k.rng_idx);
     k.lam = p->l; k.e = p->e; k.mask_ratio = p->mask_ratio;
     k.ptrs = p->l >= 10;
     // random_poisson_ptrs' per-call constants and random_poisson_mult's exp(-lam), with the host's libm as numpy has them

@@ -1,5 +1,6 @@
 """Id -> constructor table mirroring the reference's gym.register calls
-(metagym/quadrotor/__init__.py:20-32, metagym/metamaze/__init__.py:21-54, metagym/metalm/__init__.py:18-27)."""
+(metagym/quadrotor/__init__.py:20-32, metagym/metamaze/__init__.py:21-54, metagym/metalm/__init__.py:18-27,
+metagym/bandits/__init__.py:18-24)."""
 import importlib
 
 registry = {}
@@ -49,3 +50,6 @@ register("quadrupedal-v0", "metagym_amd.quadrupedal:A1GymEnv",
 
 # metagym/metalm/__init__.py:18-27
 register("meta-lm-v0", "metagym_amd.metalm:MetaLM", kwargs={"V": 64, "n": 10, "l": 64, "e": 0.10, "L": 2048})
+
+# metagym/bandits/__init__.py:18-24
+register("bandits-v0", "metagym_amd.bandits:Bandits", kwargs={"arms": 50, "max_steps": 1000})
