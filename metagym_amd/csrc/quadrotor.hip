@@ -963,10 +963,19 @@ int fold_config(const mg_quadrotor_config *c, QuadK *k, bool need_targets = true
     {
         // np.linalg.norm(pos) > fail_range, both f32 (quadrotorsim.py:213). sqrtf is monotone and
         // correctly rounded, so  sqrtf(s) > T  <=>  s > S  with S = max{ x : sqrtf(x) <= T }.
+        // The search cannot reach two ends: T < 0 (every sum fails; sqrtf(0) > T holds for ever) and T = +inf
+        // (nothing fails; nextafterf(inf, inf) is inf). T = -0.0 gives S = 0 and NaN gives S = NaN, as they should.
         const float T = (float)c->fail_range;
-        float S = T * T;
-        while (sqrtf(S) > T) S = nextafterf(S, 0.0f);
-        while (sqrtf(nextafterf(S, INFINITY)) <= T) S = nextafterf(S, INFINITY);
+        float S;
+        if (T < 0.0f) {
+            S = -INFINITY;
+        } else if (T == INFINITY) {
+            S = INFINITY;
+        } else {
+            S = T * T;
+            while (sqrtf(S) > T) S = nextafterf(S, 0.0f);
+            while (sqrtf(nextafterf(S, INFINITY)) <= T) S = nextafterf(S, INFINITY);
+        }
         k->fail_range_sq32 = S;
     }
     for (int i = 0; i < 4; ++i) {
