@@ -24,13 +24,20 @@ Envs shard across GPUs with no data-path collective (weak scaling). torch.distri
 the **gloo** backend and used only for the timing barrier and the max-over-ranks reduction of one float:
 there is no RCCL anywhere in the harness or the step path (north_star: "independent batches, no RCCL").
 
+A plain run does only what the headline needs: it sets up, warms up, times the K steps (both launch modes under
+`--launch auto`), writes the outputs if --dump-outputs is given and prints the line. `--full` adds everything else, after
+the headline has been measured and the outputs written, so neither depends on it: the in-run rocprofv3 --pmc passes, the
+hipGraph launch-cost fit, the figures quoted from profiles/, the secondary workloads and the CPU baselines. `--no-pmc`,
+`--no-secondary` and `--no-cpu-baseline` leave parts of that out again.
+
 Prints ONE JSON line on rank 0.
   value        whole-job env-steps/s = envs stepped by all ranks * steps / max-over-ranks wall time
   roofline     algorithmic bytes per launch (317 B/env-step) / average kernel-launch
-               duration measured with HIP events on the launching stream, vs the 8 TB/s HBM peak
-  cpu_baseline the UNMODIFIED reference Quadrotor.step, one single-env worker process per host core (kind "reference":
-               imported from oracle/_ref, the byte-compiled copy oracle/make_ref.py builds and ships); the C port of it
-               (oracle/) beside it as cpu_port — and alone (kind "port") only if oracle/_ref is missing
+               duration measured with HIP events on the launching stream, vs the 8 TB/s HBM peak; with --full also the
+               HBM traffic and VALU instruction count of this run's counter passes
+  cpu_baseline with --full: the UNMODIFIED reference Quadrotor.step, one single-env worker process per host core (kind
+               "reference": imported from oracle/_ref, the byte-compiled copy oracle/make_ref.py builds and ships); the C
+               port of it (oracle/) beside it as cpu_port — and alone (kind "port") only if oracle/_ref is missing
   dump_outputs with --dump-outputs DIR: where the last timed step's outputs were written (DIR/<name>.npy) and their shapes
 """
 import argparse
@@ -997,8 +1004,11 @@ def main(argv=None):
                     help="auto (default): the K timed steps are run twice, replayed as one hipGraph and as K eager launches, each in its "
                          "own barrier-bracketed region; the mode with the higher whole-job throughput is the line's value, the other "
                          "is recorded under sanity.other_launch_mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C1/C3/C4 side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the in-run counter passes, the hipGraph launch-cost fit, the figures quoted from "
+                         "profiles/, the secondary workloads and the CPU baselines (a plain run measures the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the C1/C3/C4 side measurements")
     ap.add_argument("--preroll", type=int, default=None,
                     help="untimed steps that bring the batch to its steady episode-age mix (default: nt = 1000)")
     ap.add_argument("--single-gpu-value", type=float, default=None,
@@ -1006,7 +1016,8 @@ def main(argv=None):
     ap.add_argument("--self-baseline", action="store_true",
                     help="with N > 1 ranks: rank 0 first times the same K steps ALONE (the other ranks idle at a barrier), so the line "
                          "carries efficiency = value(N) / (N * solo value) without a prior --single-gpu-value run")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc passes (VALU instruction count, HBM traffic)")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="with --full: skip the in-run rocprofv3 --pmc passes (VALU instruction count, HBM traffic)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--plan-only", action="store_true",
                     help="rendezvous + shard plans only, on CPU (what tests/test_distributed_cpu.py drives); no GPU work")
@@ -1166,7 +1177,7 @@ def main(argv=None):
     # of 10 K steps, each replayed a few times between synchronisations; T(K) = a + b K gives the per-step cost b of a long run and
     # the fixed cost a of ONE timed region (graph launch, first-dispatch latency after an idle queue, completion wake-up).
     graph_fit = None
-    if not mixed and world == 1 and args.launch != "eager":
+    if args.full and not mixed and world == 1 and args.launch != "eager":
         try:
             def replay_wall(g, reps=5):
                 best_w, best_d = 1e9, 1e9
@@ -1219,6 +1230,7 @@ def main(argv=None):
                         "1.5e-5 (state) / 8.3e-5 (Euler-angle observation) over tumbling 400 - 1 000-step rollouts "
                         "(profiles/r03/numpy_pin_gap.txt); the kernel has no numpy-1.22 mode",
             "data": "synthetic",
+            "full": args.full,
         }
         out.update(scaling_fields(value, world, envs_per_rank, args.steps, rank_walls, solo_wall, args.single_gpu_value))
         if dumped is not None:
@@ -1242,7 +1254,8 @@ def main(argv=None):
                                        "against the 8 TB/s HBM peak. The kernel is NOT HBM-bound: `valu_issue` is the fraction of "
                                        "the VALU issue rate (one wave-instruction per 4 clk per SIMD, 1024 SIMDs at 2.4 GHz) its "
                                        "measured instruction count reaches in that same duration; `bound` names the larger"}
-            pmc = {} if (args.no_pmc or world != 1) else pmc_prepass(n)
+            skip_pmc = not args.full or args.no_pmc or world != 1
+            pmc = {} if skip_pmc else pmc_prepass(n)
             if "hbm_bytes_per_launch" in pmc:
                 out["roofline"]["traffic"] = pmc["hbm_bytes_per_launch"]
                 out["roofline"]["traffic_over_algorithmic"] = pmc["hbm_bytes_per_launch"] / float(BYTES_PER_ENV_STEP * n)
@@ -1271,7 +1284,7 @@ def main(argv=None):
                     out["roofline"]["bound"] = "valu_issue"
                 out["roofline"]["bound_frac"] = max(ach / peak_issue, out["roofline"]["frac"])
             if pmc.get("errors") or not pmc:
-                out["roofline"]["pmc_passes"] = {"skipped": bool(args.no_pmc or world != 1), "errors": pmc.get("errors")}
+                out["roofline"]["pmc_passes"] = {"skipped": skip_pmc, "errors": pmc.get("errors")}
             elif "pass_seconds" in pmc:
                 out["roofline"]["pmc_pass_seconds"] = pmc["pass_seconds"]
         else:
@@ -1298,9 +1311,9 @@ def main(argv=None):
         if graph_fit and "fixed_us_per_timed_region_host_wall" in graph_fit:
             out["graph_launch_us"] = graph_fit["fixed_us_per_timed_region_host_wall"]
             out["kernel_us_per_step_long_run"] = graph_fit["per_step_us_hip_events"]
-        if not mixed:
+        if args.full and not mixed:
             out["from_profiles"] = from_profiles(n, launch_s)
-        if world == 1 and not args.no_secondary and not mixed:
+        if args.full and world == 1 and not args.no_secondary and not mixed:
             del quad
             torch.cuda.empty_cache()
             ipw_run = out.get("roofline", {}).get("valu_issue", {}).get("valu_insts_per_wave")
@@ -1330,7 +1343,7 @@ def main(argv=None):
                 v = pick(key, *path)
                 if v is not None:
                     out[name] = v
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             port = cpu_port()
             ref, why = cpu_reference()
             if ref is not None:

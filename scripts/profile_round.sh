@@ -56,13 +56,13 @@ fi
 if has a1; then
   # every secondary workload of bench.py under the tracer: the a1_* kernels (Quadrupedal actuation / wrappers) among them
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/a1_trace -o a -- \
-          python bench.py --no-cpu-baseline --steps 50 --warmup 5 > $OUT/a1_trace.log 2>&1
+          python bench.py --full --no-cpu-baseline --no-pmc --steps 50 --warmup 5 > $OUT/a1_trace.log 2>&1
 fi
 if has bench; then
   python bench.py --steps 20 --warmup 5 > $OUT/bench_20steps.json 2> $OUT/bench_20steps.err      # the driver's command
-  python bench.py > $OUT/bench.json 2> $OUT/bench.err
-  python bench.py --launch eager --no-secondary --no-cpu-baseline > $OUT/bench_eager.json 2> $OUT/bench_eager.err
-  BENCH_FORCE_DIST=1 python bench.py --no-secondary --no-cpu-baseline > $OUT/bench_force_dist.json 2> $OUT/bench_force_dist.err
+  python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+  python bench.py --full --launch eager --no-secondary --no-cpu-baseline > $OUT/bench_eager.json 2> $OUT/bench_eager.err
+  BENCH_FORCE_DIST=1 python bench.py --full --no-secondary --no-cpu-baseline > $OUT/bench_force_dist.json 2> $OUT/bench_force_dist.err
   BENCH_FORCE_DIST=1 python bench.py --workload mixed --no-cpu-baseline > $OUT/bench_mixed_force_dist.json 2> $OUT/bench_mixed_force_dist.err
 fi
 ls -R $OUT | head -80
