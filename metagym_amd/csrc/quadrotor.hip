@@ -115,8 +115,57 @@ __device__ __forceinline__ void cross_f32(const float *a, const float *b, float 
     c[2] = t4 - t5;
 }
 
-__device__ __forceinline__ double norm3(const double *x) {
-    return sqrt(fma(x[2], x[2], fma(x[1], x[1], x[0] * x[0])));
+__device__ __forceinline__ double sumsq3(const double *x) {
+    return fma(x[2], x[2], fma(x[1], x[1], x[0] * x[0]));
+}
+__device__ __forceinline__ double norm3(const double *x) { return sqrt(sumsq3(x)); }
+
+// ---- in-range sqrt and reciprocal (the sub-steps of STEP_STOCK_SHADOW, update_derived<true>) --------------------
+// For f64, the compiler expands sqrt(x) and 1.0 / d into a Newton sequence wrapped in range steps. The two functions
+// below are those sequences without the range steps. They are used only where the range steps are the identity,
+// which is what all_in_range tests.
+//   sqrt(x): s = ldexp(x, x < 2^-767 ? 256 : 0); rsq Newton on s; ldexp(result, x < 2^-767 ? -128 : 0); then
+//     x itself if class(s) is zero or inf. For 2^-767 <= x < +inf both ldexp are by 0 (exact for the finite x and
+//     the finite positive result) and s is neither zero nor inf: the result is the Newton value below. The one
+//     addition, rsq clamped to 2^512, is the identity there (rsq(x) <= 2^383.5). It makes x = +0 exact as well:
+//     rsq(+0) = +inf becomes 2^512, then s = +0, h = 2^511, r = 0.5, s = +0, h = 1.5 * 2^511 (finite), and the two
+//     corrections are fma(+0, h, +0) = +0: the result is +0, which is what the class step returns. Exact zeros are
+//     ordinary states (a reset with no velocity noise, a hover at rest on equal rotor voltages keeps w = 0), so they
+//     stay on the fast path; everything else below 2^-767 (denormals included) goes to the fallback.
+//   1.0 / d: v_div_scale_f64 of d and of 1.0, rcp Newton, v_div_fmas_f64, v_div_fixup_f64. By the ISA's rules
+//     V_DIV_SCALE_F64(S0, d, 1.0) returns S0 unscaled with VCC = 0 unless d is 0, d is denormal, 1/d is denormal,
+//     exponent(1.0) - exponent(d) >= 768 or exponent(1.0) <= 53; none holds for 2^-500 <= |d| <= 2^500. Then
+//     the scaled numerator is 1.0 and the product 1.0 * y is y (exact), V_DIV_FMAS_F64 with VCC = 0 is the plain
+//     fma, and V_DIV_FIXUP_F64 (d finite, normal and non-zero, numerator 1.0, exponent difference within +-500)
+//     returns the quotient with the sign of d, which it already has.
+// The test is one u32 range check on the high words, for all three arguments of an update at once: h - base < SPAN with
+// SPAN = 1000 exponents. For x = |v|^2 or |w|^2 (never negative; a NaN may carry the sign bit) the base is the high word of
+// 2^-767 (its low word is 0), so the window is exactly x = +0 (mapped to 0) or 2^-767 <= x < 2^233; a set sign bit or an
+// exponent of 2047 (inf, NaN) lands above it. For d the sign is masked off and the window is 2^-500 <= |d| < 2^500.
+// With R in f32, a non-zero det is a sum of multiples of 2^-447 below 2^387, so only det = 0, inf or NaN leave it.
+__device__ __forceinline__ uint32_t hi_word(double x) { return (uint32_t)(__builtin_bit_cast(uint64_t, x) >> 32); }
+__device__ __forceinline__ bool all_in_range(double xv, double xw, double d) {
+    constexpr uint32_t SPAN = 1000u << 20, SQRT_BASE = 256u << 20, RCP_BASE = 523u << 20;
+    const uint32_t tv = xv == 0.0 ? 0u : hi_word(xv) - SQRT_BASE, tw = xw == 0.0 ? 0u : hi_word(xw) - SQRT_BASE;
+    const uint32_t td = (hi_word(d) & 0x7fffffffu) - RCP_BASE;
+    return max(tv, max(tw, td)) < SPAN;
+}
+__device__ __forceinline__ double sqrt_newton(double x) {
+    const double g = fmin(__builtin_amdgcn_rsq(x), 0x1p+512);   // the identity in the window; x = +0: see above
+    double s = x * g, h = g * 0.5;
+    const double r = fma(-h, s, 0.5);
+    s = fma(s, r, s);
+    h = fma(h, r, h);
+    const double d0 = fma(-s, s, x);
+    s = fma(d0, h, s);
+    const double d1 = fma(-s, s, x);
+    return fma(d1, h, s);
+}
+__device__ __forceinline__ double rcp_newton(double d) {
+    double y = __builtin_amdgcn_rcp(d);
+    y = fma(y, fma(-d, y, 1.0), y);
+    y = fma(y, fma(-d, y, 1.0), y);
+    return fma(fma(-d, y, 1.0), y, y);   // v_div_fmas_f64(1.0 - d * (1.0 * y), y, 1.0 * y)
 }
 // np.linalg.norm(f32[3])^2 = OpenBLAS sdot(x, x): every product rounded to float32, the three products
 // accumulated in double, the sum rounded to float32
@@ -129,26 +178,56 @@ __device__ __forceinline__ float sumsq3(const float *x) {
 // casts back, i.e. it returns the correctly rounded f32 inverse. Same here: adjugate / det in f64
 // (branch-free, ~60 f64 ops, one division), rounded to f32. R drifts away from orthonormal (the
 // reference never re-normalises it), so R^T is NOT a substitute.
-__device__ __forceinline__ void inv3(const float *Af, float *Ainv, double *A) {   // A: out, the widened input
+struct Cof { double c00, c01, c02, det; };
+__device__ __forceinline__ Cof inv3_cof(const float *Af, double *A) {   // A: out, the widened input
 #pragma unroll
     for (int i = 0; i < 9; ++i) A[i] = (double)Af[i];
     // a*b - c*d as fma(a, b, -(c*d)): one rounding less per cofactor and one instruction less; this is OUR
     // way of reaching the correctly rounded float32 inverse, not an operation of the reference, so fusing
     // is free as long as oracle and kernel do the same
-    const double c00 = fma(A[4], A[8], -(A[5] * A[7]));
-    const double c01 = fma(A[5], A[6], -(A[3] * A[8]));
-    const double c02 = fma(A[3], A[7], -(A[4] * A[6]));
-    const double det = fma(A[2], c02, fma(A[1], c01, A[0] * c00));
-    const double r = 1.0 / det;
-    Ainv[0] = (float)(c00 * r);
-    Ainv[3] = (float)(c01 * r);
-    Ainv[6] = (float)(c02 * r);
+    Cof c;
+    c.c00 = fma(A[4], A[8], -(A[5] * A[7]));
+    c.c01 = fma(A[5], A[6], -(A[3] * A[8]));
+    c.c02 = fma(A[3], A[7], -(A[4] * A[6]));
+    c.det = fma(A[2], c.c02, fma(A[1], c.c01, A[0] * c.c00));
+    return c;
+}
+__device__ __forceinline__ void inv3_scale(const double *A, const Cof &c, double r, float *Ainv) {   // r = 1.0 / det
+    Ainv[0] = (float)(c.c00 * r);
+    Ainv[3] = (float)(c.c01 * r);
+    Ainv[6] = (float)(c.c02 * r);
     Ainv[1] = (float)(fma(A[2], A[7], -(A[1] * A[8])) * r);
     Ainv[4] = (float)(fma(A[0], A[8], -(A[2] * A[6])) * r);
     Ainv[7] = (float)(fma(A[1], A[6], -(A[0] * A[7])) * r);
     Ainv[2] = (float)(fma(A[1], A[5], -(A[2] * A[4])) * r);
     Ainv[5] = (float)(fma(A[2], A[3], -(A[0] * A[5])) * r);
     Ainv[8] = (float)(fma(A[0], A[4], -(A[1] * A[3])) * r);
+}
+__device__ __forceinline__ void inv3(const float *Af, float *Ainv, double *A) {
+    const Cof c = inv3_cof(Af, A);
+    inv3_scale(A, c, 1.0 / c.det, Ainv);
+}
+
+// Ri, Rd, nv and nw of the lane's current R, v and w (inv3 and the two norms). FAST: the in-range sequences above, and
+// `ok` cleared for a lane whose arguments leave their window. The caller redoes the whole step with the library's sqrt
+// and division when any lane of the wave has a cleared flag: one wave-uniform branch per step, which costs the wave about
+// 60 % more time when taken. A masked recompute behind a branch after each update bounds that cost, but splits the
+// straight-line sub-steps into scheduling regions: it doubled the VGPRs and took back the whole gain (profiles/r09/).
+template <bool FAST>
+__device__ __forceinline__ void update_derived(Lane &s, bool &ok) {
+    if (!FAST) {
+        inv3(s.R, s.Ri, s.Rd);
+        s.nv = norm3(s.v);
+        s.nw = norm3(s.w);
+        return;
+    }
+    const Cof c = inv3_cof(s.R, s.Rd);
+    const double xv = sumsq3(s.v), xw = sumsq3(s.w);
+    const double r = rcp_newton(c.det), nv = sqrt_newton(xv), nw = sqrt_newton(xw);
+    ok = ok & all_in_range(xv, xw, c.det);
+    inv3_scale(s.Rd, c, r, s.Ri);
+    s.nv = nv;
+    s.nw = nw;
 }
 
 // ---- one 1 ms Euler sub-step, quadrotorsim.py:122-210 ------------------------------------------
@@ -167,8 +246,9 @@ __device__ __forceinline__ void inv3(const float *Af, float *Ainv, double *A) { 
 // eight torque products to the four T_i*c. The sums are written as the reference's own: w0*pc1 - w1*pc0 is A - B,
 // A - (-B) = A + B, (-A) - (-B) = B - A and (-A) - B, never a negated sum (-(A-B) differs from B-A in the sign of
 // a zero result).
-template <bool SIMPLE, bool RECIP = false, bool XF = false>
-__device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *eff32, bool want_power) {
+// FAST: update_derived<true> (STEP_STOCK_SHADOW).
+template <bool SIMPLE, bool RECIP = false, bool XF = false, bool FAST = false>
+__device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *eff32, bool want_power, bool &ok) {
     static_assert(!XF || SIMPLE, "the X frame is a SIMPLE configuration");
     float prop_force_z = 0.0f;
     float prop_torque[3] = {0.0f, 0.0f, 0.0f};
@@ -310,9 +390,7 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) s.w[c] = s.w[c] + k.prec * alpha[c];
-    inv3(s.R, s.Ri, s.Rd);                                       // :206-208
-    s.nv = norm3(s.v);
-    s.nw = norm3(s.w);
+    update_derived<FAST>(s, ok);                                 // :206-208, and the norms
 }
 
 // quadrotorsim.py:212-221. A select chain, not early returns: all three tests are cheap and the early returns
@@ -524,17 +602,17 @@ __device__ __forceinline__ void load_state(const mg_quadrotor_state &st, int n, 
     ct = ld_soa<BUF>(st.ct, 1, n, 0, e);
 }
 
-__device__ __forceinline__ void derive_lane(Lane &s) {
-    inv3(s.R, s.Ri, s.Rd);
-    s.nv = norm3(s.v);
-    s.nw = norm3(s.w);
+template <bool FAST = false>
+__device__ __forceinline__ void derive_lane(Lane &s, bool &ok) {
+    update_derived<FAST>(s, ok);
     s.power = 0.0f;
 }
 
 template <bool BUF = false>
 __device__ __forceinline__ void load_lane(const mg_quadrotor_state &st, int n, int e, Lane &s, int &ct) {
+    bool ok = true;
     load_state<false, BUF>(st, n, e, s, ct);
-    derive_lane(s);
+    derive_lane<false>(s, ok);
 }
 
 template <bool BUF = false>
@@ -681,6 +759,8 @@ __device__ __forceinline__ KArgsC *kernargs_fresh() {
 //                      for every lane while the prologue loads are in flight, so the restart only moves values.
 //                      With more than one wave per SIMD the VALU is busy during the loads, and ~150 extra VALU on
 //                      every wave would cost more than the branch it saves.
+//                      Its sub-steps take sqrt and 1/det without the library's range steps (update_derived<true>);
+//                      a wave with an argument out of range redoes the step with the library's (see the kernel).
 // Two options, also resolved on the host:
 //   XF   (both stock forms) the stock X frame of propellers (config_is_xframe, substep<>); any other SIMPLE layout
 //        keeps XF = false.
@@ -688,7 +768,32 @@ __device__ __forceinline__ KArgsC *kernargs_fresh() {
 //        every array of the launch spans less than 2^31 bytes. Not in STEP_STOCK: there the step loop keeps the resources
 //        live across the sub-steps and the scalar file spills (14 / 36 SGPR spills with / without XF).
 enum StepForm { STEP_GENERIC = 0, STEP_STOCK = 1, STEP_STOCK_SHADOW = 2 };
+
+// Phase timeline (diagnostic builds only, -DMG_QUAD_PHASE_STAMPS; scripts/quad_phase_timeline.py reads it): lane 0 of
+// every wave of the STEP_STOCK_SHADOW kernel records the 100 MHz wall clock at entry, after the state loads, after
+// sub-step 10, after the state stores and after the obs stores are issued (slots 0-4), the shader clock at entry (5),
+// HW_ID | XCC_ID << 32 (6) and the number of fast-path fallbacks << 32 (7). mg_quadrotor_phase_stamps copies the
+// buffer to the host. The default library has neither the stamps nor the symbol.
+#ifdef MG_QUAD_PHASE_STAMPS
+constexpr int PHASE_STAMPS = 5, PHASE_SLOTS = 8, PHASE_MAX_WAVES = 4096;
+__device__ uint64_t g_phase_stamps[PHASE_MAX_WAVES * PHASE_SLOTS];
+#define MG_PHASE_STAMP(i)                                                                 \
+    do {                                                                                  \
+        if (SHADOW) {                                                                     \
+            __builtin_amdgcn_sched_barrier(0);                                            \
+            stamp[i] = __builtin_amdgcn_s_memrealtime();                                  \
+            __builtin_amdgcn_sched_barrier(0);                                            \
+        }                                                                                 \
+    } while (0)
+#else
+#define MG_PHASE_STAMP(i) \
+    do {                  \
+    } while (0)
+#endif
 constexpr int STOCK_TIMES = 10;
+#ifndef MG_QUAD_FASTPATH
+#define MG_QUAD_FASTPATH 1         // STEP_STOCK_SHADOW: in-range sqrt and 1/det in the sub-steps (0: the library's, A/B)
+#endif
 #ifndef MG_QUAD_SUBSTEP_UNROLL
 #define MG_QUAD_SUBSTEP_UNROLL 9   // of the first nine stock sub-steps (the tenth is peeled): 9 = straight-line, 1 = rolled
 #endif
@@ -701,6 +806,7 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
     static_assert(!STOCK || SIMPLE, "the stock forms are SIMPLE");
     static_assert(STOCK || !XF, "XF is an option of the stock forms");
     static_assert(SHADOW || !BUF, "BUF is an option of STEP_STOCK_SHADOW");
+    constexpr bool FAST = SHADOW && MG_QUAD_FASTPATH;   // in-range sqrt / 1/det (update_derived), whole-step fallback below
     const int n_steps = SHADOW ? 1 : n_steps_arg;
     __shared__ float tiles[WAVES_PER_BLOCK][mg::WAVE * (OBS_DIM + 1)];
     const int e = blockIdx.x * BLOCK + threadIdx.x;
@@ -720,6 +826,13 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
             touch |= ka[line * 16];
         asm volatile("" ::"s"(touch));
     }
+#ifdef MG_QUAD_PHASE_STAMPS
+    uint64_t stamp[PHASE_STAMPS];
+    uint32_t fallbacks = 0;
+    const uint64_t clock_in = __builtin_readcyclecounter();
+#endif
+    MG_PHASE_STAMP(0);   // entry
+    bool ok = true;   // FAST: every argument of every update_derived so far was in range
     float4 a_next;
     Lane s;
     int ct;
@@ -739,7 +852,7 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         for (int c = 0; c < 3; ++c) asm volatile("" : "+v"(rd.v[c]), "+v"(rd.w[c]));   // not sunk into the restart branch
         asm volatile("" : "+v"(rd.nv), "+v"(rd.nw));
         __builtin_amdgcn_sched_barrier(0);
-        derive_lane(s);
+        derive_lane<false>(s, ok);   // the library's sqrt / 1/det: hidden behind the loads, and exact for reset states (v = w = 0)
         __builtin_amdgcn_sched_barrier(0);
     } else {
         a_next = reinterpret_cast<const float4 *>(io.action)[el];
@@ -752,6 +865,7 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
     // would be re-executed by every later step of a rollout and would also drain that step's freshly issued
     // action prefetch and the previous step's stores (2.5 us per step at K > 1; free at K = 1).
     __builtin_amdgcn_s_waitcnt(0x0F70);
+    MG_PHASE_STAMP(1);   // state loaded (and derived)
 
     for (int t = 0; t < n_steps; ++t) {
         const size_t off = (size_t)t * n;
@@ -774,21 +888,43 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         if (STOCK) {             // straight-line sub-steps (see StepForm); the first failure code is kept
 #pragma unroll MG_QUAD_SUBSTEP_UNROLL
             for (int it = 0; it < STOCK_TIMES - 1; ++it) {
-                substep<SIMPLE, true, XF>(k, s, eff32, false);
+                substep<SIMPLE, true, XF, FAST>(k, s, eff32, false, ok);
                 const int code = failure_code(k, s);
                 fail = fail ? fail : code;
             }
-            substep<SIMPLE, true, XF>(k, s, eff32, true);
+            substep<SIMPLE, true, XF, FAST>(k, s, eff32, true, ok);
             const int code = failure_code(k, s);
             fail = fail ? fail : code;
+            if (FAST && __builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0, 0)) {
+                // Some lane of the wave met a sqrt or 1/det argument outside the fast path's window (zero or tiny
+                // velocity / body rate, inf or NaN, a singular R): redo the step for the whole wave from the loaded
+                // state with the library's sqrt and division. The state is still in memory (stores come later); the
+                // step's inputs are re-read through kernargs_fresh so that none is held in SGPRs across the sub-steps.
+                const KArgsC *kaf = kernargs_fresh();
+                const QuadK &kf = *(const QuadK *)&kaf->k;
+                int ct_loaded;
+                load_state<true, BUF>(*(const mg_quadrotor_state *)&kaf->st, n, el, s, ct_loaded);
+                derive_lane<false>(s, ok);
+                fail = 0;
+#pragma unroll 1
+                for (int it = 0; it < STOCK_TIMES; ++it) {
+                    substep<SIMPLE, true, XF, false>(kf, s, eff32, it == STOCK_TIMES - 1, ok);
+                    const int code = failure_code(kf, s);
+                    fail = fail ? fail : code;
+                }
+#ifdef MG_QUAD_PHASE_STAMPS
+                fallbacks += 1;
+#endif
+            }
         } else {
             for (int it = 0; it < k.times; ++it) {                          // quadrotorsim.py:302-304
                 if (fail == 0) {  // a failed env freezes at the failing sub-step (reference raises)
-                    substep<SIMPLE>(k, s, eff32, it == k.times - 1);
+                    substep<SIMPLE>(k, s, eff32, it == k.times - 1, ok);
                     fail = failure_code(k, s);
                 }
             }
         }
+        MG_PHASE_STAMP(2);   // sub-step 10 done
         // The reward / observation constants and the output pointers are used only from here on. Held in
         // SGPRs across the sub-step loop they overflow the scalar file and get spilled to VGPR lanes
         // (125 spills, ~200 v_writelane/v_readlane on the hot path); re-reading them from the kernarg
@@ -863,11 +999,13 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
             store_lane<BUF>(ste, n, e, s, ct);
             if (episode != episode_in) st_soa<BUF>(ste.episode, 1, n, 0, e, episode);   // rare: only lanes that restarted
         }
+        MG_PHASE_STAMP(3);   // state stores issued
         __builtin_amdgcn_sched_barrier(0);   // pure arithmetic would otherwise be hoisted above the stores
         float obs[OBS_DIM + 3];
         observe(ke, s, obs);
         if (vel_task) { obs[16] = ke.vtargets[3 * tn]; obs[17] = ke.vtargets[3 * tn + 1]; obs[18] = ke.vtargets[3 * tn + 2]; }
         store_obs_wave<BUF>(tile, obs, ioe.obs + off * ke.obs_dim, n, e, ke.obs_dim);
+        MG_PHASE_STAMP(4);   // obs stores issued
         if (live) {
             if (BUF) {   // one-step form: off == 0
                 if (ioe.reward) st_soa<true>(ioe.reward + off, 1, n, 0, e, (float)reward);
@@ -882,6 +1020,20 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
             }
         }
     }
+#ifdef MG_QUAD_PHASE_STAMPS
+    if (SHADOW) {   // lane 0 of each wave, plain vector stores
+        const uint32_t wave = (blockIdx.x * BLOCK + threadIdx.x) / mg::WAVE;
+        if ((threadIdx.x & (mg::WAVE - 1)) == 0 && wave < PHASE_MAX_WAVES) {
+            uint64_t *out = &g_phase_stamps[(size_t)wave * PHASE_SLOTS];
+#pragma unroll
+            for (int i = 0; i < PHASE_STAMPS; ++i) out[i] = stamp[i];
+            out[5] = clock_in;
+            out[6] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) |                 // HW_ID: wave, SIMD, CU, SE
+                     ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);        // XCC_ID
+            out[7] = (uint64_t)fallbacks << 32;
+        }
+    }
+#endif
 }
 
 __global__ __launch_bounds__(BLOCK) void quadrotor_reset_kernel(QuadK k, mg_quadrotor_state st,
@@ -1224,6 +1376,17 @@ extern "C" int mg_quadrotor_plan_init(mg_quadrotor_plan *plan, const mg_quadroto
     p->magic = 0;
     return make_plan(p, cfg, ar, n_envs, state);
 }
+
+#ifdef MG_QUAD_PHASE_STAMPS
+// diagnostic builds only: the phase timeline of the last STEP_STOCK_SHADOW launch (see g_phase_stamps)
+extern "C" int mg_quadrotor_phase_stamps(uint64_t *host, int32_t max_waves) {
+    MG_REQUIRE_PTR(host);
+    const int32_t w = max_waves < PHASE_MAX_WAVES ? max_waves : PHASE_MAX_WAVES;
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_phase_stamps), (size_t)w * PHASE_SLOTS * sizeof(uint64_t)) != hipSuccess)
+        return mg::set_error(MG_ERR_UNSUPPORTED, "hipMemcpyFromSymbol(g_phase_stamps) failed");
+    return MG_OK;
+}
+#endif
 
 extern "C" int mg_quadrotor_plan_step(const mg_quadrotor_plan *plan, int32_t n_steps, const float *action, float *obs,
                                       float *reward, double *reward64, uint8_t *done, uint8_t *failed, void *stream) {
