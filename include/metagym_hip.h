@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MG_ABI_VERSION 9
+#define MG_ABI_VERSION 10
 
 #define MG_OK 0
 #define MG_ERR_NULL_POINTER (-1001)
@@ -907,6 +907,100 @@ int mg_bandits_reset(const mg_bandits_config *cfg, int32_t n_envs, const mg_band
 int mg_bandits_step(const mg_bandits_config *cfg, int32_t n_envs, const mg_bandits_state *state, int32_t n_steps,
                     const int32_t *actions, float *reward, uint8_t *done, int32_t *info_steps, double *expected_gain,
                     uint8_t *invalid, void *stream);
+
+/* ========================================================================================
+ * LiftSim — replaces metagym/liftsim/environment/env.py LiftSim (ABI 10)
+ * ======================================================================================== */
+
+#define MG_LIFTSIM_CUSTOM 0
+#define MG_LIFTSIM_UNIFORM 1
+#define MG_LIFTSIM_MAX_FLOORS 128
+#define MG_LIFTSIM_MAX_ELEVATORS 32
+#define MG_LIFTSIM_LOAD_CAP 80       /* persons on board: maximum_capacity 1600 / minimum weight 20 */
+#define MG_LIFTSIM_QN 16             /* binomial q^n table entries per category: n = 1..16 */
+
+typedef struct mg_liftsim_config {
+    int32_t floors;              /* F in [2, 128] */
+    int32_t elevators;           /* E in [1, 32] */
+    int32_t generator;           /* MG_LIFTSIM_CUSTOM / MG_LIFTSIM_UNIFORM */
+    int32_t queue_capacity;      /* persons per (floor, direction) queue, in [1, 4096]; a fuller queue flags `overflow` */
+    int32_t window;              /* statistics window int(600 / dt), in [1, 1 << 20] */
+    int32_t particle_number;     /* UNIFORM: ParticleNumber >= 0 */
+    int32_t table_len;           /* CUSTOM: T rows of the flow table, >= 1 */
+    int32_t pad;
+    double floor_height;         /* > 0 */
+    double dt;                   /* RunningTimeStep, in (0, 1] */
+    double generation_interval;  /* UNIFORM: GenerationInterval > 0 */
+    double nv_magic;             /* CPython's NV_MAGICCONST = 4 exp(-0.5) / sqrt(2) as the host computed it */
+    /* CUSTOM tables, DEVICE, built on the host from the flow file with the reference's float32 expressions:
+     *   times  f64 [T]            interval start times (the flow file's second column)
+     *   dens   f32 [T][F]         in-density per floor
+     *   enlam  f64 [T][F]         glibc exp(-lambda), lambda = dens * float32(dt) in float32 (numpy's poisson)
+     *   pp     f64 [T][F][F]      the probability multinomial hands the binomial of category j (p_j / remaining_p), or
+     *                             1 - that when it is above 0.5 (random_binomial's flip); 0 = category drawn as 0
+     *   flip   i32 [T][F][F]      1 = that flip happened (the count is n - inversion)
+     *   logq   f64 [T][F][F]      glibc log(1 - pp)
+     *   qn     f64 [T][F][F][16]  glibc exp(n log(1 - pp)) for n = 1..16 (OCML above) */
+    const double *times;
+    const float *dens;
+    const double *enlam;
+    const double *pp;
+    const int32_t *flip;
+    const double *logq;
+    const double *qn;
+} mg_liftsim_config;
+
+/* Fields of the state arena. mg_liftsim_layout gives each one's byte offset; every field is structure-of-arrays with the
+ * env index fastest ([item][N]), except the two stream records ([N][1248] u32: two 624-word key blocks, the second the
+ * refill of the first). */
+enum {
+    MG_LS_POS, MG_LS_VEL, MG_LS_LOAD, MG_LS_DOOR, MG_LS_KEEP, MG_LS_ALARM, MG_LS_FLOOR,   /* f64 [E][N] */
+    MG_LS_DIR, MG_LS_DISPATCH, MG_LS_DISPATCH_DIR, MG_LS_NTARGET, MG_LS_EFLAGS,         /* i32 [E][N] */
+    MG_LS_TARGETS,                                                                      /* i32 [E][F][N] */
+    MG_LS_OPENING, MG_LS_CLOSING,                                                       /* u8 [E][N] */
+    MG_LS_CLICKED,                                                                      /* u32 [E][4][N] */
+    MG_LS_NLOADED, MG_LS_LW, MG_LS_LT,     /* i32 [E][N], f64 [E][80][N], i32 [E][80][N] */
+    MG_LS_NENT, MG_LS_EW, MG_LS_ET, MG_LS_EL,   /* i32 [E][N], f64 [E][2][N], i32 [E][2][N], f64 [E][2][N] */
+    MG_LS_NEXIT, MG_LS_XW, MG_LS_XL,            /* i32 [E][N], f64 [E][2][N] x2 */
+    MG_LS_QHEAD, MG_LS_QLEN,                    /* i32 [F][2][N] */
+    MG_LS_QW, MG_LS_QA, MG_LS_QT,               /* f64 / f64 / i32 [F][2][Q][N]: weight, appear time, target floor */
+    MG_LS_UP, MG_LS_DOWN,                       /* u8 [F][N] the hall buttons */
+    MG_LS_TIME, MG_LS_LASTGEN,                  /* f64 [N] */
+    MG_LS_TIDX,                                 /* i32 [N] the CUSTOM generator's time index (reset() keeps it) */
+    MG_LS_INVALID, MG_LS_OVERFLOW, MG_LS_UNSUPPORTED,   /* u8 [N] */
+    MG_LS_SHEAD, MG_LS_SCOUNT,                  /* i32 [N] statistics ring */
+    MG_LS_SD, MG_LS_SG, MG_LS_SA,               /* i32 [W][N] delivered / generated / abandoned per step */
+    MG_LS_SW, MG_LS_SE,                         /* f64 [W][N] waiting time / energy per step */
+    MG_LS_PYKEY, MG_LS_NPKEY,                   /* u32 [N][1248] python random / numpy RandomState key blocks */
+    MG_LS_PYP, MG_LS_PYV, MG_LS_NPP, MG_LS_NPV, /* i32 [N] read position in [0, 1248); 1 = the next block is ready */
+    MG_LS_REWARD, MG_LS_TIMEC, MG_LS_ENERGY,    /* f64 [N] step outputs */
+    MG_LS_GIVEN,                                /* i32 [N] */
+    MG_LS_ST_D, MG_LS_ST_G, MG_LS_ST_A,         /* i64 [N] statistics sums (mg_liftsim_statistics) */
+    MG_LS_ST_E, MG_LS_ST_W,                     /* f64 [N] */
+    MG_LS_NFIELDS
+};
+
+/* Byte offsets of the MG_LS_NFIELDS fields (each 256-byte aligned) and the arena's total size for n_envs envs. */
+int mg_liftsim_layout(const mg_liftsim_config *cfg, int32_t n_envs, int64_t *offsets, int64_t *total_bytes);
+
+/* env.seed(s_e) for every env: random.seed(s_e) and numpy.random.seed(s_e), s_e = seeds[e] (DEVICE u32 [N]) or
+ * seed_base + e. Clears the statistics ring, the time index and the flags, then resets every env. */
+int mg_liftsim_seed(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, uint32_t seed_base, const uint32_t *seeds,
+                    void *stream);
+
+/* env.reset() for every env with mask[e] != 0 (mask NULL = all): elevators, time, queues and buttons. The statistics, the
+ * streams, the time index and the overflow / unsupported flags carry over, as in the reference. Draws nothing. */
+int mg_liftsim_reset(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, const uint8_t *mask, void *stream);
+
+/* One env.step(action) of every env. actions: DEVICE int32 [N][2E] in the reference's flat order (target, direction per
+ * elevator). An env with an action outside (target in [-1, F], direction in {-1, 0, 1}) sets INVALID and does not advance;
+ * an env flagged OVERFLOW (a queue would pass queue_capacity) or UNSUPPORTED (a draw path not built here: poisson with
+ * lambda >= 10, binomial with n p > 30, or more than 624 words of one stream in one step) is frozen. Frozen and invalid
+ * envs write 0 outputs. */
+int mg_liftsim_step(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, const int32_t *actions, void *stream);
+
+/* env.statistics of every env into the ST_* fields: the ring summed newest to oldest from 0, as Python's sum() does. */
+int mg_liftsim_statistics(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, void *stream);
 
 #ifdef __cplusplus
 }

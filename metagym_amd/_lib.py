@@ -8,7 +8,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 MG_OK = 0
 
@@ -239,6 +239,22 @@ class BanditsState(C.Structure):
                 ("steps", C.c_void_p), ("over", C.c_void_p)]
 
 
+class LiftsimConfig(C.Structure):
+    """mg_liftsim_config"""
+    _fields_ = [("floors", C.c_int32), ("elevators", C.c_int32), ("generator", C.c_int32), ("queue_capacity", C.c_int32),
+                ("window", C.c_int32), ("particle_number", C.c_int32), ("table_len", C.c_int32), ("pad", C.c_int32),
+                ("floor_height", C.c_double), ("dt", C.c_double), ("generation_interval", C.c_double),
+                ("nv_magic", C.c_double), ("times", C.c_void_p), ("dens", C.c_void_p), ("enlam", C.c_void_p),
+                ("pp", C.c_void_p), ("flip", C.c_void_p), ("logq", C.c_void_p), ("qn", C.c_void_p)]
+
+
+# the MG_LS_* fields of the LiftSim state arena, in the header's order
+LIFTSIM_FIELDS = ["pos", "vel", "load", "door", "keep", "alarm", "floor", "dir", "dispatch", "dispatch_dir", "ntarget",
+                  "eflags", "targets", "opening", "closing", "clicked", "nloaded", "lw", "lt", "nent", "ew", "et", "el",
+                  "nexit", "xw", "xl", "qhead", "qlen", "qw", "qa", "qt", "up", "down", "time", "lastgen", "tidx",
+                  "invalid", "overflow", "unsupported", "shead", "scount", "sd", "sg", "sa", "sw", "se", "pykey", "npkey",
+                  "pyp", "pyv", "npp", "npv", "reward", "timec", "energy", "given", "st_d", "st_g", "st_a", "st_e", "st_w"]
+
 # symbol -> (restype, argtypes); tests/test_abi.py checks this list against include/metagym_hip.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -293,6 +309,11 @@ SIGNATURES = {
     "mg_a1_reward_step": (C.c_int, [C.POINTER(A1RewardConfig), C.c_int32, C.POINTER(A1RewardState), _P, _P, _P, _P, _P,
                                     _P, _P, _P, _P, _P, _P, _P]),
     "mg_metalm_generate": (C.c_int, [C.POINTER(MetaLMParams), C.c_int32, C.c_uint32, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "mg_liftsim_layout": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mg_liftsim_seed": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, C.c_uint32, _P, _P]),
+    "mg_liftsim_reset": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, _P, _P]),
+    "mg_liftsim_step": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, _P, _P]),
+    "mg_liftsim_statistics": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, _P]),
     "mg_bandits_seed": (C.c_int, [C.c_int32, C.c_uint32, _P, C.POINTER(BanditsState), _P]),
     "mg_bandits_sample_task": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P, _P]),
     "mg_bandits_reset": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P]),

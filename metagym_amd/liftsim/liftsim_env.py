@@ -1,0 +1,367 @@
+"""LiftSim (reference metagym/liftsim/environment/env.py) for N buildings at once, stepped by `mg_liftsim_step` on the GPU."""
+import collections
+import configparser
+import ctypes as C
+import math
+import random
+
+import numpy as np
+
+from .. import _lib
+
+CUSTOM, UNIFORM = 0, 1
+QN = 16           # MG_LIFTSIM_QN
+REC = 1248        # u32 words of one stream record: two 624-word key blocks
+MAX_FLOORS, MAX_ELEVATORS = 128, 32
+MAXIMUM_SPEED, MAXIMUM_LOAD = 2.0, 1600
+
+# the reference's namedtuples (utils.py), so reference-style dispatchers work and states compare with ==
+ElevatorState = collections.namedtuple("ElevatorState", [
+    "Floor", "MaximumFloor", "Velocity", "MaximumSpeed", "Direction", "DoorState", "CurrentDispatchTarget",
+    "DispatchTargetDirection", "LoadWeight", "MaximumLoad", "ReservedTargetFloors", "OverloadedAlarm",
+    "DoorIsOpening", "DoorIsClosing"])
+MansionState = collections.namedtuple("MansionState", ["ElevatorStates", "RequiringUpwardFloors",
+                                                       "RequiringDownwardFloors"])
+MansionAttribute = collections.namedtuple("MansionAttribute", ["ElevatorNumber", "NumberOfFloor", "FloorHeight"])
+
+# the reference's config.ini (metagym/liftsim/config.ini); UNIFORM's two settings as its commented-out lines give them
+DEFAULTS = dict(floors=10, elevators=4, floor_height=4.0, dt=0.5, generator="CUSTOM", particle_number=12,
+                generation_interval=150.0)
+
+
+def read_config(path):
+    """A reference config.ini as keyword arguments of LiftSim (env.py:29-60; the log settings are ignored)."""
+    c = configparser.ConfigParser()
+    if not c.read(path):
+        raise FileNotFoundError(path)
+    g = c["PersonGenerator"]
+    kw = dict(dt=float(c["Configuration"]["RunningTimeStep"]), floors=int(c["MansionInfo"]["NumberOfFloors"]),
+              floor_height=float(c["MansionInfo"]["FloorHeight"]), elevators=int(c["MansionInfo"]["ElevatorNumber"]),
+              generator=g["PersonGeneratorType"])
+    if "ParticleNumber" in g:
+        kw["particle_number"] = int(g["ParticleNumber"])
+    if "GenerationInterval" in g:
+        kw["generation_interval"] = float(g["GenerationInterval"])
+    return kw
+
+
+def resolve_config(config_file=None, **settings):
+    """The settings a LiftSim runs with: config.ini's defaults, then `config_file` (parsed like env.py:29-60), then every
+    setting passed explicitly (not None), which wins over the file. An unknown setting is a TypeError."""
+    unknown = set(settings) - set(DEFAULTS)
+    if unknown:
+        raise TypeError("unknown LiftSim settings: %s" % sorted(unknown))
+    cfg = dict(DEFAULTS)
+    if config_file is not None:
+        cfg.update(read_config(config_file))
+    cfg.update({k: v for k, v in settings.items() if v is not None})
+    return cfg
+
+
+def custom_tables(flow, floors, dt):
+    """The CUSTOM generator's tables (custom_generator.py:38-69, 111-135) from a flow array [T, 2 + F (F + 1)], with the
+    reference's float32 / NEP 50 expressions for lambda and the category probabilities, and glibc (Python's math) for the
+    exp / log values that decide draw counts. Returns a dict of numpy arrays named as in mg_liftsim_config."""
+    flow = np.asarray(flow, dtype=np.float64)
+    F = int(floors)
+    if flow.ndim != 2 or flow.shape[0] < 1:
+        raise ValueError("the flow table must be a 2-D array")
+    if int(flow[0][0]) != F:
+        raise AssertionError("The dimension of the data file does not match the floor number, %d and %d"
+                             % (int(flow[0][0]), F))
+    pf = flow[:, 1:]
+    if pf.shape[1] != 1 + F * (F + 1):
+        raise AssertionError("The column of the dataset file do not match the mansion, %d and %d"
+                             % (pf.shape[1], 1 + F * (F + 1)))
+    if not pf[-1][0] < 86400:
+        raise AssertionError("The time of the day must < 86400 sec")
+    if not pf[0][0] <= 0.0:
+        raise AssertionError("The start time of the day must <= 0.0 sec")
+    T = pf.shape[0]
+    dens = np.zeros([T, F], dtype="float32")
+    out = np.zeros([T, F, F], dtype="float32")
+    for i in range(T):
+        gap = pf[i + 1][0] - pf[i][0] if i < T - 1 else 86400 - pf[i][0]
+        if not gap > 0.0:
+            raise AssertionError("The time interval must be above zero")
+        for j in range(F):
+            dens[i][j] = 1.0 / gap * pf[i][j * (F + 1) + 1]
+            out[i][j] = pf[i][(j * (F + 1) + 2):((j + 1) * (F + 1) + 1)]
+    lam = dens * np.float32(dt)                       # float32, as numpy computes it for the nominal interval
+    enlam = np.array([[math.exp(-float(x)) for x in row] for row in lam], dtype=np.float64)
+    prob = np.zeros([T, F, F], dtype="float32")
+    pp = np.zeros([T, F, F])
+    flip = np.zeros([T, F, F], dtype=np.int32)
+    logq = np.zeros([T, F, F])
+    qn = np.zeros([T, F, F, QN])
+    for i in range(T):
+        for j in range(F):
+            prob[i, j] = out[i][j] / (1.0e-5 + out[i][j].sum())
+            pix = prob[i, j].astype(np.float64)
+            rem = 1.0
+            for c in range(F - 1):                    # random_multinomial: p_c / remaining_p, then random_binomial's flip
+                p = float(pix[c]) / rem
+                rem -= float(pix[c])
+                if p > 0.5:
+                    p, flip[i, j, c] = 1.0 - p, 1
+                pp[i, j, c] = p
+                lq = math.log(1.0 - p)
+                logq[i, j, c] = lq
+                qn[i, j, c] = [math.exp(float(n) * lq) for n in range(1, QN + 1)]
+    return dict(times=pf[:, 0].copy(), dens=dens, out_prob=out, prob=prob, enlam=enlam, pp=pp, flip=flip, logq=logq,
+                qn=qn)
+
+
+def _random_state(key, p):
+    """(key block, pos) of a two-block record at read position p, as numpy / CPython state: the block of word p - 1."""
+    q = (p + REC - 1) % REC
+    blk = q // 624
+    return key[blk * 624:(blk + 1) * 624], q % 624 + 1
+
+
+class LiftSim(object):
+    """`num_envs` LiftSim buildings: env e is the reference's LiftSim after env.seed(seed + e) (or seeds[e]), bit for bit
+    (state, reward, info, statistics and both streams), given the same actions and reset() calls.
+
+    Configuration: the reference's config.ini defaults, then `config_file=` (parsed like env.py), then keyword settings,
+    which win over the file (resolve_config). `seed()` on a live object also resets every env and clears the statistics,
+    the CUSTOM time index and the flags: it starts env e over as a fresh `LiftSim(); env.seed(s_e)`, where the
+    reference's env.seed() only reseeds its two streams. A CUSTOM
+    env takes the flow table as `flow_file=` (the reference's mansion_flow.npy) or `flow=` (the array); it does not ship
+    here. Actions: int32 [N, 2E] in the reference's flat order. An env with an out-of-range entry sets `invalid` and does
+    not advance (the reference asserts mid-step; step(check=True) raises its AssertionError instead). An env whose queue
+    would pass `queue_capacity` sets `overflow`, one whose draws need a path not built here sets `unsupported`; both freeze
+    the env until the next seed(). step() never synchronises with the host unless check=True; outputs live in persistent
+    buffers (copy_outputs=True returns copies). There is no CPU path.
+    """
+
+    def __init__(self, num_envs=1, config_file=None, flow_file=None, flow=None, device="cuda", seed=0, seeds=None,
+                 floors=None, elevators=None, floor_height=None, dt=None, generator=None, particle_number=None,
+                 generation_interval=None, queue_capacity=128, copy_outputs=False, **kwargs):
+        import torch
+        cfg = resolve_config(config_file, floors=floors, elevators=elevators, floor_height=floor_height, dt=dt,
+                             generator=generator, particle_number=particle_number,
+                             generation_interval=generation_interval, **kwargs)
+        if not float(cfg["dt"]) <= 1:
+            raise AssertionError("RunningTimeStep in config.ini must be less than 1 in order to ensure accuracy")
+        if cfg["generator"] not in ("CUSTOM", "UNIFORM"):
+            raise RuntimeError("No such generator type: %s" % cfg["generator"])
+        self.F, self.E = int(cfg["floors"]), int(cfg["elevators"])
+        self.floor_height, self.dt = float(cfg["floor_height"]), float(cfg["dt"])
+        self.generator = cfg["generator"]
+        if not (2 <= self.F <= MAX_FLOORS and 1 <= self.E <= MAX_ELEVATORS):
+            raise ValueError("LiftSim here needs 2 <= floors <= %d and 1 <= elevators <= %d" % (MAX_FLOORS, MAX_ELEVATORS))
+        if self.generator == "CUSTOM" and flow is None and flow_file is None:
+            raise ValueError("a CUSTOM LiftSim needs the flow table: pass flow_file= (the reference's "
+                             "mansion_flow.npy, its CustomDataFile) or flow=")
+        if torch.device(device).type != "cuda":
+            raise _lib.MetaGymHipError("metagym_amd runs on an AMD GPU only (got device %r); there is no CPU fallback"
+                                       % (device,))
+        self.device = _lib.canonical_device(device)
+        self.num_envs = N = int(num_envs)
+        if N <= 0:
+            raise ValueError("num_envs must be positive")
+        self.copy_outputs = bool(copy_outputs)
+        self.window = int(600 / self.dt)
+        c = _lib.LiftsimConfig()
+        c.floors, c.elevators, c.queue_capacity, c.window = self.F, self.E, int(queue_capacity), self.window
+        c.floor_height, c.dt, c.nv_magic = self.floor_height, self.dt, random.NV_MAGICCONST
+        self._tables = {}
+        if self.generator == "CUSTOM":
+            if flow is None:
+                flow = np.load(flow_file)
+            tb = custom_tables(flow, self.F, self.dt)
+            c.generator, c.table_len = CUSTOM, len(tb["times"])
+            for name in ("times", "dens", "enlam", "pp", "flip", "logq", "qn"):
+                t = torch.from_numpy(np.ascontiguousarray(tb[name])).to(self.device)
+                self._tables[name] = t
+                setattr(c, name, t.data_ptr())
+            self.tables = tb
+        else:
+            c.generator = UNIFORM
+            c.particle_number = int(cfg["particle_number"])
+            c.generation_interval = float(cfg["generation_interval"])
+        self._cfg = c
+        self._lib = _lib.load()
+        offs = (C.c_int64 * len(_lib.LIFTSIM_FIELDS))()
+        total = C.c_int64()
+        _lib.check(self._lib.mg_liftsim_layout(c, N, offs, total), "mg_liftsim_layout")
+        self.arena = torch.zeros(int(total.value), dtype=torch.uint8, device=self.device)
+        self._off = dict(zip(_lib.LIFTSIM_FIELDS, [int(o) for o in offs]))
+        E, F, Q, W = self.E, self.F, int(queue_capacity), self.window
+        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
+        v = self._view
+        # observations: [N, ...] views of the [item][N] state
+        self.floor = v("floor", f64, (E, N)).t()
+        self.velocity = v("vel", f64, (E, N)).t()
+        self.direction = v("dir", i32, (E, N)).t()
+        self.door_state = v("door", f64, (E, N)).t()
+        self.dispatch_target = v("dispatch", i32, (E, N)).t()
+        self.dispatch_target_direction = v("dispatch_dir", i32, (E, N)).t()
+        self.load_weight = v("load", f64, (E, N)).t()
+        self.reserved_target_floors = v("targets", i32, (E, F, N)).permute(2, 0, 1)
+        self.reserved_count = v("ntarget", i32, (E, N)).t()
+        self.overloaded_alarm = v("alarm", f64, (E, N)).t()
+        b = torch.bool   # the kernel writes these bytes as 0 / 1: bool views, no copies
+        self.door_is_opening = v("opening", b, (E, N)).t()
+        self.door_is_closing = v("closing", b, (E, N)).t()
+        self.requiring_upward = v("up", b, (F, N)).t()
+        self.requiring_downward = v("down", b, (F, N)).t()
+        self.reward = v("reward", f64, (N,))
+        self.time_consume = v("timec", f64, (N,))
+        self.energy_consume = v("energy", f64, (N,))
+        self.given_up_persons = v("given", i32, (N,))
+        self.invalid = v("invalid", u8, (N,))
+        self.overflow = v("overflow", u8, (N,))
+        self.unsupported = v("unsupported", u8, (N,))
+        self.done = torch.zeros(N, dtype=torch.bool, device=self.device)   # always False, as in the reference
+        self.queue_capacity, self._Q, self._W = Q, Q, W
+        self.seed(seed, seeds)
+
+    # ------------------------------------------------------------------ plumbing
+    def _view(self, name, dtype, shape):
+        import torch
+        n = 1
+        for s in shape:
+            n *= s
+        size = n * torch.empty((), dtype=dtype).element_size()
+        o = self._off[name]
+        return self.arena[o:o + size].view(dtype).view(shape)
+
+    def _stream(self):
+        return _lib.current_stream(self.device)
+
+    @property
+    def attribute(self):
+        """The reference's MansionAttribute namedtuple."""
+        return MansionAttribute(self.E, self.F, self.floor_height)
+
+    # ------------------------------------------------------------------ API
+    def seed(self, seed=0, seeds=None):
+        """env.seed(seed + e) or seeds[e] for every env (32-bit values): both streams, the statistics, the time index and
+        the flags start over, and every env is reset, so env e is a fresh LiftSim after env.seed(s_e). (The reference's
+        env.seed() on a running env reseeds its streams only.)"""
+        import torch
+        N = self.num_envs
+        seeds_t = None
+        if seeds is not None:
+            arr = np.asarray(seeds.cpu().numpy() if hasattr(seeds, "cpu") else seeds, dtype=np.int64)
+            if arr.shape != (N,) or arr.min() < 0 or arr.max() >= 2 ** 32:
+                raise ValueError("seeds must be %d values in [0, 2^32)" % N)
+            seeds_t = torch.from_numpy(arr.astype(np.uint32).view(np.int32)).to(self.device)
+            seed = 0
+        if not (0 <= int(seed) and int(seed) + N <= 2 ** 32):
+            raise ValueError("seeds are 32-bit: need 0 <= seed and seed + N <= 2^32")
+        _lib.check(self._lib.mg_liftsim_seed(self._cfg, N, _lib.ptr(self.arena), int(seed), _lib.ptr(seeds_t),
+                                             self._stream()), "mg_liftsim_seed")
+        return [seed] if seeds is None else list(seeds)
+
+    def reset(self, mask=None):
+        """env.reset() for every env (or those with mask[e] != 0). Statistics, streams and the time index carry over."""
+        import torch
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device)
+            if tuple(m.shape) != (self.num_envs,):
+                raise ValueError("mask must have shape [%d]" % self.num_envs)
+            m = (m != 0).to(torch.uint8).contiguous()
+        _lib.check(self._lib.mg_liftsim_reset(self._cfg, self.num_envs, _lib.ptr(self.arena), _lib.ptr(m),
+                                              self._stream()), "mg_liftsim_reset")
+        return self.observation()
+
+    def observation(self):
+        obs = dict(Floor=self.floor, Velocity=self.velocity, Direction=self.direction, DoorState=self.door_state,
+                   CurrentDispatchTarget=self.dispatch_target, DispatchTargetDirection=self.dispatch_target_direction,
+                   LoadWeight=self.load_weight, ReservedTargetFloors=self.reserved_target_floors,
+                   ReservedTargetCount=self.reserved_count, OverloadedAlarm=self.overloaded_alarm,
+                   DoorIsOpening=self.door_is_opening, DoorIsClosing=self.door_is_closing,
+                   RequiringUpwardFloors=self.requiring_upward, RequiringDownwardFloors=self.requiring_downward)
+        if self.copy_outputs:
+            obs = {k: t.clone() for k, t in obs.items()}
+        return obs
+
+    def step(self, action, check=False):
+        """One env.step(action) per env: action int32 [N, 2E]. Returns (observation, reward, done, info)."""
+        import torch
+        a = torch.as_tensor(action, device=self.device)
+        if tuple(a.shape) != (self.num_envs, 2 * self.E):
+            raise ValueError("actions must have shape [%d, %d]" % (self.num_envs, 2 * self.E))
+        if a.dtype != torch.int32:
+            a = a.to(torch.int32)
+        a = a.contiguous()
+        if check:
+            t, d = a[:, 0::2], a[:, 1::2]
+            if bool(((t < -1) | (t > self.F)).any()):
+                raise AssertionError("action.TargetFloor >= -1 and action.TargetFloor <= number_of_floors")
+            if bool(((d < -1) | (d > 1)).any()):
+                raise AssertionError("action.DirectionIndicator in [-1, 0, 1]")
+        _lib.check(self._lib.mg_liftsim_step(self._cfg, self.num_envs, _lib.ptr(self.arena), _lib.ptr(a),
+                                             self._stream()), "mg_liftsim_step")
+        info = dict(time_consume=self.time_consume, energy_consume=self.energy_consume,
+                    given_up_persons=self.given_up_persons, invalid=self.invalid, overflow=self.overflow,
+                    unsupported=self.unsupported)
+        reward, done = self.reward, self.done
+        if self.copy_outputs:
+            info = {k: t.clone() for k, t in info.items()}
+            reward, done = reward.clone(), done.clone()
+        return self.observation(), reward, done, info
+
+    def statistics_tensors(self):
+        """env.statistics of every env as [N] tensors (one launch, no host synchronisation)."""
+        _lib.check(self._lib.mg_liftsim_statistics(self._cfg, self.num_envs, _lib.ptr(self.arena), self._stream()),
+                   "mg_liftsim_statistics")
+        import torch
+        N, i64, f64 = self.num_envs, torch.int64, torch.float64
+        return {"DeliveredPersons(10Minutes)": self._view("st_d", i64, (N,)),
+                "GeneratedPersons(10Minutes)": self._view("st_g", i64, (N,)),
+                "AbandonedPersons(10Minutes)": self._view("st_a", i64, (N,)),
+                "EnergyConsumption(10Minutes)": self._view("st_e", f64, (N,)),
+                "TotalWaitingTime(10Minutes)": self._view("st_w", f64, (N,))}
+
+    @property
+    def statistics(self):
+        """[N] tensors of the reference's statistics dict (copies)."""
+        return {k: t.clone() for k, t in self.statistics_tensors().items()}
+
+    def statistics_of(self, e):
+        """Env e's statistics as the reference's dict of Python numbers."""
+        st = self.statistics_tensors()
+        return {k: (int(t[e].item()) if "Persons" in k else float(t[e].item())) for k, t in st.items()}
+
+    def mansion_state(self, e):
+        """Env e's state as the reference's MansionState namedtuple (host copy)."""
+        F = self.F
+        fl = self.floor[e].tolist()
+        vel = self.velocity[e].tolist()
+        dr = self.direction[e].tolist()
+        door = self.door_state[e].tolist()
+        dt_ = self.dispatch_target[e].tolist()
+        dd = self.dispatch_target_direction[e].tolist()
+        lw = self.load_weight[e].tolist()
+        rt = self.reserved_target_floors[e].tolist()
+        rc = self.reserved_count[e].tolist()
+        al = self.overloaded_alarm[e].tolist()
+        op = self.door_is_opening[e].tolist()
+        cl = self.door_is_closing[e].tolist()
+        els = [ElevatorState(fl[k], F, vel[k], MAXIMUM_SPEED, dr[k], door[k], dt_[k], dd[k], lw[k], MAXIMUM_LOAD,
+                             rt[k][:rc[k]], al[k], bool(op[k]), bool(cl[k])) for k in range(self.E)]
+        up = self.requiring_upward[e].tolist()
+        down = self.requiring_downward[e].tolist()
+        return MansionState(els, [i + 1 for i in range(F) if up[i]], [i + 1 for i in range(F) if down[i]])
+
+    def random_state(self, e):
+        """Env e's CPython `random` stream as random.getstate() spells it."""
+        import torch
+        key = self._view("pykey", torch.int32, (self.num_envs, REC))[e].cpu().numpy().view(np.uint32)
+        p = int(self._view("pyp", torch.int32, (self.num_envs,))[e].item())
+        blk, pos = _random_state(key, p)
+        return (3, tuple(int(x) for x in blk) + (pos,), None)
+
+    def numpy_state(self, e):
+        """Env e's numpy stream as numpy.random.get_state() spells it."""
+        import torch
+        key = self._view("npkey", torch.int32, (self.num_envs, REC))[e].cpu().numpy().view(np.uint32)
+        p = int(self._view("npp", torch.int32, (self.num_envs,))[e].item())
+        blk, pos = _random_state(key, p)
+        return ("MT19937", blk.copy(), pos, 0, 0.0)
+

@@ -53,3 +53,8 @@ register("meta-lm-v0", "metagym_amd.metalm:MetaLM", kwargs={"V": 64, "n": 10, "l
 
 # metagym/bandits/__init__.py:18-24
 register("bandits-v0", "metagym_amd.bandits:Bandits", kwargs={"arms": 50, "max_steps": 1000})
+
+# metagym/liftsim/__init__.py:18-26: config_file=None is the reference's own config.ini (metagym_amd.liftsim.DEFAULTS);
+# make("liftsim-v0", config_file=...) reads another, and explicit settings win over either. The CUSTOM generator's flow
+# table is the caller's (`flow_file=`: the reference's mansion_flow.npy, or `flow=`), like quadrupedal's `urdf=`.
+register("liftsim-v0", "metagym_amd.liftsim:LiftSim", kwargs={"config_file": None})
