@@ -977,6 +977,10 @@ enum {
     MG_LS_GIVEN,                                /* i32 [N] */
     MG_LS_ST_D, MG_LS_ST_G, MG_LS_ST_A,         /* i64 [N] statistics sums (mg_liftsim_statistics) */
     MG_LS_ST_E, MG_LS_ST_W,                     /* f64 [N] */
+    /* the rule dispatcher's workspace (mg_liftsim_rule_policy, mg_liftsim_rollout): who holds each hall call and at which
+     * priority, [side][F][N] with side 0 = up, 1 = down. Rewritten by every policy call; not part of the env's state. */
+    MG_LS_RP_HOLDER,                            /* i8 [2][F][N] elevator index, -1 = nobody */
+    MG_LS_RP_PRIORITY,                          /* f64 [2][F][N] */
     MG_LS_NFIELDS
 };
 
@@ -1001,6 +1005,28 @@ int mg_liftsim_step(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, c
 
 /* env.statistics of every env into the ST_* fields: the ring summed newest to oldest from 0, as Python's sum() does. */
 int mg_liftsim_statistics(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, void *stream);
+
+/* Rule_dispatcher.policy(env.state) of every env — replaces metagym/liftsim/tests/rule_benchmark/dispatcher.py
+ * Rule_dispatcher.policy. actions_out: DEVICE int32 [N][2E], ready for mg_liftsim_step; (0, 1) is the dispatcher's
+ * "nothing to do". Reads the state, writes only the RP_* workspace. The dispatcher's FIFO is a ring of
+ * MG_LIFTSIM_MAX_ELEVATORS entries, which the rule cannot overrun; an env that would is flagged
+ * UNSUPPORTED and gets (0, 1) for every elevator. */
+int mg_liftsim_rule_policy(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, int32_t *actions_out, void *stream);
+
+#define MG_LIFTSIM_POLICY_ACTIONS 0   /* step t takes actions[t] */
+#define MG_LIFTSIM_POLICY_RULE 1      /* step t takes the rule dispatcher's actions for the state before it */
+
+/* n_steps env.step() calls of every env in one launch — replaces the loop of Rule_dispatcher.run_dispacher
+ * (policy = RULE: action = policy(env.state); env.step(action); acc_reward += reward) or the same loop over given
+ * actions (policy = ACTIONS: DEVICE int32 [n_steps][N][2E]; NULL with RULE). The arena ends as n_steps mg_liftsim_step
+ * calls leave it, byte for byte. ret: DEVICE f64 [N], the launch's rewards added in step order from 0.0.
+ * Optional records, DEVICE [n_steps][N], NULL = not recorded: reward, time_consume, energy_consume (f64), given_up
+ * (i32); rec_actions (i32 [n_steps][N][2E], RULE only) the actions taken, 0 for a frozen env. Flags as in
+ * mg_liftsim_step: an INVALID action skips that env's step t only (outputs 0; the flag tells of the last step), OVERFLOW
+ * and UNSUPPORTED freeze the env for the rest of the launch and after. n_steps < 1 is MG_ERR_BAD_SIZE. */
+int mg_liftsim_rollout(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, int32_t policy, const int32_t *actions,
+                       int32_t n_steps, double *ret, double *rec_reward, double *rec_time_consume,
+                       double *rec_energy_consume, int32_t *rec_given_up, int32_t *rec_actions, void *stream);
 
 #ifdef __cplusplus
 }

@@ -253,7 +253,9 @@ LIFTSIM_FIELDS = ["pos", "vel", "load", "door", "keep", "alarm", "floor", "dir",
                   "eflags", "targets", "opening", "closing", "clicked", "nloaded", "lw", "lt", "nent", "ew", "et", "el",
                   "nexit", "xw", "xl", "qhead", "qlen", "qw", "qa", "qt", "up", "down", "time", "lastgen", "tidx",
                   "invalid", "overflow", "unsupported", "shead", "scount", "sd", "sg", "sa", "sw", "se", "pykey", "npkey",
-                  "pyp", "pyv", "npp", "npv", "reward", "timec", "energy", "given", "st_d", "st_g", "st_a", "st_e", "st_w"]
+                  "pyp", "pyv", "npp", "npv", "reward", "timec", "energy", "given", "st_d", "st_g", "st_a", "st_e", "st_w",
+                  "rp_holder", "rp_priority"]
+LIFTSIM_POLICY_ACTIONS, LIFTSIM_POLICY_RULE = 0, 1
 
 # symbol -> (restype, argtypes); tests/test_abi.py checks this list against include/metagym_hip.h
 _P = C.c_void_p
@@ -314,6 +316,9 @@ SIGNATURES = {
     "mg_liftsim_reset": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, _P, _P]),
     "mg_liftsim_step": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, _P, _P]),
     "mg_liftsim_statistics": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, _P]),
+    "mg_liftsim_rule_policy": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, _P, _P]),
+    "mg_liftsim_rollout": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P,
+                                     _P, _P, _P]),
     "mg_bandits_seed": (C.c_int, [C.c_int32, C.c_uint32, _P, C.POINTER(BanditsState), _P]),
     "mg_bandits_sample_task": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P, _P]),
     "mg_bandits_reset": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P]),

@@ -16,6 +16,10 @@
 // person of a queue); the stream records are [N][1248] (two key blocks per stream). A stream never refills inside a
 // step: between steps the wave writes the refill of every lane's current block into its other block (refill_ahead), so
 // draws are lane-local reads however divergent the lanes are.
+//
+// The step is a device function (step_body) shared by liftsim_step_kernel and liftsim_rollout_kernel; the latter runs
+// {refill, actions, step} T times in one launch, the actions read from actions[t] or made on the spot by rule_policy, the
+// reference's rule-based dispatcher (tests/rule_benchmark/dispatcher.py Rule_dispatcher.policy) as a lane-local function.
 #include <cmath>
 
 #include "mg_common.h"
@@ -28,6 +32,7 @@ constexpr int REC = 2 * MTN;   // u32 words of one lane's stream record
 constexpr double EPS = 1.0e-2, GRAV = 9.80, MAX_ACC = 1.0, MAX_SPD = 2.0, ENTER_T = 2.0, DOOR_V = 0.5;
 constexpr double DOOR_P = 350.0, STANDBY_P = 100.0, MAX_LOAD = 1600.0, RATED = 600.0, NET = 300.0, PULLEY = 0.27;
 constexpr double MOTOR_EFF = 0.8, GIVE_UP = 300.0;
+constexpr double HUGE_PRIORITY = 1.0e8;   // mansion/utils.py HUGE
 constexpr int MPEE = 2, LCAP = MG_LIFTSIM_LOAD_CAP, QN = MG_LIFTSIM_QN;
 
 struct Lay {
@@ -64,6 +69,8 @@ Lay layout(int F, int E, int Q, int W, int64_t n) {
     sz[MG_LS_REWARD] = sz[MG_LS_TIMEC] = sz[MG_LS_ENERGY] = 8 * n;
     sz[MG_LS_GIVEN] = 4 * n;
     sz[MG_LS_ST_D] = sz[MG_LS_ST_G] = sz[MG_LS_ST_A] = sz[MG_LS_ST_E] = sz[MG_LS_ST_W] = 8 * n;
+    sz[MG_LS_RP_HOLDER] = 2 * F * n;
+    sz[MG_LS_RP_PRIORITY] = 8 * 2 * F * n;
     Lay l{};
     int64_t o = 0;
     for (int f = 0; f < MG_LS_NFIELDS; ++f) {
@@ -596,6 +603,7 @@ __global__ __launch_bounds__(64) void liftsim_seed_kernel(K k, Lay l, int n, uin
     s.i(MG_LS_PYP) = MTN; s.i(MG_LS_PYV) = 1; s.i(MG_LS_NPP) = MTN; s.i(MG_LS_NPV) = 1;
     s.i(MG_LS_TIDX) = 0; s.i(MG_LS_SHEAD) = 0; s.i(MG_LS_SCOUNT) = 0;
     s.b(MG_LS_OVERFLOW) = 0; s.b(MG_LS_UNSUPPORTED) = 0;
+    for (int q = 0; q < 2 * k.F; ++q) { s.at<int8_t>(MG_LS_RP_HOLDER, q) = 0; s.d(MG_LS_RP_PRIORITY, q) = 0.0; }
     reset_env(s, k);
     zero_outputs(s);
 }
@@ -606,33 +614,173 @@ __global__ __launch_bounds__(64) void liftsim_reset_kernel(K k, Lay l, int n, ui
     reset_env(Env{arena, &l, n, e}, k);
 }
 
-__global__ __launch_bounds__(64) void liftsim_step_kernel(K k, Lay l, int n, uint8_t *arena, const int32_t *actions) {
-    __shared__ uint32_t lds[MTN];
-    __shared__ uint8_t order[MG_LIFTSIM_MAX_ELEVATORS][64];   // the lane's shuffled elevator indices, in its own column
-    const int lane = threadIdx.x, e0 = blockIdx.x * 64, e = e0 + lane;
-    const bool live = e < n;
-    const Env s{arena, &l, n, live ? e : e0};
-    // restore both streams' next block, a wave job
-    {
-        int p = 0, r = 1;
-        if (live) { p = s.i(MG_LS_PYP); r = s.i(MG_LS_PYV); }
-        uint64_t bal = __ballot(live && !r);
-        uint32_t *base = reinterpret_cast<uint32_t *>(arena + l.off[MG_LS_PYKEY]) + (size_t)e0 * REC;
-        if (bal) mt::refill_ahead(lds, base, REC, bal, ((p + REC - 1) % REC) / MTN, lane);
-        if (live && !r) s.i(MG_LS_PYV) = 1;
-        p = 0; r = 1;
-        if (live) { p = s.i(MG_LS_NPP); r = s.i(MG_LS_NPV); }
-        bal = __ballot(live && !r);
-        base = reinterpret_cast<uint32_t *>(arena + l.off[MG_LS_NPKEY]) + (size_t)e0 * REC;
-        if (bal) mt::refill_ahead(lds, base, REC, bal, ((p + REC - 1) % REC) / MTN, lane);
-        if (live && !r) s.i(MG_LS_NPV) = 1;
+// Wave job (all 64 lanes): restore both streams' next key block for the lanes that used theirs up.
+__device__ void refill_streams(const Env &s, const Lay &l, uint8_t *arena, uint32_t *lds, bool live, int e0, int lane) {
+    int p = 0, r = 1;
+    if (live) { p = s.i(MG_LS_PYP); r = s.i(MG_LS_PYV); }
+    uint64_t bal = __ballot(live && !r);
+    uint32_t *base = reinterpret_cast<uint32_t *>(arena + l.off[MG_LS_PYKEY]) + (size_t)e0 * REC;
+    if (bal) mt::refill_ahead(lds, base, REC, bal, ((p + REC - 1) % REC) / MTN, lane);
+    if (live && !r) s.i(MG_LS_PYV) = 1;
+    p = 0; r = 1;
+    if (live) { p = s.i(MG_LS_NPP); r = s.i(MG_LS_NPV); }
+    bal = __ballot(live && !r);
+    base = reinterpret_cast<uint32_t *>(arena + l.off[MG_LS_NPKEY]) + (size_t)e0 * REC;
+    if (bal) mt::refill_ahead(lds, base, REC, bal, ((p + REC - 1) % REC) / MTN, lane);
+    if (live && !r) s.i(MG_LS_NPV) = 1;
+}
+
+// Where a step's actions come from: the caller's int32 [2E] row, or the lane's column of the dispatcher's LDS output.
+struct RowActions {
+    const int32_t *a;
+    __device__ __forceinline__ int target(int el) const { return a[2 * el]; }
+    __device__ __forceinline__ int direction(int el) const { return a[2 * el + 1]; }
+};
+
+struct LaneActions {
+    uint8_t (*tf)[64];
+    int8_t (*dir)[64];
+    int lane;
+    __device__ __forceinline__ int target(int el) const { return tf[el][lane]; }
+    __device__ __forceinline__ int direction(int el) const { return dir[el][lane]; }
+    __device__ __forceinline__ void set(int el, int t, int d) const { tf[el][lane] = (uint8_t)t; dir[el][lane] = (int8_t)d; }
+};
+
+// Rule_dispatcher.policy(env.state) (tests/rule_benchmark/dispatcher.py) for this lane's env: the actions into `out`.
+//
+// Every hall call (floor, side) has a holder and the holder's priority (the reference's two address dictionaries):
+// RP_HOLDER / RP_PRIORITY, [side * F + floor - 1][N] in the arena. The elevators wait in a FIFO, 0..E-1 at first; the one
+// in front bids by its Direction, and an elevator that loses its call joins the FIFO again. The quirks are the
+// reference's: the down branch emits indicator +1; a fallback writes a priority without comparing one and displaces
+// nobody; the Direction == 0 branch does not put the loser's action back to (0, 1); Velocity < EPSILON is signed.
+//
+// The FIFO is a ring of MG_LIFTSIM_MAX_ELEVATORS entries in LDS. It cannot overrun: with c_i the copies of elevator i in
+// the FIFO and h_i the calls it holds, c_i + h_i starts at 1 and never grows (a dequeue takes one copy and gives at
+// most one call, a displacement takes one call and gives one copy), so the FIFO holds at most E entries at any time.
+// It ends: a call's priority strictly rises with every take after the first, and an elevator's bid for a call is a
+// fixed number. A push on a full ring returns false all the same (the caller flags `unsupported`).
+__device__ bool rule_policy(const Env &s, const K &k, uint8_t (*ring)[64], const LaneActions &out) {
+    const int F = k.F, E = k.E, lane = out.lane;
+    constexpr int RING = MG_LIFTSIM_MAX_ELEVATORS;
+    uint32_t up[4], dn[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        uint32_t u = 0, d = 0;
+        const int nb = min(32, F - 32 * w);
+        for (int b = 0; b < nb; ++b) {
+            const int f = 32 * w + b;
+            u |= (uint32_t)(s.b(MG_LS_UP, f) != 0) << b;
+            d |= (uint32_t)(s.b(MG_LS_DOWN, f) != 0) << b;
+            s.at<int8_t>(MG_LS_RP_HOLDER, f) = -1; s.at<int8_t>(MG_LS_RP_HOLDER, F + f) = -1;
+            s.d(MG_LS_RP_PRIORITY, f) = -HUGE_PRIORITY; s.d(MG_LS_RP_PRIORITY, F + f) = -HUGE_PRIORITY;
+        }
+        up[w] = u; dn[w] = d;
     }
-    if (!live) return;
+    for (int el = 0; el < E; ++el) { ring[el][lane] = (uint8_t)el; out.set(el, 0, 1); }
+    int head = 0, cnt = E;
+    bool ok = true;
+    auto push = [&](int el) {
+        if (cnt == RING) { ok = false; return; }
+        ring[(head + cnt) & (RING - 1)][lane] = (uint8_t)el;
+        ++cnt;
+    };
+    while (cnt > 0 && ok) {
+        const int el = ring[head][lane];
+        head = (head + 1) & (RING - 1);
+        --cnt;
+        const int dir = s.i(MG_LS_DIR, el);
+        const double fl = s.d(MG_LS_FLOOR, el);
+        if (dir != 0) {
+            const bool upw = dir > 0;
+            const int side = upw ? 0 : F, other = upw ? F : 0;
+            const bool slow = s.d(MG_LS_VEL, el) < EPS;
+            // ReservedTargetFloors as a bit set
+            uint32_t tm[4] = {0, 0, 0, 0};
+            const int nt = s.i(MG_LS_NTARGET, el);
+            for (int j = 0; j < nt; ++j) {
+                const int t = s.i(MG_LS_TARGETS, (int64_t)el * F + j) - 1;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) tm[w] |= (t >> 5) == w ? 1u << (t & 31) : 0u;
+            }
+            double sel_p = -HUGE_PRIORITY;
+            int sel = -1;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                uint32_t bits = upw ? up[w] : dn[w];
+                while (bits) {
+                    const int b = __builtin_ctz(bits);
+                    bits &= bits - 1;
+                    const int f = 32 * w + b + 1;
+                    const double ff = (double)f;
+                    if (upw ? ff < fl - EPS : ff > fl + EPS) continue;
+                    double p = upw ? fl - ff : -fl + ff;
+                    if ((tm[w] >> b) & 1u) { p = p + 5.0; p = p < 0.0 ? p : 0.0; }
+                    if (slow) p -= 5.0;
+                    if (p > s.d(MG_LS_RP_PRIORITY, side + f - 1) && p > sel_p) { sel_p = p; sel = f; }
+                }
+            }
+            if (sel > 0) {
+                out.set(el, sel, 1);
+                const int h = s.at<int8_t>(MG_LS_RP_HOLDER, side + sel - 1);
+                if (h >= 0) { out.set(h, 0, 1); push(h); }
+                s.at<int8_t>(MG_LS_RP_HOLDER, side + sel - 1) = (int8_t)el;
+                s.d(MG_LS_RP_PRIORITY, side + sel - 1) = sel_p;
+            } else {
+                // nothing to take on its own side: the highest unheld down call (moving up), the lowest unheld up call
+                int found = -1;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t bits = upw ? dn[w] : up[w];
+                    while (bits) {
+                        const int b = __builtin_ctz(bits);
+                        bits &= bits - 1;
+                        const int f = 32 * w + b + 1;
+                        if (s.at<int8_t>(MG_LS_RP_HOLDER, other + f - 1) < 0 && (upw || found < 0)) found = f;
+                    }
+                }
+                if (found >= 0) {
+                    out.set(el, found, upw ? -1 : 1);
+                    s.at<int8_t>(MG_LS_RP_HOLDER, other + found - 1) = (int8_t)el;
+                    s.d(MG_LS_RP_PRIORITY, other + found - 1) = upw ? -fl - EPS + (double)found : fl + EPS - (double)found;
+                }
+            }
+        } else {
+            double sel_p = -HUGE_PRIORITY;
+            int sel = -1, side = 0;
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t bits = half == 0 ? up[w] : dn[w];
+                    while (bits) {
+                        const int b = __builtin_ctz(bits);
+                        bits &= bits - 1;
+                        const int f = 32 * w + b + 1;
+                        const double p = -fabs((double)f - fl);
+                        if (p > s.d(MG_LS_RP_PRIORITY, half * F + f - 1) && p > sel_p) { sel_p = p; sel = f; side = half * F; }
+                    }
+                }
+            }
+            if (sel > 0) {
+                out.set(el, sel, side == 0 ? 1 : -1);
+                const int h = s.at<int8_t>(MG_LS_RP_HOLDER, side + sel - 1);
+                if (h >= 0) push(h);   // its action stays as it is
+                s.at<int8_t>(MG_LS_RP_HOLDER, side + sel - 1) = (int8_t)el;
+                s.d(MG_LS_RP_PRIORITY, side + sel - 1) = sel_p;
+            }
+        }
+    }
+    return ok;
+}
+
+// One env.step(action) of this lane's env (the wave's stream refill comes first, outside). Frozen and invalid envs leave
+// early with zero outputs.
+template <class Actions>
+__device__ void step_body(const Env &s, const K &k, int lane, uint8_t (*order)[64], const Actions &act) {
     if (s.b(MG_LS_OVERFLOW) || s.b(MG_LS_UNSUPPORTED)) { zero_outputs(s); return; }
-    const int32_t *act = actions + (size_t)e * (size_t)(2 * k.E);
     bool bad = false;
     for (int el = 0; el < k.E; ++el) {
-        const int tf = act[2 * el], d = act[2 * el + 1];
+        const int tf = act.target(el), d = act.direction(el);
         bad |= tf < -1 || tf > k.F || d < -1 || d > 1;
     }
     s.b(MG_LS_INVALID) = bad;
@@ -654,8 +802,8 @@ __global__ __launch_bounds__(64) void liftsim_step_kernel(K k, Lay l, int n, uin
         return;
     }
     for (int el = 0; el < k.E; ++el) {
-        const int tf = act[2 * el];
-        if (tf >= 0) { s.i(MG_LS_DISPATCH, el) = tf; s.i(MG_LS_DISPATCH_DIR, el) = act[2 * el + 1]; }
+        const int tf = act.target(el);
+        if (tf >= 0) { s.i(MG_LS_DISPATCH, el) = tf; s.i(MG_LS_DISPATCH_DIR, el) = act.direction(el); }
     }
     double energy = 0.0;   // Python's sum() from int 0, in index order
     int delivered = 0, loaded = 0;
@@ -707,6 +855,83 @@ __global__ __launch_bounds__(64) void liftsim_step_kernel(K k, Lay l, int n, uin
     s.d(MG_LS_SW, head) = waiting; s.d(MG_LS_SE, head) = energy;
     s.i(MG_LS_PYP) = py.p; s.i(MG_LS_PYV) = py.ready;
     s.i(MG_LS_NPP) = npg.p; s.i(MG_LS_NPV) = npg.ready;
+}
+
+__global__ __launch_bounds__(64) void liftsim_step_kernel(K k, Lay l, int n, uint8_t *arena, const int32_t *actions) {
+    __shared__ uint32_t lds[MTN];
+    __shared__ uint8_t order[MG_LIFTSIM_MAX_ELEVATORS][64];   // the lane's shuffled elevator indices, in its own column
+    const int lane = threadIdx.x, e0 = blockIdx.x * 64, e = e0 + lane;
+    const bool live = e < n;
+    const Env s{arena, &l, n, live ? e : e0};
+    refill_streams(s, l, arena, lds, live, e0, lane);
+    if (!live) return;
+    step_body(s, k, lane, order, RowActions{actions + (size_t)e * (size_t)(2 * k.E)});
+}
+
+struct Records {
+    double *ret, *reward, *timec, *energy;
+    int32_t *given, *actions;
+};
+
+// T steps in one launch: per step the wave's stream refill, then the actions (row t of `actions`, or rule_policy on the
+// state as it stands), then the step. Every lane stays in the loop for the next refill: a frozen or invalid env leaves
+// step_body early, not the kernel. ret[e] adds the T rewards in step order from 0.0.
+template <bool RULE>
+__global__ __launch_bounds__(64) void liftsim_rollout_kernel(K k, Lay l, int n, uint8_t *arena, const int32_t *actions,
+                                                             int T, Records rec) {
+    __shared__ uint32_t lds[MTN];
+    __shared__ uint8_t order[MG_LIFTSIM_MAX_ELEVATORS][64];
+    __shared__ uint8_t ring[RULE ? MG_LIFTSIM_MAX_ELEVATORS : 1][64];
+    __shared__ uint8_t atf[RULE ? MG_LIFTSIM_MAX_ELEVATORS : 1][64];
+    __shared__ int8_t adir[RULE ? MG_LIFTSIM_MAX_ELEVATORS : 1][64];
+    const int lane = threadIdx.x, e0 = blockIdx.x * 64, e = e0 + lane;
+    const bool live = e < n;
+    const Env s{arena, &l, n, live ? e : e0};
+    const size_t A = (size_t)(2 * k.E);
+    double acc = 0.0;
+    for (int t = 0; t < T; ++t) {
+        refill_streams(s, l, arena, lds, live, e0, lane);
+        if (live) {
+            const size_t at = (size_t)t * (size_t)n + (size_t)e;
+            if (RULE) {
+                const LaneActions la{atf, adir, lane};
+                const bool frozen = s.b(MG_LS_OVERFLOW) || s.b(MG_LS_UNSUPPORTED);
+                if (!frozen && !rule_policy(s, k, ring, la)) s.b(MG_LS_UNSUPPORTED) = 1;
+                step_body(s, k, lane, order, la);
+                if (rec.actions != nullptr)
+                    for (int el = 0; el < k.E; ++el) {
+                        rec.actions[at * A + 2 * el] = frozen ? 0 : la.target(el);
+                        rec.actions[at * A + 2 * el + 1] = frozen ? 0 : la.direction(el);
+                    }
+            } else {
+                step_body(s, k, lane, order, RowActions{actions + at * A});
+            }
+            acc += s.d(MG_LS_REWARD);
+            if (rec.reward != nullptr) rec.reward[at] = s.d(MG_LS_REWARD);
+            if (rec.timec != nullptr) rec.timec[at] = s.d(MG_LS_TIMEC);
+            if (rec.energy != nullptr) rec.energy[at] = s.d(MG_LS_ENERGY);
+            if (rec.given != nullptr) rec.given[at] = s.i(MG_LS_GIVEN);
+        }
+    }
+    if (live) rec.ret[e] = acc;
+}
+
+// Rule_dispatcher.policy for every env, the actions as int32 [N][2E]
+__global__ __launch_bounds__(64) void liftsim_rule_policy_kernel(K k, Lay l, int n, uint8_t *arena, int32_t *actions) {
+    __shared__ uint8_t ring[MG_LIFTSIM_MAX_ELEVATORS][64];
+    __shared__ uint8_t atf[MG_LIFTSIM_MAX_ELEVATORS][64];
+    __shared__ int8_t adir[MG_LIFTSIM_MAX_ELEVATORS][64];
+    const int lane = threadIdx.x, e = blockIdx.x * 64 + lane;
+    if (e >= n) return;
+    const Env s{arena, &l, n, e};
+    const LaneActions la{atf, adir, lane};
+    const bool ok = rule_policy(s, k, ring, la);
+    if (!ok) s.b(MG_LS_UNSUPPORTED) = 1;
+    int32_t *row = actions + (size_t)e * (size_t)(2 * k.E);
+    for (int el = 0; el < k.E; ++el) {
+        row[2 * el] = ok ? la.target(el) : 0;
+        row[2 * el + 1] = ok ? la.direction(el) : 1;
+    }
 }
 
 __global__ __launch_bounds__(64) void liftsim_statistics_kernel(K k, Lay l, int n, uint8_t *arena) {
@@ -828,4 +1053,43 @@ extern "C" int mg_liftsim_statistics(const mg_liftsim_config *cfg, int32_t n_env
     hipLaunchKernelGGL(liftsim_statistics_kernel, grid(n_envs), dim3(64), 0, static_cast<hipStream_t>(stream), fold(cfg),
                        lay(cfg, n_envs), n_envs, static_cast<uint8_t *>(arena));
     return mg::check_launch("liftsim_statistics_kernel");
+}
+
+extern "C" int mg_liftsim_rule_policy(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, int32_t *actions_out,
+                                      void *stream) {
+    MG_REQUIRE_PTR(cfg);
+    MG_REQUIRE_PTR(arena);
+    MG_REQUIRE_PTR(actions_out);
+    const int rc = check(cfg, n_envs, "mg_liftsim_rule_policy");
+    if (rc != MG_OK) return rc;
+    mg::DeviceGuard guard(mg::device_of(arena));
+    hipLaunchKernelGGL(liftsim_rule_policy_kernel, grid(n_envs), dim3(64), 0, static_cast<hipStream_t>(stream), fold(cfg),
+                       lay(cfg, n_envs), n_envs, static_cast<uint8_t *>(arena), actions_out);
+    return mg::check_launch("liftsim_rule_policy_kernel");
+}
+
+extern "C" int mg_liftsim_rollout(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, int32_t policy,
+                                  const int32_t *actions, int32_t n_steps, double *ret, double *rec_reward,
+                                  double *rec_time_consume, double *rec_energy_consume, int32_t *rec_given_up,
+                                  int32_t *rec_actions, void *stream) {
+    MG_REQUIRE_PTR(cfg);
+    MG_REQUIRE_PTR(arena);
+    MG_REQUIRE_PTR(ret);
+    if (policy == MG_LIFTSIM_POLICY_ACTIONS) MG_REQUIRE_PTR(actions);
+    const int rc = check(cfg, n_envs, "mg_liftsim_rollout");
+    if (rc != MG_OK) return rc;
+    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_liftsim_rollout: n_steps = %d", n_steps);
+    if (policy != MG_LIFTSIM_POLICY_ACTIONS && policy != MG_LIFTSIM_POLICY_RULE)
+        return mg::set_error(MG_ERR_BAD_CONFIG, "mg_liftsim_rollout: policy = %d", policy);
+    if (policy == MG_LIFTSIM_POLICY_ACTIONS && rec_actions != nullptr)
+        return mg::set_error(MG_ERR_BAD_CONFIG, "mg_liftsim_rollout: rec_actions records the rule policy's actions only");
+    mg::DeviceGuard guard(mg::device_of(arena));
+    const Records rec{ret, rec_reward, rec_time_consume, rec_energy_consume, rec_given_up, rec_actions};
+    if (policy == MG_LIFTSIM_POLICY_RULE)
+        hipLaunchKernelGGL(liftsim_rollout_kernel<true>, grid(n_envs), dim3(64), 0, static_cast<hipStream_t>(stream),
+                           fold(cfg), lay(cfg, n_envs), n_envs, static_cast<uint8_t *>(arena), actions, n_steps, rec);
+    else
+        hipLaunchKernelGGL(liftsim_rollout_kernel<false>, grid(n_envs), dim3(64), 0, static_cast<hipStream_t>(stream),
+                           fold(cfg), lay(cfg, n_envs), n_envs, static_cast<uint8_t *>(arena), actions, n_steps, rec);
+    return mg::check_launch("liftsim_rollout_kernel");
 }

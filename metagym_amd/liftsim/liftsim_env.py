@@ -1,4 +1,5 @@
-"""LiftSim (reference metagym/liftsim/environment/env.py) for N buildings at once, stepped by `mg_liftsim_step` on the GPU."""
+"""LiftSim (reference metagym/liftsim/environment/env.py) for N buildings at once, stepped by `mg_liftsim_step` on the GPU;
+the reference's rule-based dispatcher (`rule_policy`) and whole rollouts in one launch (`rollout`) run there too."""
 import collections
 import configparser
 import ctypes as C
@@ -216,6 +217,7 @@ class LiftSim(object):
         self.unsupported = v("unsupported", u8, (N,))
         self.done = torch.zeros(N, dtype=torch.bool, device=self.device)   # always False, as in the reference
         self.queue_capacity, self._Q, self._W = Q, Q, W
+        self._rule_actions = torch.zeros(N, 2 * E, dtype=i32, device=self.device)   # rule_policy()'s output
         self.seed(seed, seeds)
 
     # ------------------------------------------------------------------ plumbing
@@ -305,6 +307,62 @@ class LiftSim(object):
             info = {k: t.clone() for k, t in info.items()}
             reward, done = reward.clone(), done.clone()
         return self.observation(), reward, done, info
+
+    def rule_policy(self):
+        """The reference's rule-based dispatcher (tests/rule_benchmark/dispatcher.py Rule_dispatcher.policy) on every
+        env's current state: int32 [N, 2E], so `env.step(env.rule_policy())` is one step of its run_dispacher. One launch,
+        no host synchronisation; the result is a persistent buffer (a copy with copy_outputs=True)."""
+        _lib.check(self._lib.mg_liftsim_rule_policy(self._cfg, self.num_envs, _lib.ptr(self.arena),
+                                                    _lib.ptr(self._rule_actions), self._stream()),
+                   "mg_liftsim_rule_policy")
+        return self._rule_actions.clone() if self.copy_outputs else self._rule_actions
+
+    RECORDS = ("reward", "time_consume", "energy_consume", "given_up_persons", "actions")
+
+    def rollout(self, actions=None, steps=None, policy=None, record=("reward",)):
+        """T steps of every env in one launch: over `actions` (int32 [T, N, 2E]), or with policy="rule" and steps=T over
+        the rule dispatcher's own actions (run_dispacher's loop); exactly one of the two. Returns a dict: "return" [N],
+        the T rewards added in step order from 0.0, and the [T, N] records named in `record` (of RECORDS; "actions",
+        [T, N, 2E], with policy="rule" only). The arena, and so every observation view, ends as after T step() calls.
+        No host synchronisation; the returned tensors are new ones."""
+        import torch
+        N, E = self.num_envs, self.E
+        if (actions is None) == (policy is None):
+            raise ValueError("rollout takes either actions or policy=\"rule\" with steps")
+        if policy is not None:
+            if policy != "rule":
+                raise ValueError("unknown policy %r (the one built here is \"rule\")" % (policy,))
+            if steps is None or int(steps) < 1:
+                raise ValueError("rollout(policy=\"rule\") needs steps >= 1")
+            T, a, mode = int(steps), None, _lib.LIFTSIM_POLICY_RULE
+        else:
+            a = torch.as_tensor(actions, device=self.device)
+            if a.dim() != 3 or tuple(a.shape[1:]) != (N, 2 * E) or a.shape[0] < 1:
+                raise ValueError("actions must have shape [T, %d, %d] with T >= 1" % (N, 2 * E))
+            if steps is not None and int(steps) != a.shape[0]:
+                raise ValueError("steps = %d but actions holds %d steps" % (int(steps), a.shape[0]))
+            if a.dtype != torch.int32:
+                a = a.to(torch.int32)
+            a = a.contiguous()
+            T, mode = int(a.shape[0]), _lib.LIFTSIM_POLICY_ACTIONS
+        record = (record,) if isinstance(record, str) else tuple(record or ())
+        unknown = set(record) - set(self.RECORDS)
+        if unknown:
+            raise ValueError("unknown records: %s (known: %s)" % (sorted(unknown), list(self.RECORDS)))
+        if "actions" in record and mode != _lib.LIFTSIM_POLICY_RULE:
+            raise ValueError("the actions record is for policy=\"rule\"; given actions are the caller's already")
+        out = {"return": torch.empty(N, dtype=torch.float64, device=self.device)}
+        for name in record:
+            if name == "actions":
+                out[name] = torch.empty(T, N, 2 * E, dtype=torch.int32, device=self.device)
+            else:
+                out[name] = torch.empty(T, N, dtype=torch.int32 if name == "given_up_persons" else torch.float64,
+                                        device=self.device)
+        _lib.check(self._lib.mg_liftsim_rollout(
+            self._cfg, N, _lib.ptr(self.arena), mode, _lib.ptr(a), T, _lib.ptr(out["return"]),
+            _lib.ptr(out.get("reward")), _lib.ptr(out.get("time_consume")), _lib.ptr(out.get("energy_consume")),
+            _lib.ptr(out.get("given_up_persons")), _lib.ptr(out.get("actions")), self._stream()), "mg_liftsim_rollout")
+        return out
 
     def statistics_tensors(self):
         """env.statistics of every env as [N] tensors (one launch, no host synchronisation)."""
