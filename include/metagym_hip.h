@@ -374,6 +374,34 @@ int mg_maze3d_step(const mg_maze_tasks *tasks, const mg_maze_view *view, int32_t
                    const void *action, void *obs, float *reward, double *reward64, uint8_t *done,
                    void *stream);
 
+/* Rollouts: n_steps steps per call, by definition the loop `for t: mg_maze*_step(action = actions[t])` on the same state —
+ * same transitions, rewards, dones, auto-resets and end state bit for bit, also for an env without auto_reset that is
+ * stepped past done (it goes on stepping, as in the batched step). Additive entry points; MG_ABI_VERSION is unchanged.
+ *   n_steps >= 1. obs_every selects the steps that leave an observation: 0 = the last step only; k >= 1 = every step t
+ *   (0-based) with (t + 1) % k == 0, and always the last one. K = number of recorded steps, in ascending order.
+ *   reward f32 [n_steps][N] (may be NULL), reward64 f64 [n_steps][N] (may be NULL), done u8 [n_steps][N].
+ *   obs: K slices of the matching step's obs, [K][N]...; slice k is the observation after recorded step k (with auto_reset:
+ *   the first observation of the next episode where that step ended one).
+ * Errors are found on the host before anything is launched: NULL pointers, n_steps < 1, obs_every < 0 (MG_ERR_BAD_SIZE),
+ * and whatever the matching step refuses. Nothing is allocated and nothing synchronises (stream capture works as for the steps;
+ * for the 3-D call an unchecked mg_maze_view.uniform_cell_size is refused under capture exactly as mg_maze3d_step refuses it).
+ *
+ * mg_maze2d_rollout — MetaMaze2D.step (maze_env.py:189-204 -> maze_2d.py:21-34 + maze_base.py:65-95) n_steps times and
+ * update_observation (maze_2d.py:89-121) on the recorded steps: ONE launch. actions i32 [n_steps][N] in 0..3. */
+int mg_maze2d_rollout(const mg_maze_tasks *tasks, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                      int32_t auto_reset, int32_t n_envs, const mg_maze_state *state, int32_t n_steps, int32_t obs_every,
+                      const int32_t *actions, float *obs, float *reward, double *reward64, uint8_t *done, void *stream);
+
+/* mg_maze3d_rollout — MetaMazeDiscrete3D.step (maze_env.py:59-75 -> maze_discrete_3d.py:51-81) or, with continuous != 0,
+ * MetaMazeContinuous3D.step (maze_env.py:129-145 -> maze_continuous_3d.py:47-56 -> dynamics.py:71-92) n_steps times; the
+ * first-person render (ray_caster_utils.py:66-209) runs for the recorded steps only. TWO launches per recorded step (the steps
+ * up to it without a picture, then the renderer of mg_maze3d_step in its observe-only form): 2K in all, 2 with obs_every 0.
+ *   actions: discrete i32 [n_steps][N]; continuous f32 [n_steps][N][2]. obs as mg_maze3d_step's, K slices. */
+int mg_maze3d_rollout(const mg_maze_tasks *tasks, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                      int32_t continuous, int32_t auto_reset, int32_t n_envs, const mg_maze_state *state, int32_t n_steps,
+                      int32_t obs_every, const void *actions, void *obs, float *reward, double *reward64, uint8_t *done,
+                      void *stream);
+
 /* ========================================================================================
  * MetaLocomotion walkers (humanoid / ant) — replaces, for N envs, WalkerBaseEnv.step
  * (metalocomotion/envs/utils/walker_base_env.py:43-82) including the physics the reference

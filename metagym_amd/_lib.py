@@ -288,6 +288,11 @@ SIGNATURES = {
     "mg_maze_forget_tasks": (C.c_int, [C.POINTER(MazeTasks)]),
     "mg_maze3d_step": (C.c_int, [C.POINTER(MazeTasks), C.POINTER(MazeView), C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_int32, C.POINTER(MazeState), _P, _P, _P, _P, _P, _P]),
+    "mg_maze2d_rollout": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(MazeState), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mg_maze3d_rollout": (C.c_int, [C.POINTER(MazeTasks), C.POINTER(MazeView), C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int32, C.POINTER(MazeState), C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                    _P]),
     "mg_walker_reset": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
                                   C.c_int32, C.POINTER(WalkerState), _P, _P, _P, _P]),
     "mg_walker_step": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),

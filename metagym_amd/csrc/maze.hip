@@ -8,6 +8,8 @@
 //   vector_move_with_collision & friends      dynamics.py:17-92                 (transition_continuous)
 //   DDA_2D / maze_view                        ray_caster_utils.py:11-62, :66-209 (column_pass, pixel_pass)
 //   life bar overlay                          maze_discrete_3d.py:118-126       (pixel_pass)
+//   MetaMaze2D.step, T times per launch       maze_env.py:189-204               (maze2d_rollout_kernel)
+//   the 3-D steps without their picture       maze_env.py:59-75, :129-145       (maze3d_advance_kernel)
 //
 // Design (MI355X)
 //   * 2-D maze: integer grid logic + a (2v+1)^2 window -> one lane per env, SoA state.
@@ -1072,6 +1074,146 @@ __global__ __launch_bounds__(MZ_BLOCK) void maze_cont_move_kernel(mg_maze_tasks 
     st.loc[n_envs + e] = a.ly;
 }
 
+// ------------------------------------------------------------------------------------------------
+// rollouts: T steps per call (mg_maze2d_rollout, mg_maze3d_rollout)
+// ------------------------------------------------------------------------------------------------
+
+// Which steps of a rollout leave an observation: obs_every = 0 the last one only, k >= 1 the steps t with (t + 1) % k == 0 and
+// always the last one (metamaze/maze_env.py rollout_obs_steps restates the rule for the host).
+__host__ __device__ __forceinline__ bool rollout_records(int t, int n_steps, int obs_every) {
+    return t == n_steps - 1 || (obs_every > 0 && (t + 1) % obs_every == 0);
+}
+
+// update_observation maze_2d.py:89-121, value by value as maze2d_step_kernel computes it; `put(i, v)` receives window entry i.
+template <class Put>
+__device__ __forceinline__ void observe_2d(const Task &t, const mg_maze_state &st, int e, int task_type, int vg, const Agent &a,
+                                           Put &&put) {
+    const int w = 2 * vg + 1;
+    for (int p = 0; p < w; ++p)
+        for (int q = 0; q < w; ++q) {
+            const int x = a.gx - vg + p, y = a.gy - vg + q;
+            float v = -1.0f;
+            if (x >= 0 && x < t.n && y >= 0 && y < t.n) {
+                v = (float)(-(int)t.walls[x * t.n + y]);                                   // :113
+                if (task_type == MG_MAZE_SURVIVAL) {                                       // :117
+                    double food;
+                    if (st.food_by_slot) {
+                        const int k = t.cell_slot[x * t.n + y];
+                        food = k >= 0 ? st.cur_food[fidx(st, e, k)] : (k == -1 ? 0.0 : t.food[x * t.n + y]);
+                    } else food = st.cur_food[fidx(st, e, x * t.n + y)];
+                    v = (float)((double)v + food);
+                }
+                else v = (float)((double)v + ((x == t.gx && y == t.gy) ? 1.0 : 0.0));       // :120
+            }
+            if (task_type == MG_MAZE_SURVIVAL && p == vg && q == vg) v = (float)a.life;     // :118
+            put(p * w + q, v);
+        }
+}
+
+// MetaMaze2D.step (maze_env.py:189-204 -> maze_2d.py:21-34 + maze_base.py:65-95) n_steps times, one lane per env, one wave per
+// workgroup. Task and agent stay in registers for the whole call; the SURVIVAL cells go through the same eval_scalar /
+// eval_cells / reset_cells as the step kernel (a lane only ever reads its own writes). STAGE: the 64 windows of the wave are
+// written to LDS lane-major (lane * w*w + i; w*w is odd, so the 32 lanes of a ds_write_b32 group fall on 32 different banks) and
+// leave as one contiguous run of 64 * w*w floats, 256 bytes per store instruction; !STAGE keeps the step kernel's per-lane
+// store (one dword per lane at a stride of w*w floats) for windows too large for LDS.
+constexpr int MZ_ROLL_BLOCK = mg::WAVE;
+template <bool STAGE>
+__global__ __launch_bounds__(MZ_ROLL_BLOCK) void maze2d_rollout_kernel(mg_maze_tasks T, mg_maze_state st, int task_type,
+                                                                       int max_steps, int vg, int auto_reset, int n_envs,
+                                                                       int n_steps, int obs_every, const int32_t *actions,
+                                                                       float *obs, float *reward, double *reward64,
+                                                                       uint8_t *done) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *tile = reinterpret_cast<float *>(smem);             // STAGE: [64][w*w]
+    const int lane = threadIdx.x;
+    const int e0 = blockIdx.x * MZ_ROLL_BLOCK;                 // first env of this wave
+    const int e = e0 + lane;
+    const bool live = e < n_envs;                              // (the last wave's spare lanes stay for the staged copy-out)
+    const int el = live ? e : n_envs - 1;
+    const Task t = load_task(T, st.task_id[el]);
+    Agent a = load_agent(st, n_envs, el);
+    const int ww = (2 * vg + 1) * (2 * vg + 1);
+    const int run = min(MZ_ROLL_BLOCK, n_envs - e0) * ww;      // floats this wave owns in a slice of obs
+    const size_t slice = (size_t)n_envs * ww;
+    float *out = obs;
+    for (int s = 0; s < n_steps; ++s) {
+        const size_t rec = (size_t)s * n_envs + el;
+        if (live) {
+            const int act = actions[rec] & 3;
+            // DISCRETE_ACTIONS maze_env.py:14 = [(-1,0),(1,0),(0,-1),(0,1)]; maze_2d.py:24-29
+            const int ti = a.gx + (act == 0 ? -1 : (act == 1 ? 1 : 0));
+            const int tj = a.gy + (act == 2 ? -1 : (act == 3 ? 1 : 0));
+            const int wi = ti < 0 ? ti + t.n : ti, wj = tj < 0 ? tj + t.n : tj;   // python negative index
+            if (wi < t.n && wj < t.n && t.walls[wi * t.n + wj] < 1) { a.gx = ti; a.gy = tj; }
+            double r;
+            const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
+            if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);
+            if (reward) reward[rec] = (float)r;
+            if (reward64) reward64[rec] = r;
+            done[rec] = (uint8_t)d;
+            if (d && auto_reset) {
+                reset_agent(t, task_type, a);
+                if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
+            }
+        }
+        if (!rollout_records(s, n_steps, obs_every)) continue;               // (uniform: every lane is at step s)
+        if (STAGE) {
+            if (live) observe_2d(t, st, e, task_type, vg, a, [&](int i, float v) { tile[lane * ww + i] = v; });
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            float *dst = out + (size_t)e0 * ww;
+            for (int i = lane; i < run; i += MZ_ROLL_BLOCK) dst[i] = tile[i];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");           // the next recorded step overwrites the tile
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        } else if (live) {
+            float *o = out + (size_t)e * ww;
+            observe_2d(t, st, e, task_type, vg, a, [&](int i, float v) { o[i] = v; });
+        }
+        out += slice;
+    }
+    if (live) store_agent(st, n_envs, e, a);
+}
+
+// The part of a 3-D maze step that is not the picture — MazeCoreDiscrete3D.turn / move (maze_discrete_3d.py:51-72) or
+// MazeCoreContinuous3D.do_action (maze_continuous_3d.py:47-56 -> dynamics.py:59-92), then evaluation_rule (maze_base.py:65-95)
+// and the auto-reset — for the steps s0 .. s1-1 of a rollout, one lane per env like maze_cont_move_kernel, the agent in
+// registers for the stretch. The same device functions in the same order as phase 0 of maze3d_step_kernel; there the 256
+// threads of an env share its cells, here the lane sweeps them alone (the sweeps touch disjoint cells, so the order among
+// cells does not matter). The SURVIVAL arrays are read through the strides of mg_maze_state: [N][n*n] for the 3-D envs, i.e.
+// lane e at e * n*n + c — one line per lane per access, a handful of accesses per step with the food-cell list.
+__global__ __launch_bounds__(MZ_BLOCK) void maze3d_advance_kernel(mg_maze_tasks T, mg_maze_state st, double col_dist,
+                                                                  int task_type, int max_steps, int continuous,
+                                                                  int auto_reset, int n_envs, int s0, int s1,
+                                                                  const void *actions, float *reward, double *reward64,
+                                                                  uint8_t *done) {
+    const int e = blockIdx.x * MZ_BLOCK + threadIdx.x;
+    if (e >= n_envs) return;
+    const Task t = load_task(T, st.task_id[e]);
+    Agent a = load_agent(st, n_envs, e);
+    for (int s = s0; s < s1; ++s) {
+        const size_t rec = (size_t)s * n_envs + e;
+        if (continuous) {
+            const float *ac = static_cast<const float *>(actions) + 2 * rec;
+            transition_continuous(t, col_dist, ac[0], ac[1], a);
+        } else {
+            transition_discrete(t, static_cast<const int32_t *>(actions)[rec] & 3, a);
+        }
+        double r;
+        const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
+        if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);      // :83-88
+        if (reward) reward[rec] = (float)r;
+        if (reward64) reward64[rec] = r;
+        done[rec] = (uint8_t)d;
+        if (d && auto_reset) {
+            if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
+            reset_agent(t, task_type, a);
+        }
+    }
+    store_agent(st, n_envs, e, a);
+}
+
 __global__ __launch_bounds__(MZ_BLOCK) void maze_reset_kernel(mg_maze_tasks T, mg_maze_state st, int task_type,
                                                               int n_envs, const uint8_t *mask) {
     // one wave per env so the SURVIVAL cell arrays are written coalesced
@@ -1237,10 +1379,12 @@ extern "C" int mg_maze_check_uniform_cell_size(const mg_maze_tasks *T, double un
     return MG_OK;
 }
 
-extern "C" int mg_maze3d_step(const mg_maze_tasks *T, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
-                              int32_t continuous, int32_t auto_reset, int32_t n, const mg_maze_state *st,
-                              const void *action, void *obs, float *reward, double *reward64, uint8_t *done,
-                              void *stream) {
+// mg_maze3d_step, and with check_only its host half alone: every argument check, the launch plan and the LDS opt-in, no launch
+// (mg_maze3d_rollout refuses a bad call before its first kernel is enqueued).
+static int maze3d_step_impl(const mg_maze_tasks *T, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                            int32_t continuous, int32_t auto_reset, int32_t n, const mg_maze_state *st,
+                            const void *action, void *obs, float *reward, double *reward64, uint8_t *done,
+                            void *stream, bool check_only) {
     MG_REQUIRE_PTR(T);
     MG_REQUIRE_PTR(view);
     MG_REQUIRE_PTR(st);
@@ -1374,6 +1518,7 @@ extern "C" int mg_maze3d_step(const mg_maze_tasks *T, const mg_maze_view *view, 
             granted[slot].store(lds, std::memory_order_relaxed);
         }
     }
+    if (check_only) return MG_OK;
     int pre_moved = 0;
     if (continuous && action != nullptr) {
         hipLaunchKernelGGL(maze_cont_move_kernel, dim3((n + MZ_BLOCK - 1) / MZ_BLOCK), dim3(MZ_BLOCK), 0,
@@ -1414,4 +1559,75 @@ extern "C" int mg_maze3d_step(const mg_maze_tasks *T, const mg_maze_view *view, 
 #undef MG_MAZE3D_PICK
 #undef MG_MAZE3D_LAUNCH
     return mg::check_launch("maze3d_step_kernel");
+}
+
+extern "C" int mg_maze3d_step(const mg_maze_tasks *T, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                              int32_t continuous, int32_t auto_reset, int32_t n, const mg_maze_state *st,
+                              const void *action, void *obs, float *reward, double *reward64, uint8_t *done,
+                              void *stream) {
+    return maze3d_step_impl(T, view, task_type, max_steps, continuous, auto_reset, n, st, action, obs, reward, reward64, done,
+                            stream, false);
+}
+
+extern "C" int mg_maze2d_rollout(const mg_maze_tasks *T, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                                 int32_t auto_reset, int32_t n, const mg_maze_state *st, int32_t n_steps, int32_t obs_every,
+                                 const int32_t *actions, float *obs, float *reward, double *reward64, uint8_t *done,
+                                 void *stream) {
+    MG_REQUIRE_PTR(T);
+    MG_REQUIRE_PTR(st);
+    MG_REQUIRE_PTR(actions);
+    MG_REQUIRE_PTR(obs);
+    MG_REQUIRE_PTR(done);
+    if (n <= 0 || view_grid < 0) return mg::set_error(MG_ERR_BAD_SIZE, "n_envs=%d view_grid=%d", n, view_grid);
+    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze2d_rollout: n_steps=%d (at least 1)", n_steps);
+    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze2d_rollout: obs_every=%d (0 = the last step only, k >= 1 = every k-th)", obs_every);
+    if (int rc = check_tasks(T, task_type)) return rc;
+    if (int rc = check_mstate(st, task_type)) return rc;
+    if (int rc = check_slots(T, st, task_type)) return rc;
+    mg::DeviceGuard guard(mg::device_of(st->grid));
+    // the wave's 64 windows staged in LDS, up to the 64 KiB a kernel gets without opting in (view_grid <= 7); larger windows
+    // keep the per-lane store.
+    // MG_MAZE2D_ROLLOUT_DIRECT=1 (read once) forces the per-lane store, for A/B timing; same values either way.
+    static const bool force_direct = getenv("MG_MAZE2D_ROLLOUT_DIRECT") != nullptr;
+    const long w = 2L * view_grid + 1;
+    const size_t lds = sizeof(float) * (size_t)MZ_ROLL_BLOCK * (size_t)(w * w);
+    const dim3 grid((unsigned)((n + MZ_ROLL_BLOCK - 1) / MZ_ROLL_BLOCK)), block(MZ_ROLL_BLOCK);
+    if (lds <= 64 * 1024 && !force_direct)
+        hipLaunchKernelGGL(maze2d_rollout_kernel<true>, grid, block, lds, (hipStream_t)stream, *T, *st, task_type, max_steps,
+                           view_grid, auto_reset, n, n_steps, obs_every, actions, obs, reward, reward64, done);
+    else
+        hipLaunchKernelGGL(maze2d_rollout_kernel<false>, grid, block, 0, (hipStream_t)stream, *T, *st, task_type, max_steps,
+                           view_grid, auto_reset, n, n_steps, obs_every, actions, obs, reward, reward64, done);
+    return mg::check_launch("maze2d_rollout_kernel");
+}
+
+extern "C" int mg_maze3d_rollout(const mg_maze_tasks *T, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                                 int32_t continuous, int32_t auto_reset, int32_t n, const mg_maze_state *st, int32_t n_steps,
+                                 int32_t obs_every, const void *actions, void *obs, float *reward, double *reward64,
+                                 uint8_t *done, void *stream) {
+    MG_REQUIRE_PTR(actions);
+    MG_REQUIRE_PTR(done);
+    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze3d_rollout: n_steps=%d (at least 1)", n_steps);
+    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze3d_rollout: obs_every=%d (0 = the last step only, k >= 1 = every k-th)", obs_every);
+    // everything mg_maze3d_step refuses, before the first launch
+    if (int rc = maze3d_step_impl(T, view, task_type, max_steps, continuous, auto_reset, n, st, nullptr, obs, nullptr, nullptr,
+                                  nullptr, stream, true)) return rc;
+    const size_t frame = (size_t)n * view->res_h * view->res_v * 3 * (view->obs_format == 1 ? 1 : sizeof(int32_t));
+    unsigned char *slice = static_cast<unsigned char *>(obs);
+    mg::DeviceGuard guard(mg::device_of(st->grid));
+    for (int s0 = 0; s0 < n_steps;) {
+        int s1 = s0;
+        while (!rollout_records(s1, n_steps, obs_every)) ++s1;      // the stretch ends with the next recorded step
+        ++s1;
+        hipLaunchKernelGGL(maze3d_advance_kernel, dim3((unsigned)((n + MZ_BLOCK - 1) / MZ_BLOCK)), dim3(MZ_BLOCK), 0,
+                           (hipStream_t)stream, *T, *st, view->collision_dist, task_type, max_steps, continuous, auto_reset, n,
+                           s0, s1, actions, reward, reward64, done);
+        if (int rc = mg::check_launch("maze3d_advance_kernel")) return rc;
+        // the frame of the state the stretch left: mg_maze3d_step's observe-only form (action == NULL), renderer untouched
+        if (int rc = maze3d_step_impl(T, view, task_type, max_steps, continuous, auto_reset, n, st, nullptr, slice, nullptr,
+                                      nullptr, nullptr, stream, false)) return rc;
+        slice += frame;
+        s0 = s1;
+    }
+    return MG_OK;
 }

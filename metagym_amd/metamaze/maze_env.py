@@ -74,6 +74,18 @@ def food_lists(food_rewards, food_interval, by_slot):
     return out
 
 
+def rollout_obs_steps(n_steps, obs_every):
+    """The steps (0-based, ascending) of a `rollout` of `n_steps` steps that leave an observation: `obs_every` 0 = the last
+    step only; k >= 1 = every step t with (t + 1) % k == 0, and always the last one (never twice). The kernels apply the same
+    rule (csrc/maze.hip rollout_records)."""
+    n_steps, obs_every = int(n_steps), int(obs_every)
+    if n_steps < 1:
+        raise ValueError("a rollout needs at least one step (got %d)" % n_steps)
+    if obs_every < 0:
+        raise ValueError("obs_every must be 0 (the last step only) or k >= 1 (every k-th step), got %d" % obs_every)
+    return [t for t in range(n_steps) if t == n_steps - 1 or (obs_every > 0 and (t + 1) % obs_every == 0)]
+
+
 class _MazeBatch(object):
     """State, task table and launch plumbing shared by the three envs."""
 
@@ -281,6 +293,42 @@ class _MazeBatch(object):
     def reward64(self):
         return self._reward64
 
+    def rollout(self, actions, obs_every=0):
+        """`for t in range(T): step(actions[t])` without the host in the loop: same end state, rewards and dones bit for bit, for
+        both task types and both settings of `auto_reset` (an env without it that is stepped past `done` goes on stepping, as
+        in `step`). actions: [T, num_envs] ints (2-D, discrete 3-D) or float32 [T, num_envs, 2] (continuous 3-D), T >= 1.
+        `obs_every` selects the steps that leave an observation (`rollout_obs_steps`): 0 = the last one only, k >= 1 = every
+        k-th and the last. Returns (obs, reward, done, info): reward float32 [T, N] and done bool [T, N], fresh tensors per call
+        (`self.rollout_reward64`: the exact float64 [T, N]); obs is the persistent [N, ...] buffer `step` returns when
+        obs_every == 0, else a fresh [K, N, ...] tensor with one slice per recorded step (with auto_reset, the first
+        observation of the next episode where that step ended one); info["steps"] the counters after the last step,
+        info["obs_steps"] the K recorded step indices. The 2-D env runs ONE launch, the 3-D envs two per recorded step (the
+        renderer only runs for those). Nothing synchronises: the call can be captured in a hipGraph like `step`. The
+        persistent reward / done buffers of `step` are not written."""
+        if self.need_set_task:
+            raise Exception("Must call \"set_task\" before rollout")
+        self._check_step()
+        a = self._rollout_actions(actions)
+        T = int(a.shape[0])
+        idx = rollout_obs_steps(T, obs_every)
+        N, dev = self.num_envs, self.device
+        reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+        reward64 = torch.empty(T, N, dtype=torch.float64, device=dev)
+        done = torch.empty(T, N, dtype=torch.bool, device=dev)
+        obs = self._obs if int(obs_every) == 0 else torch.empty((len(idx),) + tuple(self._obs.shape), dtype=self._obs.dtype,
+                                                                 device=dev)
+        self._launch_rollout(a, T, int(obs_every), obs, reward, reward64, done)
+        self.rollout_reward64 = reward64
+        return obs, reward, done, {"steps": self.steps, "obs_steps": idx}
+
+    def _rollout_actions(self, actions):
+        """[T, N] int32 on the device; a wrong shape is a ValueError."""
+        a = torch.as_tensor(actions, device=self.device)
+        if a.dim() != 2 or a.shape[0] < 1 or a.shape[1] != self.num_envs:
+            raise ValueError("rollout actions must be [T, num_envs = %d] ints in 0..3 with T >= 1, got %s"
+                             % (self.num_envs, tuple(a.shape)))
+        return a.to(torch.int32).contiguous()
+
     def render(self, mode="human"):
         raise NotImplementedError("rendering is out of scope for the batched engine")
 
@@ -318,6 +366,13 @@ class MetaMaze2D(_MazeBatch):
         assert a.shape == (self.num_envs,), "action must be [num_envs] ints in 0..3"
         self._launch(a)
         return self._obs, self._reward, self._done, {"steps": self.steps}
+
+    def _launch_rollout(self, a, T, obs_every, obs, reward, reward64, done):
+        rc = self._lib.mg_maze2d_rollout(self._tasks_c, self._tt, self.max_steps, self.view_grid, int(self.auto_reset),
+                                         self.num_envs, self._state_c, T, obs_every, _lib.ptr(a), _lib.ptr(obs),
+                                         _lib.ptr(reward), _lib.ptr(reward64), _lib.ptr(done),
+                                         _lib.current_stream(self.device))
+        _lib.check(rc, "mg_maze2d_rollout")
 
 
 class _Maze3D(_MazeBatch):
@@ -391,6 +446,17 @@ class _Maze3D(_MazeBatch):
                                       _lib.ptr(self._done), _lib.current_stream(self.device))
         _lib.check(rc, "mg_maze3d_step")
 
+    _CONTINUOUS = False
+
+    def _launch_rollout(self, a, T, obs_every, obs, reward, reward64, done):
+        if self._tex_version != MAZE_TASK_MANAGER.version:
+            self._build_view()
+        rc = self._lib.mg_maze3d_rollout(self._tasks_c, self._view_c, self._tt, self.max_steps, int(self._CONTINUOUS),
+                                         int(self.auto_reset), self.num_envs, self._state_c, T, obs_every, _lib.ptr(a),
+                                         _lib.ptr(obs), _lib.ptr(reward), _lib.ptr(reward64), _lib.ptr(done),
+                                         _lib.current_stream(self.device))
+        _lib.check(rc, "mg_maze3d_rollout")
+
 
 class MetaMazeDiscrete3D(_Maze3D):
     """maze_env.py:16-83. action int in {0..3}: turn left / right, step back / forward."""
@@ -419,6 +485,15 @@ class MetaMazeContinuous3D(_Maze3D):
                  max_steps=5000, task_type="SURVIVAL", auto_reset=False, obs_dtype=torch.int32):
         super().__init__(num_envs, device, resolution, max_steps, task_type, auto_reset, obs_dtype=obs_dtype)
         self.action_space = Box(low=np.array([-1.0, -1.0]), high=np.array([1.0, 1.0]), dtype=np.float32)
+
+    _CONTINUOUS = True
+
+    def _rollout_actions(self, actions):
+        a = torch.as_tensor(actions, dtype=torch.float32, device=self.device)
+        if a.dim() != 3 or a.shape[0] < 1 or tuple(a.shape[1:]) != (self.num_envs, 2):
+            raise ValueError("rollout actions must be float32 [T, num_envs = %d, 2] with T >= 1, got %s"
+                             % (self.num_envs, tuple(a.shape)))
+        return a.contiguous()
 
     def _observe(self):
         self._launch(None, True)
