@@ -373,17 +373,30 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) tw[c] = s.w[c] + k.half_dt * alpha[c];
-    // skew(tw) rounded to f32 (:193-199); R += dt * (R @ S) with the sgemm FMA association, the
-    // structural zero of each S column folded away (0*x contributes +-0)
+    // skew(tw) rounded to f32 (:193-199); R += dt * (R @ S) with the sgemm FMA association. The diagonal of S is a
+    // structural zero, but its three terms per row are real instructions: without fast-math the compiler keeps
+    // x * 0.0f and fmaf(x, 0.0f, y) (signed zeros, inf * 0 = NaN). FAST writes the rows without them, 3 v_mul_f32
+    // and 6 v_fma_f32 fewer per sub-step, and the new R is bit-identical wherever the step's result is used:
+    //   Finite row (r0, r1, r2). In column j the dropped term is rj * 0 = +-0 with the sign of rj, and column j's sum
+    //   rs_j is added to that same rj. Adding +-0 to the partner sum changes nothing unless that sum is an exact
+    //   zero, and then only the sign of rs_j can differ. prec32 * (+-0) = +-0, and rj + (+-0) = rj for rj != 0 and
+    //   +0 for rj = +0, whichever sign. For rj = -0 the dropped term is -0, and x + (-0) = x for every x, so rs_j
+    //   itself is unchanged. A non-finite s entry gives the same inf / NaN with or without the +-0.
+    //   Non-finite row. Any non-finite entry of R makes det non-finite in either formulation (every entry of R is a
+    //   factor of a term of det; a non-finite factor makes the term inf or NaN, and so the sum), and a finite entry
+    //   becomes non-finite only through rs, which then is non-finite in both. all_in_range() clears `ok` and the
+    //   wave redoes the whole step with FAST = false, which keeps the full products, as do STEP_STOCK and
+    //   STEP_GENERIC. This covers the loaded, unchecked R too: sub-step 1 takes det on the updated R, and a
+    //   non-finite loaded entry leaves its updated entry non-finite (r + x, r non-finite) in both forms.
     const float s01 = (float)(-tw[2]), s02 = (float)(tw[1]);
     const float s10 = (float)(tw[2]), s12 = (float)(-tw[0]);
     const float s20 = (float)(-tw[1]), s21 = (float)(tw[0]);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         const float r0 = s.R[3 * r], r1 = s.R[3 * r + 1], r2 = s.R[3 * r + 2];
-        const float rs0 = fmaf(r2, s20, fmaf(r1, s10, r0 * 0.0f));
-        const float rs1 = fmaf(r2, s21, fmaf(r1, 0.0f, r0 * s01));
-        const float rs2 = fmaf(r2, 0.0f, fmaf(r1, s12, r0 * s02));
+        const float rs0 = FAST ? fmaf(r2, s20, r1 * s10) : fmaf(r2, s20, fmaf(r1, s10, r0 * 0.0f));
+        const float rs1 = FAST ? fmaf(r2, s21, r0 * s01) : fmaf(r2, s21, fmaf(r1, 0.0f, r0 * s01));
+        const float rs2 = FAST ? fmaf(r1, s12, r0 * s02) : fmaf(r2, 0.0f, fmaf(r1, s12, r0 * s02));
         s.R[3 * r] = r0 + k.prec32 * rs0;
         s.R[3 * r + 1] = r1 + k.prec32 * rs1;
         s.R[3 * r + 2] = r2 + k.prec32 * rs2;
@@ -446,6 +459,18 @@ __device__ __forceinline__ bool collision(const QuadK &k, const double *op, cons
             for (long x = x0; x < x1; ++x) any |= (k.map[y * k.map_w + x] != 0);
     }
     return (mn[2] < any) || (mx[2] < any);  // heights compared with the *bool* np.any(...)
+}
+// collision() for k.map == nullptr, established on the host (FLAT): any is 0 and the x and y extents are never read,
+// so the test is (long)floor(lo_z) < 0 || (long)ceil(hi_z) < 0 with lo_z, hi_z as selected above. It equals lo_z < 0:
+//   lo_z, hi_z not NaN: lo_z <= hi_z, floor(lo_z) <= ceil(hi_z), and the conversion is monotone (it saturates: the
+//     high word is v_cvt_i32_f64 of floor(x * 2^-32)), so the first test decides. floor(x) < 0 exactly when x < 0
+//     (-0.0 -> -0 -> 0, a tiny negative -> -1, -inf and every finite x below -2^63 -> a negative long).
+//   new z NaN: both selects return the new z, and (long)NaN is 0 here (v_cvt_i32_f64 and v_cvt_u32_f64 of NaN are
+//     0): no hit. NaN < 0 is false as well.
+//   old z NaN (new z not): both selects return the new z, so lo_z = hi_z = new z: the first case.
+__device__ __forceinline__ bool collision_flat(double op_z, double np_z) {
+    const double lo = op_z < np_z ? op_z : np_z;
+    return lo < 0.0;
 }
 
 // ---- pre-reset, all-float32 sub-step: define_velocity_control_task, quadrotorsim.py:306-319 -------
@@ -761,12 +786,15 @@ __device__ __forceinline__ KArgsC *kernargs_fresh() {
 //                      every wave would cost more than the branch it saves.
 //                      Its sub-steps take sqrt and 1/det without the library's range steps (update_derived<true>);
 //                      a wave with an argument out of range redoes the step with the library's (see the kernel).
-// Two options, also resolved on the host:
+// Four options, also resolved on the host:
 //   XF   (both stock forms) the stock X frame of propellers (config_is_xframe, substep<>); any other SIMPLE layout
 //        keeps XF = false.
 //   BUF  (STEP_STOCK_SHADOW) state, action and outputs addressed through buffer resources (ld_soa / st_soa) when
 //        every array of the launch spans less than 2^31 bytes. Not in STEP_STOCK: there the step loop keeps the resources
 //        live across the sub-steps and the scalar file spills (14 / 36 SGPR spills with / without XF).
+//   FLAT (both stock forms) no collision map (k.map == nullptr): the collision test is the z test of collision_flat().
+//        A configuration with a map keeps collision().
+//   HOVER (STEP_STOCK_SHADOW) the hovering task, so the epilogue holds no test of k.task.
 enum StepForm { STEP_GENERIC = 0, STEP_STOCK = 1, STEP_STOCK_SHADOW = 2 };
 
 // Phase timeline (diagnostic builds only, -DMG_QUAD_PHASE_STAMPS; scripts/quad_phase_timeline.py reads it): lane 0 of
@@ -798,7 +826,7 @@ constexpr int STOCK_TIMES = 10;
 #define MG_QUAD_SUBSTEP_UNROLL 9   // of the first nine stock sub-steps (the tenth is peeled): 9 = straight-line, 1 = rolled
 #endif
 
-template <bool SIMPLE, int FORM, bool XF = false, bool BUF = false>
+template <bool SIMPLE, int FORM, bool XF = false, bool BUF = false, bool FLAT = false, bool HOVER = false>
 __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadrotor_state st, StepIO io,
                                                                int n, int n_steps_arg) {
     constexpr bool STOCK = FORM != STEP_GENERIC;
@@ -806,6 +834,8 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
     static_assert(!STOCK || SIMPLE, "the stock forms are SIMPLE");
     static_assert(STOCK || !XF, "XF is an option of the stock forms");
     static_assert(SHADOW || !BUF, "BUF is an option of STEP_STOCK_SHADOW");
+    static_assert(STOCK || !FLAT, "FLAT is an option of the stock forms");
+    static_assert(SHADOW || !HOVER, "HOVER is an option of STEP_STOCK_SHADOW");
     constexpr bool FAST = SHADOW && MG_QUAD_FASTPATH;   // in-range sqrt / 1/det (update_derived), whole-step fallback below
     const int n_steps = SHADOW ? 1 : n_steps_arg;
     __shared__ float tiles[WAVES_PER_BLOCK][mg::WAVE * (OBS_DIM + 1)];
@@ -933,7 +963,10 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         const KArgsC *kae = kernargs_fresh();
         const QuadK &ke = *(const QuadK *)&kae->k;
         const StepIO &ioe = *(const StepIO *)&kae->io;
-        const bool vel_task = ke.task == MG_QUADROTOR_TASK_VELOCITY_CONTROL;
+        // STEP_STOCK_SHADOW: never the velocity task (make_plan: stock needs simple, and simple excludes it), so its
+        // arm, tn and the three target entries of the observation are not compiled. STEP_STOCK keeps the test.
+        const bool vel_task = !SHADOW && ke.task == MG_QUADROTOR_TASK_VELOCITY_CONTROL;
+        const bool hover_task = HOVER || ke.task == MG_QUADROTOR_TASK_HOVERING_CONTROL;
         // _update_state env.py:262-273: the observation's target entries come from min(ct, nt-1) with ct
         // already incremented and not yet cleared by the episode end
         const int tn_step = ct < ke.nt - 1 ? ct : ke.nt - 1;
@@ -954,12 +987,12 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         } else if (fail == 0) {
             const double new_pos[3] = {(double)s.p[0] + ke.xoff, (double)s.p[1] + ke.yoff,
                                        (double)(s.p[2] + ke.zoff32)};
-            const bool hit = collision(ke, old_pos, new_pos);                // env.py:145
+            const bool hit = FLAT ? collision_flat(old_pos[2], new_pos[2]) : collision(ke, old_pos, new_pos);   // env.py:145
             // _get_reward env.py:211-246
             const float energy = ke.dt32 * s.power;
             double r = (ke.healthy32 < energy) ? -ke.healthy : -(double)energy;   // -min(energy, healthy)
             double task_reward = hit ? 0.0 : ke.healthy;
-            if (ke.task == MG_QUADROTOR_TASK_HOVERING_CONTROL) {
+            if (hover_task) {
                 task_reward -= 1.0 * s.nv + 1.0 * s.nw;
                 const float z_move = fabsf(0.0f - s.p[2]);   // pos_0 is the reset position = 0 (env.py:123)
                 if (z_move < 0.5f) task_reward += 10;
@@ -968,7 +1001,7 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
                     task_reward += (o > -20.0f) ? (double)o : -20.0;
                 }
             }
-            if (ke.task == MG_QUADROTOR_TASK_HOVERING_CONTROL || ke.healthy32 < energy)
+            if (hover_task || ke.healthy32 < energy)
                 reward = r + task_reward;     // np.float64 task_reward, or python floats on both sides
             else                              // no_collision: np.float32 + weak python float -> f32 add (env.py:220-221)
                 reward = (double)((float)r + (float)task_reward);
@@ -1252,6 +1285,13 @@ int make_plan(Plan *p, const mg_quadrotor_config *cfg, const mg_quadrotor_autore
     return MG_OK;
 }
 
+typedef decltype(&quadrotor_step_kernel<false, STEP_GENERIC>) StepKernel;
+// the STEP_STOCK_SHADOW kernel for the four host-resolved options (see StepForm)
+template <bool... B>
+StepKernel pick_shadow() { return quadrotor_step_kernel<true, STEP_STOCK_SHADOW, B...>; }
+template <bool... B, typename... Rest>
+StepKernel pick_shadow(bool b, Rest... rest) { return b ? pick_shadow<B..., true>(rest...) : pick_shadow<B..., false>(rest...); }
+
 int launch_plan(const Plan *p, int32_t n_steps, const float *action, float *obs, float *reward, double *reward64,
                 uint8_t *done, uint8_t *failed, void *stream) {
     MG_REQUIRE_PTR(action);
@@ -1264,13 +1304,14 @@ int launch_plan(const Plan *p, int32_t n_steps, const float *action, float *obs,
     const int waves = (n + mg::WAVE - 1) / mg::WAVE;
     // BUF: 32-bit buffer offsets; the [n][16] f32 observation is the largest array a one-step launch touches
     const bool buf = (uint64_t)n * (OBS_DIM * sizeof(float)) < (1ull << 31);
-    constexpr int SH = STEP_STOCK_SHADOW;
-    decltype(&quadrotor_step_kernel<false, STEP_GENERIC>) kern;
+    // FLAT / HOVER: no collision map / the hovering task, both properties of the folded configuration
+    const bool flat = p->k.map == nullptr, hover = p->k.task == MG_QUADROTOR_TASK_HOVERING_CONTROL;
+    StepKernel kern;
     if (p->stock && n_steps == 1 && waves <= p->simds) {
-        if (p->xframe) kern = buf ? quadrotor_step_kernel<true, SH, true, true> : quadrotor_step_kernel<true, SH, true, false>;
-        else kern = buf ? quadrotor_step_kernel<true, SH, false, true> : quadrotor_step_kernel<true, SH, false, false>;
+        kern = pick_shadow(p->xframe != 0, buf, flat, hover);
     } else if (p->stock) {
-        kern = p->xframe ? quadrotor_step_kernel<true, STEP_STOCK, true> : quadrotor_step_kernel<true, STEP_STOCK>;
+        if (p->xframe) kern = flat ? quadrotor_step_kernel<true, STEP_STOCK, true, false, true> : quadrotor_step_kernel<true, STEP_STOCK, true>;
+        else kern = flat ? quadrotor_step_kernel<true, STEP_STOCK, false, false, true> : quadrotor_step_kernel<true, STEP_STOCK>;
     } else if (p->simple) {
         kern = quadrotor_step_kernel<true, STEP_GENERIC>;
     } else {
