@@ -197,6 +197,25 @@ int mg_quadrotor_plan_init(mg_quadrotor_plan *plan, const mg_quadrotor_config *c
 int mg_quadrotor_plan_step(const mg_quadrotor_plan *plan, int32_t n_steps, const float *action, float *obs,
                            float *reward, double *reward64, uint8_t *done, uint8_t *failed, void *stream);
 
+/* What a plan folded for the one-wave stock step (a one-step launch of at most one wave per SIMD), for tests and
+ * diagnostics. That form holds no failure test in its sub-steps: a lane whose |v|^2 or |w|^2 has a high word (bits
+ * 63..32 of the double) of edge_v / edge_w or more, or whose position has a component of magnitude pos_safe32 or more
+ * after any sub-step, sends its wave through the full tests instead. one_wave_form is the form such a launch takes:
+ * 0 generic, 1 the stock straight-line form (stock configuration whose thresholds cannot be folded: negative, zero,
+ * NaN, a velocity or body-rate threshold below sqrt(2), a range that is not finite or below 2^-50), 2 the one-wave
+ * form; the folded fields are zero unless it is 2. Additive entry point; MG_ABI_VERSION is unchanged. */
+typedef struct mg_quadrotor_fold {
+    int32_t one_wave_form;
+    uint32_t span;               /* width of the high-word windows: a lane passes when high word - base < span */
+    uint32_t base_v, base_w;     /* edge - span */
+    uint32_t edge_v, edge_w;     /* exclusive upper edges of the |v|^2 and |w|^2 windows (high words) */
+    float pos_safe32;
+    float fail_range_sq32;       /* largest float32 sum of squares that passes the range test */
+    double fail_velocity, fail_w;
+} mg_quadrotor_fold;
+
+int mg_quadrotor_plan_fold(const mg_quadrotor_plan *plan, mg_quadrotor_fold *out);
+
 /* ========================================================================================
  * MetaMaze — replaces metagym/metamaze/envs/{maze_base,maze_2d,maze_discrete_3d,
  *            maze_continuous_3d,dynamics,ray_caster_utils}.py for N envs

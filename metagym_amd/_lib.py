@@ -53,6 +53,13 @@ class QuadrotorPlan(C.Structure):
     _fields_ = [("opaque", C.c_uint64 * 128)]
 
 
+class QuadrotorFold(C.Structure):
+    """mg_quadrotor_fold: what a plan folded for the one-wave stock step (mg_quadrotor_plan_fold)"""
+    _fields_ = [("one_wave_form", C.c_int32), ("span", C.c_uint32), ("base_v", C.c_uint32), ("base_w", C.c_uint32),
+                ("edge_v", C.c_uint32), ("edge_w", C.c_uint32), ("pos_safe32", C.c_float),
+                ("fail_range_sq32", C.c_float), ("fail_velocity", C.c_double), ("fail_w", C.c_double)]
+
+
 class MazeTasks(C.Structure):
     """mg_maze_tasks (device pointers)"""
     _fields_ = [("n", C.c_int32), ("n_tasks", C.c_int32), ("start", C.c_void_p), ("goal", C.c_void_p),
@@ -276,6 +283,7 @@ SIGNATURES = {
     "mg_quadrotor_plan_init": (C.c_int, [C.POINTER(QuadrotorPlan), C.POINTER(QuadrotorConfig),
                                          C.POINTER(QuadrotorAutoReset), C.c_int32, C.POINTER(QuadrotorState)]),
     "mg_quadrotor_plan_step": (C.c_int, [C.POINTER(QuadrotorPlan), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "mg_quadrotor_plan_fold": (C.c_int, [C.POINTER(QuadrotorPlan), C.POINTER(QuadrotorFold)]),
     "mg_quadrotor_rollout": (C.c_int, [C.POINTER(QuadrotorConfig), C.c_int32, C.c_int32,
                                        C.POINTER(QuadrotorState), _P, _P, _P, _P, _P, _P, _P]),
     "mg_maze_view_tables": (C.c_int, [C.c_int32, C.c_double, C.c_double, _P, _P]),

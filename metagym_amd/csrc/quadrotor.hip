@@ -21,6 +21,7 @@
 // -ffp-contract=off so no a*b+c is fused — NumPy never fuses — which makes this kernel bit-identical
 // to the CPU oracle for everything except atan2f (OCML vs glibc, <= 2 ulp).
 #include <cstdlib>
+#include <cstring>
 
 #include "mg_common.h"
 #include "mg_philox.h"
@@ -53,12 +54,17 @@ struct QuadK {
     // fused auto-reset (not in the reference: replaces the user's `if done: env.reset()` round trip)
     int auto_reset;
     float init_v_base[3], init_w_base[3];   // cfg['init_velocity'] / ['init_angular_velocity'] x,y,z (f32 arrays)
+    // STEP_STOCK_SHADOW's velocity and body-rate tests folded into its range window (fold_lean): all_in_range's bases for
+    // |v|^2 and |w|^2. Zero in a plan that cannot fold. The two words sit where the struct had padding: the layout of the
+    // kernel arguments is the same for every form, and the other forms' code depends on it (see KArgs).
+    uint32_t lean_base_v;
     double init_v_noisy, init_w_noisy;      // ... ['noisy']
     uint64_t seed, env_id_base;
     const int32_t *map;
     int map_h, map_w;
     const float *vtargets;   // velocity_control target trajectory [nt][3]
     int obs_dim;             // 16, or 19 for velocity_control
+    uint32_t lean_base_w;    // see lean_base_v
 };
 
 struct Lane {       // one environment, in registers
@@ -120,7 +126,7 @@ __device__ __forceinline__ double sumsq3(const double *x) {
 }
 __device__ __forceinline__ double norm3(const double *x) { return sqrt(sumsq3(x)); }
 
-// ---- in-range sqrt and reciprocal (the sub-steps of STEP_STOCK_SHADOW, update_derived<true>) --------------------
+// ---- in-range sqrt and reciprocal (the sub-steps of STEP_STOCK_SHADOW, update_derived_fast) --------------------
 // For f64, the compiler expands sqrt(x) and 1.0 / d into a Newton sequence wrapped in range steps. The two functions
 // below are those sequences without the range steps. They are used only where the range steps are the identity,
 // which is what all_in_range tests.
@@ -138,17 +144,25 @@ __device__ __forceinline__ double norm3(const double *x) { return sqrt(sumsq3(x)
 //     the scaled numerator is 1.0 and the product 1.0 * y is y (exact), V_DIV_FMAS_F64 with VCC = 0 is the plain
 //     fma, and V_DIV_FIXUP_F64 (d finite, normal and non-zero, numerator 1.0, exponent difference within +-500)
 //     returns the quotient with the sign of d, which it already has.
-// The test is one u32 range check on the high words, for all three arguments of an update at once: h - base < SPAN with
-// SPAN = 1000 exponents. For x = |v|^2 or |w|^2 (never negative; a NaN may carry the sign bit) the base is the high word of
-// 2^-767 (its low word is 0), so the window is exactly x = +0 (mapped to 0) or 2^-767 <= x < 2^233; a set sign bit or an
-// exponent of 2047 (inf, NaN) lands above it. For d the sign is masked off and the window is 2^-500 <= |d| < 2^500.
-// With R in f32, a non-zero det is a sum of multiples of 2^-447 below 2^387, so only det = 0, inf or NaN leave it.
+// The test is one u32 range check on the high words, for all three arguments of an update at once: h - base < LEAN_SPAN,
+// one span of 768 exponents for all three, so that one max and one compare serve. For x = |v|^2 or |w|^2 (never negative; a
+// NaN may carry the sign bit) the window is x = +0 (mapped to 0) or B <= x < Y, where Y is the double whose high word is the
+// plan's edge (low word 0) and B = Y * 2^-768; a set sign bit or an exponent of 2047 (inf, NaN) lands above it. The edge is
+// where the failure tests come in (fold_lean): Y <= min(threshold^2 * (1 - 2^-19), 2^233) with sqrt(Y) <= threshold checked
+// on the host, so a lane inside the window cannot fail the velocity or the body-rate test at this update: x < Y, sqrt is
+// monotone, and sqrt_newton is the library's value here. fold_lean admits only edges of 2^1 and above, so B >= 2^-767, the
+// least argument the Newton sequence is good for (stock: B = 2^-755 for |v|^2, 2^-749 for |w|^2). For d the sign is
+// masked off and the window is 2^-384 <= |d| < 2^384, inside the +-500 exponents that rcp_newton is good for. With R in f32
+// a non-zero det is a sum of multiples of 2^-447 below 2^387; besides det = 0, inf and NaN, only the dets below 2^-384
+// or from 2^384 up leave it, which R reaches long after |w| has failed.
+constexpr uint32_t LEAN_SPAN = 768u << 20;
+constexpr uint32_t SQRT_LO_HI = 256u << 20, SQRT_HI_HI = (1023u + 233u) << 20;   // high words of 2^-767 and 2^233
 __device__ __forceinline__ uint32_t hi_word(double x) { return (uint32_t)(__builtin_bit_cast(uint64_t, x) >> 32); }
-__device__ __forceinline__ bool all_in_range(double xv, double xw, double d) {
-    constexpr uint32_t SPAN = 1000u << 20, SQRT_BASE = 256u << 20, RCP_BASE = 523u << 20;
-    const uint32_t tv = xv == 0.0 ? 0u : hi_word(xv) - SQRT_BASE, tw = xw == 0.0 ? 0u : hi_word(xw) - SQRT_BASE;
+__device__ __forceinline__ bool all_in_range(uint32_t base_v, uint32_t base_w, double xv, double xw, double d) {
+    constexpr uint32_t RCP_BASE = (1023u - 384u) << 20;
+    const uint32_t tv = xv == 0.0 ? 0u : hi_word(xv) - base_v, tw = xw == 0.0 ? 0u : hi_word(xw) - base_w;
     const uint32_t td = (hi_word(d) & 0x7fffffffu) - RCP_BASE;
-    return max(tv, max(tw, td)) < SPAN;
+    return max(tv, max(tw, td)) < LEAN_SPAN;
 }
 __device__ __forceinline__ double sqrt_newton(double x) {
     const double g = fmin(__builtin_amdgcn_rsq(x), 0x1p+512);   // the identity in the window; x = +0: see above
@@ -172,6 +186,20 @@ __device__ __forceinline__ double rcp_newton(double d) {
 __device__ __forceinline__ float sumsq3(const float *x) {
     const float p0 = x[0] * x[0], p1 = x[1] * x[1], p2 = x[2] * x[2];
     return (float)(((double)p0 + (double)p1) + (double)p2);
+}
+
+// The range test of STEP_STOCK_SHADOW's main path: m = max |p_c| over the tested positions, S = fail_range_sq32 with
+// 2^-100 <= S < +inf (fold_lean). range_safe(m, S) implies sumsq3(p) <= S for every p with |p_c| <= m:
+//   q = fl(m * m) >= fl(p_c * p_c) (rounding is monotone), the double sum of the three products is at most 3q (2q and 3q
+//   are doubles, so neither addition rounds above them) and its f32 rounding at most 3q * (1 + 2^-24) + 2^-150.
+//   t = fl(q * K) >= q * K * (1 - 2^-24) - 2^-150 with K = 3 + 2^-18, and K * (1 - 2^-24) - 3 * (1 + 2^-24) > 2^-19,
+//   so t - sumsq3(p) > q * 2^-19 - 2^-149 >= 0 for q >= 2^-130: sumsq3(p) <= t < S. For q < 2^-130, sumsq3(p) < 2^-128 < S.
+// It is false for m = NaN, m = +inf and an overflowing product. It is monotone in m, so it is `m < pos_safe32` for the
+// least float32 at which it fails: fold_pos_safe finds that value for mg_quadrotor_plan_fold and the tests. The kernel
+// holds the product form because its argument block has no free word for pos_safe32 (see QuadK): two v_mul_f32 per step.
+__host__ __device__ __forceinline__ bool range_safe(float m, float S) {
+    const float q = m * m;
+    return q * 0x1.80002p+1f < S;
 }
 
 // np.linalg.inv on a float32 matrix (quadrotorsim.py:207): numpy promotes to float64, solves, and
@@ -208,23 +236,22 @@ __device__ __forceinline__ void inv3(const float *Af, float *Ainv, double *A) {
     inv3_scale(A, c, 1.0 / c.det, Ainv);
 }
 
-// Ri, Rd, nv and nw of the lane's current R, v and w (inv3 and the two norms). FAST: the in-range sequences above, and
+// Ri, Rd, nv and nw of the lane's current R, v and w (inv3 and the two norms). update_derived_fast: the in-range sequences above, and
 // `ok` cleared for a lane whose arguments leave their window. The caller redoes the whole step with the library's sqrt
 // and division when any lane of the wave has a cleared flag: one wave-uniform branch per step, which costs the wave about
 // 60 % more time when taken. A masked recompute behind a branch after each update bounds that cost, but splits the
 // straight-line sub-steps into scheduling regions: it doubled the VGPRs and took back the whole gain (profiles/r09/).
-template <bool FAST>
-__device__ __forceinline__ void update_derived(Lane &s, bool &ok) {
-    if (!FAST) {
-        inv3(s.R, s.Ri, s.Rd);
-        s.nv = norm3(s.v);
-        s.nw = norm3(s.w);
-        return;
-    }
+// The two forms are separate functions so that the fast one cannot be called without its plan's window bases.
+__device__ __forceinline__ void update_derived(Lane &s) {
+    inv3(s.R, s.Ri, s.Rd);
+    s.nv = norm3(s.v);
+    s.nw = norm3(s.w);
+}
+__device__ __forceinline__ void update_derived_fast(Lane &s, bool &ok, uint32_t base_v, uint32_t base_w) {
     const Cof c = inv3_cof(s.R, s.Rd);
     const double xv = sumsq3(s.v), xw = sumsq3(s.w);
     const double r = rcp_newton(c.det), nv = sqrt_newton(xv), nw = sqrt_newton(xw);
-    ok = ok & all_in_range(xv, xw, c.det);
+    ok = ok & all_in_range(base_v, base_w, xv, xw, c.det);
     inv3_scale(s.Rd, c, r, s.Ri);
     s.nv = nv;
     s.nw = nw;
@@ -246,7 +273,7 @@ __device__ __forceinline__ void update_derived(Lane &s, bool &ok) {
 // eight torque products to the four T_i*c. The sums are written as the reference's own: w0*pc1 - w1*pc0 is A - B,
 // A - (-B) = A + B, (-A) - (-B) = B - A and (-A) - B, never a negated sum (-(A-B) differs from B-A in the sign of
 // a zero result).
-// FAST: update_derived<true> (STEP_STOCK_SHADOW).
+// FAST: update_derived_fast (STEP_STOCK_SHADOW).
 template <bool SIMPLE, bool RECIP = false, bool XF = false, bool FAST = false>
 __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *eff32, bool want_power, bool &ok) {
     static_assert(!XF || SIMPLE, "the X frame is a SIMPLE configuration");
@@ -262,9 +289,24 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
         const double A = s.w[0] * c, B = s.w[1] * c;
         xcz[0] = A - B;
         xcz[1] = A + B;
-        xcz[2] = B - A;
-        xcz[3] = (-A) - B;
+        if (!FAST) {
+            xcz[2] = B - A;
+            xcz[3] = (-A) - B;
+        }
     }
+    // FAST (make_plan has established ct0_32 > 0 and, for the X frame, lm > 0): propellers 2 and 3 reuse the products
+    // m_i = xcz[i] * lm of propellers 0 and 1, v_1 = bvz - m_{i-2}, two v_mul_f64 and two v_add_f64 fewer per sub-step.
+    //   B - A is -(A - B) and (-A) - B is -(A + B) bit for bit unless the result is an exact zero (x - x is +0 either way
+    //   round, and so are the sums of signed zeros that differ), and a product by lm keeps that: the only difference is
+    //   the sign of a zero m. bvz - m then differs from bvz + (-m) only when bvz is -0 as well, and only in the sign of a
+    //   zero v_1 (a non-zero or +0 bvz absorbs a zero of either sign). v_1 enters t1 = (double)(ct1 * w_m) * v_1 alone,
+    //   so t1 is a zero of either sign (or NaN in both forms, for a non-finite factor). t0 = (ct0 * w_m) * w_m is
+    //   +0 or positive for ct0 > 0: the two factors w_m carry the same sign, a product that underflows is +0, and
+    //   (ct0 * -0) * -0 is +0 (a NaN w_m gives NaN in both forms). So thrust = t0 + t1 is t0 for a positive t0 and
+    //   +0 + (+-0) = +0 otherwise: the same bits in both forms.
+    //   The same fact serves prop_force_z: thrust is never -0 (t0 + t1 with t0 >= +0 gives -0 only from -0 + -0), so
+    //   0.0 + thrust is thrust and the first propeller's (float)(0.0 + thrust) is T = (float)thrust.
+    double m01[2];
 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -276,8 +318,14 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
         float w_m = s.pw[i] + k.prec32 * d_prop_w;               // :144-145
         const float *pc = &k.pc[3 * i];
         // :149-151 (omega x coord)[2] * l_m, f64
-        double cz = XF ? xcz[i] : s.w[0] * (double)pc[1] - s.w[1] * (double)pc[0];
-        double v_1 = bvz + cz * (double)(XF ? k.lm[0] : k.lm[i]);
+        double v_1;
+        if (XF && FAST) {
+            if (i < 2) m01[i] = xcz[i] * (double)k.lm[0];
+            v_1 = i < 2 ? bvz + m01[i] : bvz - m01[i - 2];
+        } else {
+            double cz = XF ? xcz[i] : s.w[0] * (double)pc[1] - s.w[1] * (double)pc[0];
+            v_1 = bvz + cz * (double)(XF ? k.lm[0] : k.lm[i]);
+        }
         float t0 = (k.ct0_32 * w_m) * w_m;                       // :154 f32 chain
         double t1 = (double)(k.ct1_32 * w_m) * v_1;              // :155 f32 product, widened
         double thrust = (double)t0 + t1;
@@ -286,8 +334,9 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
             thrust = thrust + ((k.ct2 * v_1) * v_1) * sign;      // :156 f64
         }
         s.pw[i] = w_m;                                           // :158
-        prop_force_z = (float)((double)prop_force_z + thrust);   // :159 f64 add, f32 store
         const float T = (float)thrust;                           // :160-162 cross(-[0,0,T], coord)
+        if (FAST && i == 0) prop_force_z = T;                    // (float)(0.0 + thrust), see above
+        else prop_force_z = (float)((double)prop_force_z + thrust);   // :159 f64 add, f32 store
         if (XF) {                                                // T*(+-c) = +-(T*c), the sums as above
             const float Tc = T * k.pc[1];
             prop_torque[0] = (i < 2) ? prop_torque[0] + Tc : prop_torque[0] - Tc;
@@ -403,7 +452,8 @@ __device__ __forceinline__ void substep(const QuadK &k, Lane &s, const float *ef
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) s.w[c] = s.w[c] + k.prec * alpha[c];
-    update_derived<FAST>(s, ok);                                 // :206-208, and the norms
+    if (FAST) update_derived_fast(s, ok, k.lean_base_v, k.lean_base_w);   // :206-208, and the norms
+    else update_derived(s);
 }
 
 // quadrotorsim.py:212-221. A select chain, not early returns: all three tests are cheap and the early returns
@@ -627,17 +677,15 @@ __device__ __forceinline__ void load_state(const mg_quadrotor_state &st, int n, 
     ct = ld_soa<BUF>(st.ct, 1, n, 0, e);
 }
 
-template <bool FAST = false>
-__device__ __forceinline__ void derive_lane(Lane &s, bool &ok) {
-    update_derived<FAST>(s, ok);
+__device__ __forceinline__ void derive_lane(Lane &s) {   // the library's sqrt and division
+    update_derived(s);
     s.power = 0.0f;
 }
 
 template <bool BUF = false>
 __device__ __forceinline__ void load_lane(const mg_quadrotor_state &st, int n, int e, Lane &s, int &ct) {
-    bool ok = true;
     load_state<false, BUF>(st, n, e, s, ct);
-    derive_lane<false>(s, ok);
+    derive_lane(s);
 }
 
 template <bool BUF = false>
@@ -765,6 +813,7 @@ struct StepIO {
 // The step kernel's argument block as the kernarg segment lays it out, and a pointer to it that the
 // optimiser cannot relate to the kernel's own argument loads (see the epilogue of the step kernel).
 struct KArgs { QuadK k; mg_quadrotor_state st; StepIO io; int n; int n_steps; };
+static_assert(sizeof(QuadK) == 448 && sizeof(KArgs) == 560, "kernel argument layout (the prologue touches its nine 64-byte lines)");
 typedef const __attribute__((address_space(4))) KArgs KArgsC;
 __device__ __forceinline__ KArgsC *kernargs_fresh() {
     KArgsC *p = (KArgsC *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -784,8 +833,10 @@ __device__ __forceinline__ KArgsC *kernargs_fresh() {
 //                      for every lane while the prologue loads are in flight, so the restart only moves values.
 //                      With more than one wave per SIMD the VALU is busy during the loads, and ~150 extra VALU on
 //                      every wave would cost more than the branch it saves.
-//                      Its sub-steps take sqrt and 1/det without the library's range steps (update_derived<true>);
+//                      Its sub-steps take sqrt and 1/det without the library's range steps (update_derived_fast);
 //                      a wave with an argument out of range redoes the step with the library's (see the kernel).
+//                      The three failure tests are part of that range (fold_lean), so its sub-steps hold no
+//                      failure_code(); a plan whose thresholds cannot be folded takes STEP_STOCK instead.
 // Four options, also resolved on the host:
 //   XF   (both stock forms) the stock X frame of propellers (config_is_xframe, substep<>); any other SIMPLE layout
 //        keeps XF = false.
@@ -836,7 +887,7 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
     static_assert(SHADOW || !BUF, "BUF is an option of STEP_STOCK_SHADOW");
     static_assert(STOCK || !FLAT, "FLAT is an option of the stock forms");
     static_assert(SHADOW || !HOVER, "HOVER is an option of STEP_STOCK_SHADOW");
-    constexpr bool FAST = SHADOW && MG_QUAD_FASTPATH;   // in-range sqrt / 1/det (update_derived), whole-step fallback below
+    constexpr bool FAST = SHADOW && MG_QUAD_FASTPATH;   // in-range sqrt / 1/det (update_derived_fast), whole-step fallback below
     const int n_steps = SHADOW ? 1 : n_steps_arg;
     __shared__ float tiles[WAVES_PER_BLOCK][mg::WAVE * (OBS_DIM + 1)];
     const int e = blockIdx.x * BLOCK + threadIdx.x;
@@ -882,7 +933,7 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         for (int c = 0; c < 3; ++c) asm volatile("" : "+v"(rd.v[c]), "+v"(rd.w[c]));   // not sunk into the restart branch
         asm volatile("" : "+v"(rd.nv), "+v"(rd.nw));
         __builtin_amdgcn_sched_barrier(0);
-        derive_lane<false>(s, ok);   // the library's sqrt / 1/det: hidden behind the loads, and exact for reset states (v = w = 0)
+        derive_lane(s);   // the library's sqrt / 1/det: hidden behind the loads, and exact for reset states (v = w = 0)
         __builtin_amdgcn_sched_barrier(0);
     } else {
         a_next = reinterpret_cast<const float4 *>(io.action)[el];
@@ -915,7 +966,27 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         const double old_pos[3] = {(double)s.p[0] + k.xoff, (double)s.p[1] + k.yoff,
                                    (double)(s.p[2] + k.zoff32)};            // env.py:131-133
         int fail = 0;
-        if (STOCK) {             // straight-line sub-steps (see StepForm); the first failure code is kept
+        if (FAST) {
+            // Straight-line sub-steps without the failure tests: fold_lean has moved them into `ok`. The velocity and the
+            // body-rate test are the upper edges of all_in_range's windows. The range test is a running max-norm: pmax is
+            // the largest |p_c| of the ten tested positions, and range_safe(pmax) implies sumsq3(p) <= fail_range_sq32 at
+            // each of them (see range_safe). A NaN component is dropped by the max; it makes sumsq3(p) NaN and the
+            // reference's test `NaN > S` false, so it cannot fail that sample either, and the other components cannot
+            // alone: each is at most pmax. (If every |p_c| of every sample is NaN, pmax is NaN, the compare is false and
+            // the wave takes the fallback, which is always right.) So a lane with `ok` set has failed no test at any
+            // sub-step: fail = 0. A lane that fails one has `ok` clear, and the wave redoes the step below with the full
+            // tests.
+            float pmax = 0.0f;
+#pragma unroll MG_QUAD_SUBSTEP_UNROLL
+            for (int it = 0; it < STOCK_TIMES - 1; ++it) {
+                substep<SIMPLE, true, XF, true>(k, s, eff32, false, ok);
+                const float m3 = fmaxf(fmaxf(fabsf(s.p[0]), fabsf(s.p[1])), fabsf(s.p[2]));
+                pmax = it == 0 ? m3 : fmaxf(pmax, m3);
+            }
+            substep<SIMPLE, true, XF, true>(k, s, eff32, true, ok);
+            pmax = fmaxf(pmax, fmaxf(fmaxf(fabsf(s.p[0]), fabsf(s.p[1])), fabsf(s.p[2])));
+            ok = ok & range_safe(pmax, k.fail_range_sq32);
+        } else if (STOCK) {      // straight-line sub-steps (see StepForm); the first failure code is kept
 #pragma unroll MG_QUAD_SUBSTEP_UNROLL
             for (int it = 0; it < STOCK_TIMES - 1; ++it) {
                 substep<SIMPLE, true, XF, FAST>(k, s, eff32, false, ok);
@@ -925,16 +996,19 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
             substep<SIMPLE, true, XF, FAST>(k, s, eff32, true, ok);
             const int code = failure_code(k, s);
             fail = fail ? fail : code;
+        }
+        if (STOCK) {
             if (FAST && __builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0, 0)) {
-                // Some lane of the wave met a sqrt or 1/det argument outside the fast path's window (zero or tiny
-                // velocity / body rate, inf or NaN, a singular R): redo the step for the whole wave from the loaded
+                // Some lane of the wave met a sqrt or 1/det argument outside the fast path's window (a tiny velocity or
+                // body rate, inf or NaN, a singular R), or came near a failure threshold (a squared norm at its window's
+                // upper edge, |p|_inf >= pos_safe32): redo the step for the whole wave from the loaded
                 // state with the library's sqrt and division. The state is still in memory (stores come later); the
                 // step's inputs are re-read through kernargs_fresh so that none is held in SGPRs across the sub-steps.
                 const KArgsC *kaf = kernargs_fresh();
                 const QuadK &kf = *(const QuadK *)&kaf->k;
                 int ct_loaded;
                 load_state<true, BUF>(*(const mg_quadrotor_state *)&kaf->st, n, el, s, ct_loaded);
-                derive_lane<false>(s, ok);
+                derive_lane(s);
                 fail = 0;
 #pragma unroll 1
                 for (int it = 0; it < STOCK_TIMES; ++it) {
@@ -1200,7 +1274,57 @@ int fold_config(const mg_quadrotor_config *c, QuadK *k, bool need_targets = true
     for (int i = 0; i < 3; ++i) { k->init_v_base[i] = 0.0f; k->init_w_base[i] = 0.0f; }
     k->init_v_noisy = k->init_w_noisy = 0.0;
     k->seed = k->env_id_base = 0;
+    k->lean_base_v = k->lean_base_w = 0;
     return MG_OK;
+}
+
+// ---- host: the failure tests of STEP_STOCK_SHADOW folded into its range window (see all_in_range, the step kernel) --
+double from_hi_word(uint32_t h) { const uint64_t b = (uint64_t)h << 32; double x; memcpy(&x, &b, sizeof x); return x; }
+uint32_t host_hi_word(double x) { uint64_t b; memcpy(&b, &x, sizeof b); return (uint32_t)(b >> 32); }
+
+// The exclusive upper edge (a high word) of the window for x = norm^2 under the test `norm > thr`: the double Y with
+// that high word and a zero low word has Y <= thr^2 * (1 - 2^-19), Y <= 2^233 and sqrt(Y) <= thr. A lane with
+// hi_word(x) below the edge has x < Y, so sqrt(x) <= sqrt(Y) <= thr: it does not fail. The slack of 2^-19 is there for
+// a device sqrt that is not the host's correctly rounded one; the loop, as the search for fail_range_sq32, makes the
+// statement about the host's sqrt unconditional. 0: the test cannot be folded. That is a NaN threshold (`>` is false
+// for ever, but a window has an edge), a negative one or -0.0 / +0.0 (a zero norm fails or sits on the threshold, and
+// zeros are mapped into the window), and one whose edge is below 2^1: then base = edge - LEAN_SPAN would lie below 2^-767,
+// the least argument of sqrt_newton. thr = +inf folds: nothing fails, the edge is that of the sqrt window.
+uint32_t fold_norm_edge(double thr) {
+    if (!(thr > 0.0)) return 0;
+    const double y = (thr * thr) * (1.0 - 0x1p-19);          // +inf for a large threshold
+    uint32_t e = y < 0x1p+233 ? host_hi_word(y) : SQRT_HI_HI;
+    while (e > 0 && sqrt(from_hi_word(e)) > thr) e -= 1;
+    return e >= SQRT_LO_HI + LEAN_SPAN ? e : 0;
+}
+
+// pos_safe32: the least float32 m >= 0 with !range_safe(m, S), so that the kernel's test is m < pos_safe32 (range_safe is
+// monotone in m: both products round monotonically). 0: the range test cannot be folded, for S = NaN (no position
+// fails), -inf (a negative range: every position fails), +inf (a range of FLT_MAX's square root and up, or +inf) and
+// S < 2^-100, where range_safe's argument needs normal products. Bisection on the bit patterns of the non-negative floats.
+float fold_pos_safe(float S) {
+    if (!(S >= 0x1p-100f) || S == INFINITY) return 0.0f;
+    uint32_t lo = 0, hi = 0x7f800000u;   // range_safe(+0) holds (0 < S), range_safe(+inf) does not
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        float m;
+        memcpy(&m, &mid, sizeof m);
+        if (range_safe(m, S)) lo = mid; else hi = mid;
+    }
+    float P;
+    memcpy(&P, &hi, sizeof P);
+    return P;
+}
+
+// Fills the folded constants; false when one of the three tests cannot be folded, or when ct0_32 > 0 does not
+// hold (substep<FAST> relies on it). launch_plan then takes STEP_STOCK, which keeps failure_code() per sub-step.
+bool fold_lean(QuadK *k) {
+    const uint32_t ev = fold_norm_edge(k->fail_velocity), ew = fold_norm_edge(k->fail_w);
+    const float P = fold_pos_safe(k->fail_range_sq32);
+    if (ev == 0 || ew == 0 || P == 0.0f || !(k->ct0_32 > 0.0f)) return false;
+    k->lean_base_v = ev - LEAN_SPAN;
+    k->lean_base_w = ew - LEAN_SPAN;
+    return true;
 }
 
 // structure test for the SIMPLE kernel specialisation (see substep<>)
@@ -1243,6 +1367,7 @@ struct Plan {
     int32_t stock;   // STEP_STOCK applies (see StepForm)
     int32_t xframe;  // ... with the X-frame option (see StepForm)
     int32_t simds;   // SIMDs of the device (0: unknown, STEP_STOCK_SHADOW is not used)
+    int32_t lean;    // the failure tests fold into the range window (fold_lean); 0: STEP_STOCK_SHADOW is not used
     QuadK k;
     mg_quadrotor_state st;
 };
@@ -1275,6 +1400,8 @@ int make_plan(Plan *p, const mg_quadrotor_config *cfg, const mg_quadrotor_autore
     const bool force_generic = getenv("MG_QUAD_GENERIC") != nullptr;
     p->stock = (!force_generic && p->simple && p->k.quality_recip_exact && p->k.times == STOCK_TIMES && p->k.auto_reset) ? 1 : 0;
     p->xframe = (p->stock && config_is_xframe(cfg)) ? 1 : 0;
+    // lm > 0 with the X frame: c > 0 does not give it (c * c can underflow to 0 in float32), and substep<XF, FAST> states it
+    p->lean = (p->stock && fold_lean(&p->k) && (!p->xframe || p->k.lm[0] > 0.0f)) ? 1 : 0;
     p->simds = 0;
     int cus = 0;
     if (p->device >= 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess)
@@ -1307,7 +1434,7 @@ int launch_plan(const Plan *p, int32_t n_steps, const float *action, float *obs,
     // FLAT / HOVER: no collision map / the hovering task, both properties of the folded configuration
     const bool flat = p->k.map == nullptr, hover = p->k.task == MG_QUADROTOR_TASK_HOVERING_CONTROL;
     StepKernel kern;
-    if (p->stock && n_steps == 1 && waves <= p->simds) {
+    if (p->stock && p->lean && n_steps == 1 && waves <= p->simds) {
         kern = pick_shadow(p->xframe != 0, buf, flat, hover);
     } else if (p->stock) {
         if (p->xframe) kern = flat ? quadrotor_step_kernel<true, STEP_STOCK, true, false, true> : quadrotor_step_kernel<true, STEP_STOCK, true>;
@@ -1416,6 +1543,27 @@ extern "C" int mg_quadrotor_plan_init(mg_quadrotor_plan *plan, const mg_quadroto
     Plan *p = reinterpret_cast<Plan *>(plan);
     p->magic = 0;
     return make_plan(p, cfg, ar, n_envs, state);
+}
+
+extern "C" int mg_quadrotor_plan_fold(const mg_quadrotor_plan *plan, mg_quadrotor_fold *out) {
+    MG_REQUIRE_PTR(plan);
+    MG_REQUIRE_PTR(out);
+    const Plan *p = reinterpret_cast<const Plan *>(plan);
+    if (p->magic != PLAN_MAGIC) return mg::set_error(MG_ERR_BAD_CONFIG, "mg_quadrotor_plan is not initialised");
+    *out = mg_quadrotor_fold{};
+    out->one_wave_form = !p->stock ? STEP_GENERIC : (p->lean ? STEP_STOCK_SHADOW : STEP_STOCK);
+    out->span = LEAN_SPAN;
+    out->fail_velocity = p->k.fail_velocity;
+    out->fail_w = p->k.fail_w;
+    out->fail_range_sq32 = p->k.fail_range_sq32;
+    if (p->lean) {
+        out->base_v = p->k.lean_base_v;
+        out->base_w = p->k.lean_base_w;
+        out->edge_v = p->k.lean_base_v + LEAN_SPAN;
+        out->edge_w = p->k.lean_base_w + LEAN_SPAN;
+        out->pos_safe32 = fold_pos_safe(p->k.fail_range_sq32);
+    }
+    return MG_OK;
 }
 
 #ifdef MG_QUAD_PHASE_STAMPS
