@@ -639,6 +639,31 @@ int mg_walker_step(const mg_walker_topology *topo, const mg_walker_models *model
                    int32_t n_envs, const mg_walker_state *state, const float *action, float *obs, float *reward,
                    float *rewards5, uint8_t *done, void *stream);
 
+/* mg_walker_rollout — n_steps steps per call, by definition the loop `for t: mg_walker_step(action = actions[t])` on the same
+ * state with prm->step_index advanced by one per step — same transitions, rewards, rewards5, dones, fused auto-resets (the
+ * Philox joint noise of a reset inside step t is keyed by step index prm->step_index + t) and end state bit for bit, every
+ * array of mg_walker_state included (potential, steps, feet_contact, bad_contacts and foot_force after the last step), also
+ * for an env without auto_reset that is stepped past done (it goes on stepping, as in the batched step). ONE launch: the robot
+ * stays in LDS between the steps; the topology tables, the model constants and the per-robot lookups are set up once, the
+ * state is loaded once and stored once. Additive entry point; MG_ABI_VERSION is unchanged.
+ *   n_steps >= 1. obs_every selects the steps that leave an observation: 0 = the last step only; k >= 1 = every step t
+ *   (0-based) with (t + 1) % k == 0, and always the last one. K = number of recorded steps, in ascending order.
+ *   actions f32 [n_steps][N][nj]; reward f32 [n_steps][N]; rewards5 f32 [n_steps][N][5] (may be NULL); done u8 [n_steps][N].
+ *   obs f32 [K][N][8 + 2 nj + nf]: slice k is the observation after recorded step k (with auto_reset: the first observation
+ *   of the next episode where that step ended one).
+ * Honoured step by step, as mg_walker_step does with actuation == 0: terrain boxes and per-robot terrain tables, per-proxy
+ * friction, per-robot gravity / foot friction, body damping, contact margins, self-collision, the velocity clamp, and
+ * ext_wrench in the first sub-step of EVERY env step.
+ * Errors are found on the host before anything is launched: NULL topo / models / prm / state / actions / obs / reward / done,
+ * n_steps < 1 or obs_every < 0 (MG_ERR_BAD_SIZE), whatever mg_walker_step refuses about the descriptors, the terrain and the
+ * wave mapping's limits, prm->mapping == 0 (MG_ERR_UNSUPPORTED: the lane mapping is the single-step cross-check path),
+ * prm->actuation != 0 (MG_ERR_UNSUPPORTED: the in-launch actuators take one pd_command per launch) and a non-NULL
+ * prm->substep_log (MG_ERR_BAD_CONFIG: its shape is one launch's sub-steps). Nothing is allocated and nothing synchronises
+ * (stream capture works as for the step). */
+int mg_walker_rollout(const mg_walker_topology *topo, const mg_walker_models *models, const mg_walker_params *prm,
+                      int32_t n_envs, const mg_walker_state *state, int32_t n_steps, int32_t obs_every,
+                      const float *actions, float *obs, float *reward, float *rewards5, uint8_t *done, void *stream);
+
 /* ========================================================================================
  * Quadrupedal (Unitree A1) — the ACTUATION path of metagym/quadrupedal/robots/minitaur.py + a1.py +
  * laikago_motor.py for N robots: everything `Minitaur._StepInternal` (minitaur.py:232-238) does on either side of

@@ -305,6 +305,8 @@ SIGNATURES = {
                                   C.c_int32, C.POINTER(WalkerState), _P, _P, _P, _P]),
     "mg_walker_step": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
                                  C.c_int32, C.POINTER(WalkerState), _P, _P, _P, _P, _P, _P]),
+    "mg_walker_rollout": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
+                                    C.c_int32, C.POINTER(WalkerState), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mg_a1_apply_action": (C.c_int, [C.POINTER(A1ActuatorConfig), C.c_int32, C.POINTER(A1ActuatorState), _P, _P,
                                      C.c_double, _P, _P]),
     "mg_a1_receive_observation": (C.c_int, [C.POINTER(A1ActuatorConfig), C.c_int32, C.POINTER(A1ActuatorState),

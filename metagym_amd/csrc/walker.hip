@@ -134,9 +134,9 @@ struct Env {   // per-lane simulation state
 
 // Joint noise of the fused auto-reset: numpy's uniform(low=-0.1, high=0.1) = low + (high - low) * u
 // (walker_base.py:15) with u from Philox4x32-10, counter (global env id, step, joint / 4).
-__device__ __forceinline__ double reset_joint_noise(const mg_walker_params &prm, int e, int j) {
+__device__ __forceinline__ double reset_joint_noise(const mg_walker_params &prm, uint64_t step, int e, int j) {
     uint32_t r[4];
-    const uint64_t gid = prm.env_id_base + (uint64_t)e, step = prm.step_index;
+    const uint64_t gid = prm.env_id_base + (uint64_t)e;
     philox4x32_10((uint32_t)gid, (uint32_t)step, (uint32_t)(step >> 32) ^ ((uint32_t)(gid >> 32) << 8),
                   0x57414c4bu + (uint32_t)(j >> 2), (uint32_t)prm.seed, (uint32_t)(prm.seed >> 32), r);
     return -0.1 + 0.2 * ((double)r[j & 3] * (1.0 / 4294967296.0));
@@ -600,7 +600,7 @@ __global__ __launch_bounds__(WK_BLOCK) void walker_step_kernel(mg_walker_topolog
         for (int i = 0; i < 9; ++i) s.rot[i] = m.body_rot[i];
         s.vel = v3(0, 0, 0);
         s.omega = v3(0, 0, 0);
-        for (int j = 0; j < nj; ++j) { s.q[j] = reset_joint_noise(prm, e, j); s.qd[j] = 0.0; }
+        for (int j = 0; j < nj; ++j) { s.q[j] = reset_joint_noise(prm, prm.step_index, e, j); s.qd[j] = 0.0; }
         for (int f = 0; f < nf; ++f) { fc[f] = 0.0f; st.feet_contact[(size_t)f * n_envs + e] = 0.0f; }
         observe(tp, m, prm, s, fc, ob, dist, at_limit);
         st.potential[e] = -dist / (prm.time_step * prm.frame_skip);
@@ -1855,13 +1855,30 @@ __device__ __forceinline__ void wave_substep(const mg_walker_topology &tp, const
 // (WavePlan::tail) once per launch: an exposed trip to L2 for each read before, 1 - 2.5 % of the A1's 13-sub-step launch. Larger
 // robots and the tuned kernels keep reading the table (their LDS decides how many envs fit a CU).
 template <int NMAX, class SH> constexpr bool WAVE_MODEL_IN_LDS = SH::nb == 0 && NMAX <= 18;
-template <int NMAX, class SH>
-__global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 && SH::nb != 0) ? 3 : (SH::nb != 0 ? MG_WALKER_HUM_WAVES : ((NMAX == 18 && SH::nj == 12) ? MG_WALKER_A1_WAVES : 2))))) void walker_step_wave_kernel(mg_walker_topology tp, mg_walker_models ms,
+// The rollout form (ROLL) is compiled for one wave fewer — 2 for the tuned ant, 1 elsewhere: at the step's setting every rollout
+// instantiation spilled 41 - 95 VGPRs to scratch (the sub-step loop's invariants stay live through calc_state once the code
+// jumps back), and a rollout may not use more scratch than its step (profiles/walker/rollout_resources.txt; DESIGN.md §3.12
+// has what that costs at large N).
+template <int NMAX, class SH, bool ROLL> constexpr int WAVE_WAVES_PER_EU =
+    ROLL ? ((NMAX <= 14 && SH::nb != 0) ? 2 : 1)
+         : ((NMAX <= 14 && SH::nb != 0) ? 3 : (SH::nb != 0 ? MG_WALKER_HUM_WAVES : ((NMAX == 18 && SH::nj == 12) ? MG_WALKER_A1_WAVES : 2)));
+// ROLL = false: one env step per launch, walker_step_wave_kernel<NMAX, SH>. ROLL = true: the rollout form of the same code
+// (mg_walker_rollout), roll.n_steps env steps with the robot resident in LDS — the topology tables, the model tail, the
+// per-robot lookups and the state load / store are paid once, the step loop holds what one step does. There `action`,
+// `reward`, `rewards5` and `done` are [n_steps] rows of the step's arrays (they advance by one row per step) and `obs` holds one
+// [N][obs_dim] slice per recorded step (roll.obs_every: the rule above mg_maze2d_rollout in the header).
+template <bool ROLL> struct WaveRoll { };
+template <> struct WaveRoll<true> { int n_steps, obs_every; };
+template <int NMAX, class SH, bool ROLL = false>
+__global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu(WAVE_WAVES_PER_EU<NMAX, SH, ROLL>))) void walker_step_wave_kernel(mg_walker_topology tp, mg_walker_models ms,
                                                               mg_walker_params prm, mg_walker_state st, int n_envs,
                                                               int plan_rows, int plan_scan, const float *action, float *obs,
-                                                              float *reward, float *rewards5, uint8_t *done) {
+                                                              float *reward, float *rewards5, uint8_t *done, WaveRoll<ROLL> roll) {
+    int n_steps = 1, obs_every = 0;
+    if constexpr (ROLL) { n_steps = roll.n_steps; obs_every = roll.obs_every; }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int e = mg::env_of_block(blockIdx.x, n_envs), lane = threadIdx.x;
+    const int e = mg::env_of_block(blockIdx.x, n_envs);
+    int lane = threadIdx.x;       // (written again only by the rollout form, at the head of every env step)
     const int nb = SH::nb ? SH::nb : tp.n_bodies, nj = SH::nj ? SH::nj : tp.n_joints, ns = SH::nb ? SH::ns : tp.n_spheres;
     const int nf = tp.n_feet, obs_dim = 8 + 2 * nj + nf;
     const double *row = ms.table + (size_t)st.task_id[e] * ms.model_stride;
@@ -1964,7 +1981,7 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
     if (lane < nj) {
         L.q[lane] = st.q[(size_t)lane * n_envs + e];
         L.qd[lane] = st.qd[(size_t)lane * n_envs + e];
-        L.tau[lane] = prm.actuation != 0 ? 0.0 : motor_torque(prm, m.motor()[lane], action[(size_t)e * nj + lane]);
+        if (!ROLL) L.tau[lane] = prm.actuation != 0 ? 0.0 : motor_torque(prm, m.motor()[lane], action[(size_t)e * nj + lane]);
     }
     WSYNC();
     unsigned long long touch[2] = {0ull, 0ull};     // proxies in contact with the ground / terrain in the last sub-step
@@ -1982,7 +1999,7 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
         gvec = v3(prm.gravity_env[e], prm.gravity_env[(size_t)n_envs + e], prm.gravity_env[2 * (size_t)n_envs + e]);
     if (GENERIC && prm.foot_friction_env != nullptr) foot_mu = prm.foot_friction_env[e];
     ActLane act{0.0, 0.0, 0.0, 0.0, 0.0};
-    if (prm.actuation != 0 && lane < nj) {
+    if (!ROLL && prm.actuation != 0 && lane < nj) {      // (a rollout is refused with actuators on: one pd_command per launch)
         if (GENERIC && prm.actuation == 3) {          // HYBRID: desired angle, kp, desired rate, kd, additional torque
             const double *c5 = prm.pd_command + ((size_t)5 * lane) * n_envs + e;
             act = ActLane{c5[0], c5[(size_t)n_envs], c5[2 * (size_t)n_envs], c5[3 * (size_t)n_envs], c5[4 * (size_t)n_envs]};
@@ -1994,8 +2011,21 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
             }
         }
     }
+    // ---- the env step: once in the step kernel; the rollout form comes back to env_step n_steps - 1 times, the robot staying
+    // in the slab. (A label and not a loop statement: the step form then compiles to what it was before the rollout existed.)
+    // Every env step of a rollout starts from a lane index the optimiser cannot see through and behind a compiler-level memory
+    // barrier, so what a step derives from the lane or loads (addresses, model constants, tables) is derived in that step, as
+    // in a launch of its own, and is not carried in registers across the whole rollout.
+    int t = 0;
+env_step:
+    if (ROLL) {
+        asm volatile("" : "+v"(lane) : : "memory");
+        if (lane < nj) L.tau[lane] = motor_torque(prm, m.motor()[lane], action[(size_t)e * nj + lane]);
+        touch[0] = 0ull; touch[1] = 0ull;
+        WSYNC();
+    }
     for (int it = 0; it < prm.frame_skip; ++it) {
-        double *log_row = prm.substep_log ? prm.substep_log + ((size_t)it * (3 * nj + 7)) * n_envs + e : nullptr;
+        double *log_row = (!ROLL && prm.substep_log) ? prm.substep_log + ((size_t)it * (3 * nj + 7)) * n_envs + e : nullptr;
         wave_substep<NMAX, GENERIC, VELF>(tp, m, prm, L, lane, plan.maxr, touch, act, log_row, n_envs,
                                     (st.foot_force != nullptr && it == prm.frame_skip - 1) ? st.foot_force + e : nullptr, nf,
                                     (GENERIC && prm.ext_wrench != nullptr && it == 0) ? prm.ext_wrench + e : nullptr, terrain, gvec, foot_mu);
@@ -2012,8 +2042,10 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
     // after_reset = false: post-step state; the obs carries the PREVIOUS step's feet flags and the flags
     // are then refreshed from this step's contacts (walker_base_env.py:46 vs :57-63).
     // after_reset = true: first observation of a new episode; feet flags are zero (walker_base.py:18).
+    // (rollout: a step that is not recorded writes its row into the slice of the next recorded step, which overwrites it last)
     auto clip5 = [](float v) { return v < -5.0f ? -5.0f : (v > 5.0f ? 5.0f : v); };
     float *ob = obs + (size_t)e * obs_dim;
+    if (ROLL && obs_every > 0) ob += (size_t)(t / obs_every) * n_envs * obs_dim;
     float head[8];
     auto calc_state = [&](bool after_reset, double &dist, int &at_limit, bool &all_finite) {
         wave_kinematics<false>(m, L, lane, false);
@@ -2125,10 +2157,15 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
         }
         if (lane < 9) L.base[3 + lane] = m.body_rot()[lane];
         if (lane < nj) {
-            L.q[lane] = reset_joint_noise(prm, e, lane);
+            L.q[lane] = reset_joint_noise(prm, ROLL ? prm.step_index + (uint64_t)t : prm.step_index, e, lane);
             L.qd[lane] = 0.0;
         }
         WSYNC();
+    }
+    if (ROLL && ++t < n_steps) {       // row t of the per-step arrays
+        action += (size_t)n_envs * nj; reward += n_envs; done += n_envs;
+        if (rewards5) rewards5 += (size_t)n_envs * 5;
+        goto env_step;
     }
 #ifdef MG_WALKER_PROFILE
     if (lane == 0) atomicAdd(&mg_walker_phase_cycles[15], __builtin_readcyclecounter() - ph_k0);   // sub-steps + calc_state
@@ -2145,7 +2182,6 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu((NMAX <= 14 
         st.qd[(size_t)lane * n_envs + e] = L.qd[lane];
     }
 }
-
 
 int check_walker(const mg_walker_topology *tp, const mg_walker_models *ms, const mg_walker_params *prm,
                  const mg_walker_state *st, int n) {
@@ -2179,10 +2215,26 @@ int check_walker(const mg_walker_topology *tp, const mg_walker_models *ms, const
     return MG_OK;
 }
 
+// The terrain arguments of a step or a rollout
+int check_walker_terrain(const mg_walker_params *prm) {
+    if (prm->n_terrain_boxes < 0) return mg::set_error(MG_ERR_BAD_SIZE, "walker terrain: %d boxes", prm->n_terrain_boxes);
+    if (prm->n_terrain_boxes > 0) {
+        if (prm->mapping == 0) return mg::set_error(MG_ERR_UNSUPPORTED, "terrain boxes need the wave mapping");
+        MG_REQUIRE_PTR(prm->terrain);
+        if (prm->terrain_id != nullptr && prm->n_terrain_tables < 1)
+            return mg::set_error(MG_ERR_BAD_SIZE, "walker terrain table: %d courses", prm->n_terrain_tables);
+    }
+    return MG_OK;
+}
+
 // One launch of the wave kernel: the instantiation, its plan and its dynamic LDS (the slab, + the model-constant tail)
-struct WaveLaunch { decltype(&walker_step_wave_kernel<ND, ShapeAny>) kernel; bool model_in_lds; WavePlan plan; size_t lds; };
+struct WaveLaunch {
+    decltype(&walker_step_wave_kernel<ND, ShapeAny>) kernel;
+    decltype(&walker_step_wave_kernel<ND, ShapeAny, true>) rollout;     // the same instantiation's n_steps-per-launch form
+    bool model_in_lds; WavePlan plan; size_t lds;
+};
 template <int NMAX, class SH>
-void wave_use(WaveLaunch *w) { w->kernel = walker_step_wave_kernel<NMAX, SH>; w->model_in_lds = WAVE_MODEL_IN_LDS<NMAX, SH>; w->plan.fd = SH::fd; }
+void wave_use(WaveLaunch *w) { w->kernel = walker_step_wave_kernel<NMAX, SH>; w->rollout = walker_step_wave_kernel<NMAX, SH, true>; w->model_in_lds = WAVE_MODEL_IN_LDS<NMAX, SH>; w->plan.fd = SH::fd; }
 
 // Every decision of a wave-mapping step, made on the host before anything is launched.
 int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const mg_walker_state *st, WaveLaunch *w) {
@@ -2302,13 +2354,7 @@ extern "C" int mg_walker_step(const mg_walker_topology *tp, const mg_walker_mode
         if (prm->mapping == 0) return mg::set_error(MG_ERR_UNSUPPORTED, "in-launch actuators need the wave mapping");
         MG_REQUIRE_PTR(prm->pd_command);
     }
-    if (prm->n_terrain_boxes < 0) return mg::set_error(MG_ERR_BAD_SIZE, "walker terrain: %d boxes", prm->n_terrain_boxes);
-    if (prm->n_terrain_boxes > 0) {
-        if (prm->mapping == 0) return mg::set_error(MG_ERR_UNSUPPORTED, "terrain boxes need the wave mapping");
-        MG_REQUIRE_PTR(prm->terrain);
-        if (prm->terrain_id != nullptr && prm->n_terrain_tables < 1)
-            return mg::set_error(MG_ERR_BAD_SIZE, "walker terrain table: %d courses", prm->n_terrain_tables);
-    }
+    if (int rc = check_walker_terrain(prm)) return rc;
     MG_REQUIRE_PTR(obs);
     MG_REQUIRE_PTR(reward);
     MG_REQUIRE_PTR(done);
@@ -2325,6 +2371,35 @@ extern "C" int mg_walker_step(const mg_walker_topology *tp, const mg_walker_mode
     if (int rc = wave_plan(tp, prm, st, &w)) return rc;
     const WavePlanArgs a = pack(w.plan);
     hipLaunchKernelGGL(w.kernel, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan, action, obs,
-                       reward, rewards5, done);
+                       reward, rewards5, done, WaveRoll<false>{});
     return mg::check_launch("walker_step_wave_kernel");
+}
+
+extern "C" int mg_walker_rollout(const mg_walker_topology *tp, const mg_walker_models *ms, const mg_walker_params *prm,
+                                 int32_t n, const mg_walker_state *st, int32_t n_steps, int32_t obs_every,
+                                 const float *actions, float *obs, float *reward, float *rewards5, uint8_t *done,
+                                 void *stream) {
+    if (int rc = check_walker(tp, ms, prm, st, n)) return rc;
+    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_walker_rollout: n_steps=%d (want >= 1)", n_steps);
+    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "mg_walker_rollout: obs_every=%d (want 0 or k >= 1)", obs_every);
+    if (prm->mapping == 0)
+        return mg::set_error(MG_ERR_UNSUPPORTED, "mg_walker_rollout: mapping = lane is the single-step cross-check path; "
+                             "rollouts need the wave mapping");
+    if (prm->actuation != 0)
+        return mg::set_error(MG_ERR_UNSUPPORTED, "mg_walker_rollout: actuation = %d (the in-launch actuators take one pd_command "
+                             "per launch; rollouts run torque actions, actuation = 0)", prm->actuation);
+    if (prm->substep_log != nullptr)
+        return mg::set_error(MG_ERR_BAD_CONFIG, "mg_walker_rollout: substep_log holds one launch's sub-steps; leave it NULL");
+    if (int rc = check_walker_terrain(prm)) return rc;
+    MG_REQUIRE_PTR(actions);
+    MG_REQUIRE_PTR(obs);
+    MG_REQUIRE_PTR(reward);
+    MG_REQUIRE_PTR(done);
+    WaveLaunch w;
+    if (int rc = wave_plan(tp, prm, st, &w)) return rc;
+    mg::DeviceGuard guard(mg::device_of(st->pos));
+    const WavePlanArgs a = pack(w.plan);
+    hipLaunchKernelGGL(w.rollout, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan, actions, obs,
+                       reward, rewards5, done, WaveRoll<true>{n_steps, obs_every});
+    return mg::check_launch("walker_step_wave_kernel (rollout)");
 }

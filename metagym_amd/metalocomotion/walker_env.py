@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..metamaze.maze_env import rollout_obs_steps
 from ..spaces import Box
 from . import variants
 from .mjcf import DEFAULT_PRESET, Model, contact_margins, load_mjcf, preset_options
@@ -382,8 +383,49 @@ class WalkerBatchEnv(object):
         _lib.check(rc, "mg_walker_step")
         return self._obs, self._reward, self._done, {"rewards": self._rewards5, "steps": self.steps}
 
+    def rollout(self, actions, obs_every=0, rewards5=False):
+        """`for t in range(T): step(actions[t])` in ONE launch, the robots staying in LDS between the steps: same end state
+        (every `_STATE_KEYS` tensor), rewards, dones and fused auto-resets bit for bit, for both settings of `auto_reset` (an env
+        without it that is stepped past `done` goes on stepping, as in `step`). actions: float32 [T, num_envs, n_joints],
+        T >= 1 (a wrong shape is a ValueError). `obs_every` selects the steps that leave an observation
+        (`metamaze.maze_env.rollout_obs_steps`): 0 = the last one only, k >= 1 = every k-th and the last. Returns
+        (obs, reward, done, info): reward float32 [T, N] and done bool [T, N], fresh tensors per call; obs is the persistent
+        [N, obs_dim] buffer `step` returns when obs_every == 0, else a fresh [K, N, obs_dim] tensor with one slice per recorded
+        step (with auto_reset, the first observation of the next episode where that step ended one); info["steps"] the
+        counters after the last step, info["obs_steps"] the K recorded step indices, info["rewards"] float32 [T, N, 5] with
+        `rewards5=True`. `global_step` advances by T (the Philox step of an auto-reset inside step t is global_step + t), so a
+        following `step` or `rollout` continues like the loop would. Terrain, pushes (`set_external_wrench`: the first
+        sub-step of every env step), per-proxy friction and foot forces act step by step. `mapping="lane"` is refused by
+        the library. Nothing synchronises: the call can be captured in a hipGraph like `step`. The persistent reward / done
+        buffers of `step` are not written."""
+        a = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions))
+        if a.dim() != 3 or a.shape[0] < 1:
+            raise ValueError("rollout actions must be [T, num_envs, n_joints] float32 with T >= 1, got %s" % (tuple(a.shape),))
+        if not self._robot_set:
+            raise Exception("BaseBulletEnv::_reset: must call set_robot and set_scene first")   # env_bases.py:68-69
+        if tuple(a.shape[1:]) != (self.num_envs, self.n_joints):
+            raise ValueError("rollout actions must be [T, num_envs = %d, n_joints = %d], got %s"
+                             % (self.num_envs, self.n_joints, tuple(a.shape)))
+        a = a.to(device=self.device, dtype=torch.float32).contiguous()
+        T, N, dev = int(a.shape[0]), self.num_envs, self.device
+        idx = rollout_obs_steps(T, obs_every)
+        reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+        done = torch.empty(T, N, dtype=torch.bool, device=dev)
+        r5 = torch.empty(T, N, 5, dtype=torch.float32, device=dev) if rewards5 else None
+        obs = self._obs if int(obs_every) == 0 else torch.empty(len(idx), N, self.obs_dim, dtype=torch.float32, device=dev)
+        self._params_c.step_index = self.global_step
+        rc = self._lib.mg_walker_rollout(self._topo, self._models_c, self._params_c, N, self._state_c, T, int(obs_every),
+                                         _lib.ptr(a), _lib.ptr(obs), _lib.ptr(reward), _lib.ptr(r5), _lib.ptr(done),
+                                         _lib.current_stream(dev))
+        _lib.check(rc, "mg_walker_rollout")
+        self.global_step += T
+        info = {"steps": self.steps, "obs_steps": idx}
+        if rewards5:
+            info["rewards"] = r5
+        return obs, reward, done, info
+
     def set_external_wrench(self, wrench):
-        """A push on the base body during the first sub-step of every following launch (mg_walker_params.ext_wrench): float64
+        """A push on the base body during the first sub-step of every following env step (mg_walker_params.ext_wrench): float64
         `[6, num_envs]` — force and application point in the base body frame — or None. The tensor is read at launch time, so
         it can be rewritten in place between steps (also inside a captured hipGraph)."""
         if wrench is not None:
