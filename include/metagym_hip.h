@@ -216,6 +216,66 @@ typedef struct mg_quadrotor_fold {
 
 int mg_quadrotor_plan_fold(const mg_quadrotor_plan *plan, mg_quadrotor_fold *out);
 
+/* Task table: per-env simulator parameters in one launch (domain randomisation, meta-learning). Every key of the
+ * reference's config.json is per task: precision, quality, inertia, drag, gravity_center, thrust (CT, Mm, Jm, RA, phi),
+ * propeller, fail (velocity, w, range), electric (min / max voltage) and the init_velocity / init_angular_velocity
+ * blocks (base and noisy). dt, nt, task, healthy_reward, the map and its offsets stay in the one mg_quadrotor_config
+ * of the call (its per-task fields are ignored there, but it must be a valid config), and so do seed and env_id_base of
+ * the auto-reset block. Because precision is per task, so is the sub-step count int(dt / precision).
+ *
+ * A table is n_tasks folded rows in DEVICE memory (mg_quadrotor_tasks_row_bytes() each, 16-byte aligned, the caller
+ * uploads them) and one int32 task id per env. mg_quadrotor_tasks_fold is host only: it validates one config exactly as
+ * every other entry point does (precision in [1e-8, dt], ...) and writes its row, with the same arithmetic the uniform
+ * path folds its constants with. One lane per env reads its row once per launch into registers and runs the arithmetic
+ * of the generic uniform step on it: a table of identical rows reproduces the uniform env bit for bit (fused auto-reset
+ * included: the Philox key stays (seed, env_id_base + e, episode), the row supplies base and noisy).
+ * Additive entry points; MG_ABI_VERSION is unchanged. */
+typedef struct mg_quadrotor_tasks {
+    const void *rows_d;                /* DEVICE n_tasks rows written by mg_quadrotor_tasks_fold */
+    const int32_t *task_id_d;          /* DEVICE int32 [n_envs], each in [0, n_tasks): validated by the caller (the
+                                          kernel clamps an id into the table, it never reads outside it) */
+    const float *velocity_targets_d;   /* DEVICE f32 [n_tasks][nt][3], VELOCITY_CONTROL only: row v holds the
+                                          trajectory of mg_quadrotor_velocity_targets for task v's config */
+    int32_t n_tasks;
+    int32_t all_simple;                /* 1: every row reports simple (mg_quadrotor_task_fold), the launch may take the
+                                          specialisation for the stock structure; 0 is always right */
+    double dt;                         /* the dt the rows were folded with; must equal cfg->dt of the call */
+} mg_quadrotor_tasks;
+
+/* What a row holds, for tests and diagnostics (mg_quadrotor_tasks_describe, host only). */
+typedef struct mg_quadrotor_task_fold {
+    float inertia_inv[9];              /* float32 inverse of the float32 inertia (quadrotorsim.py:64) */
+    float lm[4];                       /* |prop_coord[i]| */
+    float fail_range_sq32;             /* largest float32 sum of squares that passes the range test */
+    float prec32;
+    int32_t times;                     /* int(dt / precision) */
+    int32_t simple;                    /* the stock structure: diagonal drag / inertia, zero centre of gravity, CT[2] == 0,
+                                          propellers in the z = 0 plane */
+    double precision, half_dt2, dt;    /* half_dt2 = 0.5 * precision * precision */
+    float init_velocity[3], init_angular_velocity[3];
+    double init_velocity_noisy, init_angular_velocity_noisy;
+} mg_quadrotor_task_fold;
+
+int32_t mg_quadrotor_tasks_row_bytes(void);
+/* ar == NULL: a zero init-noise block. seed and env_id_base of `ar` are not per task and are ignored here. */
+int mg_quadrotor_tasks_fold(const mg_quadrotor_config *cfg, const mg_quadrotor_autoreset *ar, void *row_out_host);
+int mg_quadrotor_tasks_describe(const void *row_host, mg_quadrotor_task_fold *out);
+
+/* n_steps >= 1 env steps of a heterogeneous batch in one launch: arguments, layouts and semantics of
+ * mg_quadrotor_rollout (ar == NULL) / mg_quadrotor_step_autoreset (ar != NULL: only seed and env_id_base are read,
+ * base and noisy come from the env's row). Nothing depends on a step counter and nothing is copied synchronously:
+ * the call is hipGraph-capturable as it stands. */
+int mg_quadrotor_tasks_step(const mg_quadrotor_config *cfg, const mg_quadrotor_tasks *tasks, int32_t n_envs,
+                            int32_t n_steps, const mg_quadrotor_state *state, const mg_quadrotor_autoreset *ar,
+                            const float *action, float *obs, float *reward, double *reward64, uint8_t *done,
+                            uint8_t *failed, void *stream);
+
+/* mg_quadrotor_reset for a table: the reset observation reads shared fields only, except the three target entries of
+ * VELOCITY_CONTROL, which come from the env's own trajectory. */
+int mg_quadrotor_tasks_reset(const mg_quadrotor_config *cfg, const mg_quadrotor_tasks *tasks, int32_t n_envs,
+                             const mg_quadrotor_state *state, const uint8_t *mask, const double *init_vel,
+                             const double *init_omega, float *obs, void *stream);
+
 /* ========================================================================================
  * MetaMaze — replaces metagym/metamaze/envs/{maze_base,maze_2d,maze_discrete_3d,
  *            maze_continuous_3d,dynamics,ray_caster_utils}.py for N envs

@@ -60,6 +60,21 @@ class QuadrotorFold(C.Structure):
                 ("fail_range_sq32", C.c_float), ("fail_velocity", C.c_double), ("fail_w", C.c_double)]
 
 
+class QuadrotorTasks(C.Structure):
+    """mg_quadrotor_tasks (device pointers)"""
+    _fields_ = [("rows_d", C.c_void_p), ("task_id_d", C.c_void_p), ("velocity_targets_d", C.c_void_p),
+                ("n_tasks", C.c_int32), ("all_simple", C.c_int32), ("dt", C.c_double)]
+
+
+class QuadrotorTaskFold(C.Structure):
+    """mg_quadrotor_task_fold: what one row of a task table holds (mg_quadrotor_tasks_describe)"""
+    _fields_ = [("inertia_inv", C.c_float * 9), ("lm", C.c_float * 4), ("fail_range_sq32", C.c_float),
+                ("prec32", C.c_float), ("times", C.c_int32), ("simple", C.c_int32),
+                ("precision", C.c_double), ("half_dt2", C.c_double), ("dt", C.c_double),
+                ("init_velocity", C.c_float * 3), ("init_angular_velocity", C.c_float * 3),
+                ("init_velocity_noisy", C.c_double), ("init_angular_velocity_noisy", C.c_double)]
+
+
 class MazeTasks(C.Structure):
     """mg_maze_tasks (device pointers)"""
     _fields_ = [("n", C.c_int32), ("n_tasks", C.c_int32), ("start", C.c_void_p), ("goal", C.c_void_p),
@@ -284,6 +299,14 @@ SIGNATURES = {
                                          C.POINTER(QuadrotorAutoReset), C.c_int32, C.POINTER(QuadrotorState)]),
     "mg_quadrotor_plan_step": (C.c_int, [C.POINTER(QuadrotorPlan), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "mg_quadrotor_plan_fold": (C.c_int, [C.POINTER(QuadrotorPlan), C.POINTER(QuadrotorFold)]),
+    "mg_quadrotor_tasks_row_bytes": (C.c_int32, []),
+    "mg_quadrotor_tasks_fold": (C.c_int, [C.POINTER(QuadrotorConfig), C.POINTER(QuadrotorAutoReset), _P]),
+    "mg_quadrotor_tasks_describe": (C.c_int, [_P, C.POINTER(QuadrotorTaskFold)]),
+    "mg_quadrotor_tasks_step": (C.c_int, [C.POINTER(QuadrotorConfig), C.POINTER(QuadrotorTasks), C.c_int32, C.c_int32,
+                                          C.POINTER(QuadrotorState), C.POINTER(QuadrotorAutoReset),
+                                          _P, _P, _P, _P, _P, _P, _P]),
+    "mg_quadrotor_tasks_reset": (C.c_int, [C.POINTER(QuadrotorConfig), C.POINTER(QuadrotorTasks), C.c_int32,
+                                           C.POINTER(QuadrotorState), _P, _P, _P, _P, _P]),
     "mg_quadrotor_rollout": (C.c_int, [C.POINTER(QuadrotorConfig), C.c_int32, C.c_int32,
                                        C.POINTER(QuadrotorState), _P, _P, _P, _P, _P, _P, _P]),
     "mg_maze_view_tables": (C.c_int, [C.c_int32, C.c_double, C.c_double, _P, _P]),

@@ -1359,6 +1359,9 @@ int check_state(const mg_quadrotor_state *s) {
     return MG_OK;
 }
 
+#ifdef MG_QUADROTOR_CORE_ONLY   // quadrotor_tasks.hip takes the device functions and the folding above, and none of what follows
+}  // namespace
+#else
 // What mg_quadrotor_plan holds (caller-owned host memory, see the header): everything a step launch needs
 // except the per-call I/O pointers.
 struct Plan {
@@ -1584,3 +1587,4 @@ extern "C" int mg_quadrotor_plan_step(const mg_quadrotor_plan *plan, int32_t n_s
     if (p->magic != PLAN_MAGIC) return mg::set_error(MG_ERR_BAD_CONFIG, "mg_quadrotor_plan is not initialised");
     return launch_plan(p, n_steps, action, obs, reward, reward64, done, failed, stream);
 }
+#endif   // MG_QUADROTOR_CORE_ONLY

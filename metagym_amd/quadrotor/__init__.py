@@ -1,4 +1,5 @@
 """Batched Quadrotor (mirrors metagym/quadrotor/__init__.py: id 'quadrotor-v0')."""
 from .env import Quadrotor, DEFAULT_SIM_CONFIG
+from .tasks import QuadrotorTaskTable, sample_tasks
 
-__all__ = ["Quadrotor", "DEFAULT_SIM_CONFIG"]
+__all__ = ["Quadrotor", "DEFAULT_SIM_CONFIG", "QuadrotorTaskTable", "sample_tasks"]

@@ -231,6 +231,10 @@ class Quadrotor(object):
         self._plan_step = self._lib.mg_quadrotor_plan_step
         self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         self._action_shape = (N, 4)
+        # task table (set_task): None = the uniform plan above
+        self.task_table = None
+        self.task_ids = None
+        self._tasks = self._task_ids_host = self._tasks_keep = self.task_velocity_targets = None
 
     # ------------------------------------------------------------------ reference API
     def reset(self, mask=None, seed=None, init_velocity=None, init_angular_velocity=None):
@@ -243,6 +247,15 @@ class Quadrotor(object):
         N, dev = self.num_envs, self.device
         if seed is not None:
             self.np_random = np.random.RandomState(seed)
+        if self.task_table is not None and (init_velocity is None or init_angular_velocity is None):
+            # the same four draws per env, scaled by its own row's init_* block
+            u = self.np_random.random_sample((N, 4, 3))
+            tb, ids = self.task_table, self._task_ids_host
+            v = tb.init_velocity[ids] + (tb.init_velocity_noisy[ids][:, None] * u[:, 1]) * ((u[:, 0] > 0.5).astype(int) * 2 - 1.0)
+            w = tb.init_angular_velocity[ids] + (tb.init_angular_velocity_noisy[ids][:, None] * u[:, 3]) * \
+                ((u[:, 2] > 0.5).astype(int) * 2 - 1.0)
+            init_velocity = v if init_velocity is None else init_velocity
+            init_angular_velocity = w if init_angular_velocity is None else init_angular_velocity
         if init_velocity is None or init_angular_velocity is None:
             u = self.np_random.random_sample((N, 4, 3))
             cv, cw = self.sim_config.get("init_velocity"), self.sim_config.get("init_angular_velocity")
@@ -263,10 +276,73 @@ class Quadrotor(object):
         if mask is not None:
             m = torch.as_tensor(mask, device=dev).to(torch.uint8).contiguous()
             assert m.shape == (N,)
+        if self._tasks is not None:
+            rc = self._lib.mg_quadrotor_tasks_reset(self._cfg, self._tasks, N, self._state, _lib.ptr(m), _lib.ptr(iv),
+                                                    _lib.ptr(iw), _lib.ptr(self._obs), _lib.current_stream(dev))
+            _lib.check(rc, "mg_quadrotor_tasks_reset")
+            return self._obs
         rc = self._lib.mg_quadrotor_reset(self._cfg, N, self._state, _lib.ptr(m), _lib.ptr(iv), _lib.ptr(iw),
                                           _lib.ptr(self._obs), _lib.current_stream(dev))
         _lib.check(rc, "mg_quadrotor_reset")
         return self._obs
+
+    # ------------------------------------------------------------------ task table
+    def set_task(self, table, task_ids=None):
+        """Give every env its own simulator parameters: env e flies row `task_ids[e]` of `table` (a
+        `QuadrotorTaskTable`; `task_ids=None` = e % V). step(), rollout(), reset() and the fused auto-reset then run the
+        table launch (mg_quadrotor_tasks_step): one lane per env, each with its own row, sub-step count included.
+        dt, nt, task, healthy_reward, the map, seed and env_id_base stay those of the env. `set_task(None)` returns to
+        the uniform plan. A refused call (an id out of range, a wrong shape, a row the library rejects for this env's
+        dt) raises and leaves the env as it was."""
+        if table is None:
+            self.task_table = self.task_ids = self._tasks = self._task_ids_host = None
+            self._tasks_keep = self.task_velocity_targets = None
+            self._plan_step = self._lib.mg_quadrotor_plan_step
+            self._plan_ref = C.byref(self._plan)
+            return
+        N, dev, V = self.num_envs, self.device, len(table)
+        if task_ids is None:
+            ids_h = np.arange(N, dtype=np.int64) % V
+        else:
+            ids_h = task_ids.detach().cpu().numpy() if isinstance(task_ids, torch.Tensor) else np.asarray(task_ids)
+            if ids_h.shape != (N,):
+                raise ValueError("task_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
+            if ids_h.dtype.kind not in "iu":
+                raise ValueError("task_ids must be integers, got %s" % ids_h.dtype)
+            if N and (int(ids_h.min()) < 0 or int(ids_h.max()) >= V):
+                raise ValueError("task_ids must be in [0, %d)" % V)
+        rows_h, all_simple = table.fold(self.dt)                      # MetaGymHipError for a row the library rejects
+        targets = None
+        if self.task == "velocity_control":
+            # one trajectory per task, each as the uniform env of that config rolls its own (same seed, its own voltages)
+            nt = int(self.nt)
+            targets = torch.zeros(V, nt, 3, dtype=torch.float32, device=dev)
+            for v in range(V):
+                cfg_v = table.config_struct(v, self.dt, nt, self.task, self.healthy_reward)
+                rs = np.random.RandomState(self.seed_value)
+                acts = np.stack([rs.uniform(low=cfg_v.min_voltage, high=cfg_v.max_voltage, size=4).astype(np.float32)
+                                 for _ in range(nt)])
+                a_t = torch.from_numpy(acts).to(dev).contiguous()
+                rc = self._lib.mg_quadrotor_velocity_targets(cfg_v, nt, _lib.ptr(a_t), _lib.ptr(targets[v]),
+                                                             _lib.current_stream(dev))
+                _lib.check(rc, "mg_quadrotor_velocity_targets (task %d)" % v)
+        rows_d = table.device_rows(dev, self.dt)
+        ids_d = torch.as_tensor(ids_h.astype(np.int32), device=dev).contiguous()
+        tasks = _lib.QuadrotorTasks()
+        tasks.rows_d, tasks.task_id_d = rows_d.data_ptr(), ids_d.data_ptr()
+        tasks.velocity_targets_d = targets.data_ptr() if targets is not None else None
+        tasks.n_tasks, tasks.all_simple, tasks.dt = V, int(all_simple), float(self.dt)
+        # everything is built: commit. step() / rollout() call self._plan_step(self._plan_ref, T, ...): bind the table
+        # launch behind the same call, so the stepping code is the same with and without a table.
+        self.task_table, self.task_ids, self._tasks = table, ids_d, tasks
+        self._task_ids_host = ids_h.astype(np.int64)
+        self._tasks_keep = (rows_d, targets)
+        self.task_velocity_targets = targets          # [V, nt, 3] (velocity_control), else None
+        fn, cfg, st, ar = self._lib.mg_quadrotor_tasks_step, self._cfg, self._state, (self._ar if self.auto_reset else None)
+
+        def tasks_step(_plan_ref, n_steps, action, obs, reward, reward64, done, failed, stream):
+            return fn(cfg, tasks, N, n_steps, st, ar, action, obs, reward, reward64, done, failed, stream)
+        self._plan_step = tasks_step
 
     def step(self, action):
         """action: float32 [N,4] tensor (or array-like). Returns (obs [N,16] f32, reward [N] f32,
@@ -330,9 +406,21 @@ class Quadrotor(object):
         (the Philox stream position of each env) and the host RandomState behind reset()."""
         sd = {k: getattr(self, k).clone() for k in self._STATE_KEYS}
         sd["np_random"] = self.np_random.get_state()
+        if self.task_table is not None:
+            sd["task_ids"] = self.task_ids.clone()
         return sd
 
     def load_state_dict(self, sd):
+        if "task_ids" in sd:
+            if self.task_table is None:
+                raise ValueError("state_dict carries task_ids, but this env has no task table: call set_task first")
+            ids_h = torch.as_tensor(sd["task_ids"]).detach().cpu().numpy()
+            if ids_h.shape != (self.num_envs,) or ids_h.dtype.kind not in "iu" or \
+                    (ids_h.size and (int(ids_h.min()) < 0 or int(ids_h.max()) >= len(self.task_table))):
+                raise ValueError("state_dict['task_ids'] must be %d integers in [0, %d)" % (self.num_envs, len(self.task_table)))
+            # in place: the id tensor's address is a launch argument (a captured hipGraph keeps it)
+            self.task_ids.copy_(torch.as_tensor(ids_h.astype(np.int32)))
+            self._task_ids_host = ids_h.astype(np.int64)
         for k in self._STATE_KEYS:
             if k == "episode" and k not in sd:
                 continue                           # checkpoints of ABI 1 carried no counters
