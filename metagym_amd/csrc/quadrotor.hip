@@ -609,10 +609,62 @@ __global__ void quadrotor_targets_kernel(QuadK k, int nt, const float *actions, 
 
 // ---- SoA load / store ----------------------------------------------------------------------------
 
-// Every output of a step is written once and next read by a later launch (or by the caller), never by
-// this one: streaming (nontemporal) stores let the bytes leave through the fabric as they are issued
-// instead of waiting in L2 for the end-of-kernel write-back (-2..3 % at 65 536 envs).
-template <typename T> __device__ __forceinline__ void st_stream(T *p, T v) { __builtin_nontemporal_store(v, p); }
+// Cache policy of a global access = the aux operand of a buffer instruction (gfx950 cache bits: sc0 = 1, nt = 2, sc1 = 16).
+// plain and nt leave the written line dirty in the XCD's L2 until the end-of-kernel write-back (nt is a streaming hint in
+// a write-back cache, not a write-through); sc1 and sc0 sc1 write through as the store is issued; sc1 nt is both.
+constexpr int AUX_PLAIN = 0, AUX_NT = 2, AUX_SC1 = 16, AUX_SC0_SC1 = 17, AUX_SC1_NT = 18;
+constexpr bool st_policy_ok(int aux) {
+    return aux == AUX_PLAIN || aux == AUX_NT || aux == AUX_SC1 || aux == AUX_SC0_SC1 || aux == AUX_SC1_NT;
+}
+constexpr bool ld_policy_ok(int aux) { return aux == AUX_PLAIN || aux == AUX_NT; }
+// Every output of a step is written once and next read by a later launch (or by the caller), never by this one. Its
+// stores fall into three classes, each with a policy of its own, per addressing path: MG_QUAD_ST_* for the buffer path
+// (BUF: the one-wave form at the headline size), MG_QUAD_STP_* for the pointer path (st_stream: STEP_STOCK, the generic
+// forms, the reset and the task-table kernels, and the one-wave form past 2^31 bytes). -D values are the aux numbers
+// above, for A/B builds (scripts/build_variant.sh NAME REV -DMG_QUAD_ST_STATE=16 ...).
+//   STATE   pos / vel / omega / propw / rot / ct (store_lane) and the rare episode store: read back by the next launch
+//   OBS     the [n][16] observation rows (store_obs_wave)
+//   SCALAR  reward, reward64, done, failed: 1 to 8 bytes per env
+// MG_QUAD_LD_STATE is the policy of the state loads (plain or nt).
+// Measured on MI355X at 65 536 envs (profiles/r12/trace_gaps.jsonl, bench_ab_eager400.jsonl; EXPERIMENTS.md round 12),
+// kernel duration plus the gap to the next launch, 4 040 launches each: nt 12.02 / 12.05 us (two runs), plain 12.16,
+// sc1 on the state alone 11.75, on state and observation 11.50, on all three classes 11.32, sc0 sc1 11.43, sc1 nt 11.47.
+// nt was 1 % better than plain and still left the lines dirty for the end-of-kernel write-back; written through, they
+// leave under the arithmetic of the waves that entered later. WRITE_SIZE per launch is the same to 0.05 % (byte-wide
+// done / failed included: profiles/r12/pmc_traffic.jsonl). So the buffer path ships sc1 for every class. nt state loads on
+// top of it gained nothing (11.32 against 11.70, profiles/r12/timelines.jsonl: load phase 1.08 us either way) and stay plain.
+// The pointer path keeps nt: its kernels are the parent's instruction for instruction (profiles/r12/isa_quadrotor.txt).
+#ifndef MG_QUAD_ST_STATE
+#define MG_QUAD_ST_STATE 16
+#endif
+#ifndef MG_QUAD_ST_OBS
+#define MG_QUAD_ST_OBS 16
+#endif
+#ifndef MG_QUAD_ST_SCALAR
+#define MG_QUAD_ST_SCALAR 16
+#endif
+#ifndef MG_QUAD_STP_STATE
+#define MG_QUAD_STP_STATE 2
+#endif
+#ifndef MG_QUAD_STP_OBS
+#define MG_QUAD_STP_OBS 2
+#endif
+#ifndef MG_QUAD_STP_SCALAR
+#define MG_QUAD_STP_SCALAR 2
+#endif
+#ifndef MG_QUAD_LD_STATE
+#define MG_QUAD_LD_STATE 0
+#endif
+static_assert(st_policy_ok(MG_QUAD_ST_STATE) && st_policy_ok(MG_QUAD_ST_OBS) && st_policy_ok(MG_QUAD_ST_SCALAR) &&
+              st_policy_ok(MG_QUAD_STP_STATE) && st_policy_ok(MG_QUAD_STP_OBS) && st_policy_ok(MG_QUAD_STP_SCALAR),
+              "store policy: 0 plain, 2 nt, 16 sc1, 17 sc0 sc1, 18 sc1 nt");
+static_assert(ld_policy_ok(MG_QUAD_LD_STATE), "load policy: 0 plain, 2 nt");
+enum StoreClass { ST_STATE = 0, ST_OBS = 1, ST_SCALAR = 2 };
+template <bool BUF, int CLS> constexpr int st_policy() {
+    return CLS == ST_STATE ? (BUF ? MG_QUAD_ST_STATE : MG_QUAD_STP_STATE)
+         : CLS == ST_OBS   ? (BUF ? MG_QUAD_ST_OBS : MG_QUAD_STP_OBS)
+                           : (BUF ? MG_QUAD_ST_SCALAR : MG_QUAD_STP_SCALAR);
+}
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
@@ -621,32 +673,63 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 // offset e*sizeof(T) is one VGPR per element size and the component's c*n*sizeof(T) a scalar soffset, so an access
 // costs no VALU; a flat address is two 64-bit VALU ops per access (v_mad_u64_u32 / v_lshl_add_u64), ~120 per step
 // on the prologue's and the epilogue's critical paths. Offsets are 32-bit: launch_plan picks BUF only when the
-// largest array of the launch (the [n][16] observation of a one-step launch) spans less than 2^31 bytes. Stores carry
-// aux = 2 (nt), the streaming policy of st_stream.
-constexpr int AUX_NT = 2;
+// largest array of the launch (the [n][16] observation of a one-step launch) spans less than 2^31 bytes. The policy of
+// a store is a bit of the instruction (aux), so changing it moves no address arithmetic: sc1 (write-through) by default,
+// which measured 0.7 us per step better than nt at 65 536 envs (see MG_QUAD_ST_* above; profiles/r12/trace_gaps.jsonl).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void *base, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)bytes, 0x00020000);
 }
-template <typename T> __device__ __forceinline__ T buf_ld(__amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so) {
-    if constexpr (sizeof(T) == 4) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
-    else if constexpr (sizeof(T) == 8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
-    else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0));
+template <typename T, int AUX = AUX_PLAIN> __device__ __forceinline__ T buf_ld(__amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so) {
+    static_assert(ld_policy_ok(AUX), "load policy");
+    if constexpr (sizeof(T) == 4) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, AUX));
+    else if constexpr (sizeof(T) == 8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, AUX));
+    else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, AUX));
 }
 template <int AUX, typename T> __device__ __forceinline__ void buf_st(T v, __amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so) {
+    static_assert(st_policy_ok(AUX), "store policy");
     if constexpr (sizeof(T) == 1) __builtin_amdgcn_raw_buffer_store_b8(__builtin_bit_cast(uint8_t, v), r, vo, so, AUX);
     else if constexpr (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, vo, so, AUX);
     else if constexpr (sizeof(T) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), r, vo, so, AUX);
     else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, vo, so, AUX);
 }
-template <bool BUF, typename T> __device__ __forceinline__ T ld_soa(const T *a, int comps, int n, int c, int e) {
-    if (!BUF) return a[(size_t)c * n + e];
-    return buf_ld<T>(rsrc_of(a, (uint32_t)comps * (uint32_t)n * sizeof(T)), (uint32_t)e * sizeof(T),
-                     (uint32_t)c * (uint32_t)n * sizeof(T));
+// The pointer path. plain is a C++ store and nt the nontemporal builtin. sc1 on up to 8 bytes is a relaxed agent-scope
+// atomic store (global_store ... sc1). Everything else (the 16-byte observation quads, sc0 sc1, sc1 nt) has no builtin on
+// a flat pointer and goes out as a buffer store: the resource starts at the address of the wave's first active lane and
+// the lane's offset is its distance from it. Every caller stores one element or one observation quad per lane at
+// addresses that rise with the lane, at most 64 bytes apart (one observation row), so a wave spans at most 4 KiB.
+template <typename T> struct same_size_uint;
+template <> struct same_size_uint<uint8_t> { typedef uint8_t type; };
+template <> struct same_size_uint<int> { typedef uint32_t type; };
+template <> struct same_size_uint<uint32_t> { typedef uint32_t type; };
+template <> struct same_size_uint<float> { typedef uint32_t type; };
+template <> struct same_size_uint<double> { typedef uint64_t type; };
+template <int AUX, typename T> __device__ __forceinline__ void st_stream(T *p, T v) {
+    static_assert(st_policy_ok(AUX), "store policy");
+    if constexpr (AUX == AUX_NT) __builtin_nontemporal_store(v, p);
+    else if constexpr (AUX == AUX_PLAIN) *p = v;
+    else if constexpr (AUX == AUX_SC1 && sizeof(T) <= 8) {
+        typedef typename same_size_uint<T>::type U;
+        __hip_atomic_store(reinterpret_cast<U *>(p), __builtin_bit_cast(U, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        const uint64_t a = (uint64_t)p;
+        // (the builtin returns int: through uint32_t, or a low word with bit 31 set would sign-extend into the high word)
+        const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32)) << 32) |
+                              (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
+        buf_st<AUX>(v, rsrc_of((const void *)base, mg::WAVE * OBS_DIM * 4), (uint32_t)(a - base), 0);
+    }
 }
-template <bool BUF, typename T> __device__ __forceinline__ void st_soa(T *a, int comps, int n, int c, int e, T v) {
-    if (!BUF) return st_stream(&a[(size_t)c * n + e], v);
-    buf_st<AUX_NT>(v, rsrc_of(a, (uint32_t)comps * (uint32_t)n * sizeof(T)), (uint32_t)e * sizeof(T),
-                   (uint32_t)c * (uint32_t)n * sizeof(T));
+template <bool BUF, int AUX = AUX_PLAIN, typename T> __device__ __forceinline__ T ld_soa(const T *a, int comps, int n, int c, int e) {
+    if (!BUF) {
+        if constexpr (AUX == AUX_NT) return __builtin_nontemporal_load(&a[(size_t)c * n + e]);
+        else return a[(size_t)c * n + e];
+    }
+    return buf_ld<T, AUX>(rsrc_of(a, (uint32_t)comps * (uint32_t)n * sizeof(T)), (uint32_t)e * sizeof(T),
+                          (uint32_t)c * (uint32_t)n * sizeof(T));
+}
+template <bool BUF, int CLS, typename T> __device__ __forceinline__ void st_soa(T *a, int comps, int n, int c, int e, T v) {
+    if (!BUF) return st_stream<st_policy<false, CLS>()>(&a[(size_t)c * n + e], v);
+    buf_st<st_policy<true, CLS>()>(v, rsrc_of(a, (uint32_t)comps * (uint32_t)n * sizeof(T)), (uint32_t)e * sizeof(T),
+                                   (uint32_t)c * (uint32_t)n * sizeof(T));
 }
 
 // ROT_FIRST: issue rot, vel and omega ahead of the rest, in the order the derived values below consume them
@@ -654,27 +737,27 @@ template <bool ROT_FIRST = false, bool BUF = false>
 __device__ __forceinline__ void load_state(const mg_quadrotor_state &st, int n, int e, Lane &s, int &ct) {
     if (ROT_FIRST) {
 #pragma unroll
-        for (int c = 0; c < 9; ++c) s.R[c] = ld_soa<BUF>(st.rot, 9, n, c, e);
+        for (int c = 0; c < 9; ++c) s.R[c] = ld_soa<BUF, MG_QUAD_LD_STATE>(st.rot, 9, n, c, e);
     }
     if (!ROT_FIRST) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) s.p[c] = ld_soa<BUF>(st.pos, 3, n, c, e);
+        for (int c = 0; c < 3; ++c) s.p[c] = ld_soa<BUF, MG_QUAD_LD_STATE>(st.pos, 3, n, c, e);
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) s.v[c] = ld_soa<BUF>(st.vel, 3, n, c, e);
+    for (int c = 0; c < 3; ++c) s.v[c] = ld_soa<BUF, MG_QUAD_LD_STATE>(st.vel, 3, n, c, e);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) s.w[c] = ld_soa<BUF>(st.omega, 3, n, c, e);
+    for (int c = 0; c < 3; ++c) s.w[c] = ld_soa<BUF, MG_QUAD_LD_STATE>(st.omega, 3, n, c, e);
     if (ROT_FIRST) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) s.p[c] = ld_soa<BUF>(st.pos, 3, n, c, e);
+        for (int c = 0; c < 3; ++c) s.p[c] = ld_soa<BUF, MG_QUAD_LD_STATE>(st.pos, 3, n, c, e);
     }
 #pragma unroll
-    for (int c = 0; c < 4; ++c) s.pw[c] = ld_soa<BUF>(st.propw, 4, n, c, e);
+    for (int c = 0; c < 4; ++c) s.pw[c] = ld_soa<BUF, MG_QUAD_LD_STATE>(st.propw, 4, n, c, e);
     if (!ROT_FIRST) {
 #pragma unroll
-        for (int c = 0; c < 9; ++c) s.R[c] = ld_soa<BUF>(st.rot, 9, n, c, e);
+        for (int c = 0; c < 9; ++c) s.R[c] = ld_soa<BUF, MG_QUAD_LD_STATE>(st.rot, 9, n, c, e);
     }
-    ct = ld_soa<BUF>(st.ct, 1, n, 0, e);
+    ct = ld_soa<BUF, MG_QUAD_LD_STATE>(st.ct, 1, n, 0, e);
 }
 
 __device__ __forceinline__ void derive_lane(Lane &s) {   // the library's sqrt and division
@@ -691,21 +774,22 @@ __device__ __forceinline__ void load_lane(const mg_quadrotor_state &st, int n, i
 template <bool BUF = false>
 __device__ __forceinline__ void store_lane(const mg_quadrotor_state &st, int n, int e, const Lane &s, int ct) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) st_soa<BUF>(st.pos, 3, n, c, e, s.p[c]);
+    for (int c = 0; c < 3; ++c) st_soa<BUF, ST_STATE>(st.pos, 3, n, c, e, s.p[c]);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) st_soa<BUF>(st.vel, 3, n, c, e, s.v[c]);
+    for (int c = 0; c < 3; ++c) st_soa<BUF, ST_STATE>(st.vel, 3, n, c, e, s.v[c]);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) st_soa<BUF>(st.omega, 3, n, c, e, s.w[c]);
+    for (int c = 0; c < 3; ++c) st_soa<BUF, ST_STATE>(st.omega, 3, n, c, e, s.w[c]);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) st_soa<BUF>(st.propw, 4, n, c, e, s.pw[c]);
+    for (int c = 0; c < 4; ++c) st_soa<BUF, ST_STATE>(st.propw, 4, n, c, e, s.pw[c]);
 #pragma unroll
-    for (int c = 0; c < 9; ++c) st_soa<BUF>(st.rot, 9, n, c, e, s.R[c]);
-    st_soa<BUF>(st.ct, 1, n, 0, e, ct);
+    for (int c = 0; c < 9; ++c) st_soa<BUF, ST_STATE>(st.rot, 9, n, c, e, s.R[c]);
+    st_soa<BUF, ST_STATE>(st.ct, 1, n, 0, e, ct);
 }
 
 // Transpose the wave's 64 x 16 observation rows through LDS and store them as 4 coalesced
 // dwordx4 sweeps (each wave instruction writes 1 KiB contiguous). Rows are padded to 17 floats so
-// the per-lane row writes hit distinct banks; a partial last wave falls back to per-row stores.
+// the per-lane row writes hit distinct banks; a partial last wave falls back to per-row stores, which take the OBS
+// policy without its nt bit (a row per lane, 16 bytes at a time, is not a stream: under nt they are plain stores).
 // BUF (STEP_STOCK_SHADOW, where obs_dim is 16): the same stores through a buffer resource over the step's n rows.
 template <bool BUF = false>
 __device__ __forceinline__ void store_obs_wave(float *tile, const float *obs, float *out, int n, int e, int obs_dim) {
@@ -729,8 +813,8 @@ __device__ __forceinline__ void store_obs_wave(float *tile, const float *obs, fl
             const int row = q >> 2, col = (q & 3) * 4;
             const float *src = &tile[row * (OBS_DIM + 1) + col];
             const v4f v{src[0], src[1], src[2], src[3]};
-            if (BUF) buf_st<AUX_NT>(v, r, (uint32_t)(wave_base * OBS_DIM + 4 * lane) * 4 + j * (mg::WAVE * 16), 0);
-            else st_stream(reinterpret_cast<v4f *>(dst + q), v);
+            if (BUF) buf_st<st_policy<true, ST_OBS>()>(v, r, (uint32_t)(wave_base * OBS_DIM + 4 * lane) * 4 + j * (mg::WAVE * 16), 0);
+            else st_stream<st_policy<false, ST_OBS>()>(reinterpret_cast<v4f *>(dst + q), v);
         }
         __builtin_amdgcn_wave_barrier();
     } else if (e < n) {
@@ -739,8 +823,9 @@ __device__ __forceinline__ void store_obs_wave(float *tile, const float *obs, fl
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const v4f v{obs[4 * j], obs[4 * j + 1], obs[4 * j + 2], obs[4 * j + 3]};
-            if (BUF) buf_st<0>(v, r, (uint32_t)e * (OBS_DIM * 4) + j * 16, 0);
-            else dst[j] = make_float4(v.x, v.y, v.z, v.w);
+            if (BUF) buf_st<st_policy<true, ST_OBS>() & ~AUX_NT>(v, r, (uint32_t)e * (OBS_DIM * 4) + j * 16, 0);
+            else if constexpr ((st_policy<false, ST_OBS>() & ~AUX_NT) == AUX_PLAIN) dst[j] = make_float4(v.x, v.y, v.z, v.w);
+            else st_stream<st_policy<false, ST_OBS>() & ~AUX_NT>(reinterpret_cast<v4f *>(dst + j), v);
         }
     }
 }
@@ -1104,7 +1189,7 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         if (t == n_steps - 1 && live) {
             const mg_quadrotor_state &ste = *(const mg_quadrotor_state *)&kae->st;
             store_lane<BUF>(ste, n, e, s, ct);
-            if (episode != episode_in) st_soa<BUF>(ste.episode, 1, n, 0, e, episode);   // rare: only lanes that restarted
+            if (episode != episode_in) st_soa<BUF, ST_STATE>(ste.episode, 1, n, 0, e, episode);   // rare: only lanes that restarted
         }
         MG_PHASE_STAMP(3);   // state stores issued
         __builtin_amdgcn_sched_barrier(0);   // pure arithmetic would otherwise be hoisted above the stores
@@ -1115,15 +1200,15 @@ __global__ __launch_bounds__(BLOCK) void quadrotor_step_kernel(QuadK k, mg_quadr
         MG_PHASE_STAMP(4);   // obs stores issued
         if (live) {
             if (BUF) {   // one-step form: off == 0
-                if (ioe.reward) st_soa<true>(ioe.reward + off, 1, n, 0, e, (float)reward);
-                if (ioe.reward64) st_soa<true>(ioe.reward64 + off, 1, n, 0, e, reward);
-                st_soa<true>(ioe.done + off, 1, n, 0, e, (uint8_t)done);
-                if (ioe.failed) st_soa<true>(ioe.failed + off, 1, n, 0, e, (uint8_t)fail);
+                if (ioe.reward) st_soa<true, ST_SCALAR>(ioe.reward + off, 1, n, 0, e, (float)reward);
+                if (ioe.reward64) st_soa<true, ST_SCALAR>(ioe.reward64 + off, 1, n, 0, e, reward);
+                st_soa<true, ST_SCALAR>(ioe.done + off, 1, n, 0, e, (uint8_t)done);
+                if (ioe.failed) st_soa<true, ST_SCALAR>(ioe.failed + off, 1, n, 0, e, (uint8_t)fail);
             } else {
-                if (ioe.reward) st_stream(&ioe.reward[off + e], (float)reward);
-                if (ioe.reward64) st_stream(&ioe.reward64[off + e], reward);
-                st_stream(&ioe.done[off + e], (uint8_t)done);
-                if (ioe.failed) st_stream(&ioe.failed[off + e], (uint8_t)fail);
+                if (ioe.reward) st_stream<st_policy<false, ST_SCALAR>()>(&ioe.reward[off + e], (float)reward);
+                if (ioe.reward64) st_stream<st_policy<false, ST_SCALAR>()>(&ioe.reward64[off + e], reward);
+                st_stream<st_policy<false, ST_SCALAR>()>(&ioe.done[off + e], (uint8_t)done);
+                if (ioe.failed) st_stream<st_policy<false, ST_SCALAR>()>(&ioe.failed[off + e], (uint8_t)fail);
             }
         }
     }

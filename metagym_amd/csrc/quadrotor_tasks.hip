@@ -171,10 +171,10 @@ __global__ __launch_bounds__(TASKS_BLOCK) void quadrotor_tasks_step_kernel(QuadK
         if (vel_task) { obs[16] = kl.vtargets[3 * tn]; obs[17] = kl.vtargets[3 * tn + 1]; obs[18] = kl.vtargets[3 * tn + 2]; }
         store_obs_wave(tile, obs, io.obs + off * k.obs_dim, n, e, k.obs_dim);
         if (live) {
-            if (io.reward) st_stream(&io.reward[off + e], (float)reward);
-            if (io.reward64) st_stream(&io.reward64[off + e], reward);
-            st_stream(&io.done[off + e], (uint8_t)done);
-            if (io.failed) st_stream(&io.failed[off + e], (uint8_t)fail);
+            if (io.reward) st_stream<st_policy<false, ST_SCALAR>()>(&io.reward[off + e], (float)reward);
+            if (io.reward64) st_stream<st_policy<false, ST_SCALAR>()>(&io.reward64[off + e], reward);
+            st_stream<st_policy<false, ST_SCALAR>()>(&io.done[off + e], (uint8_t)done);
+            if (io.failed) st_stream<st_policy<false, ST_SCALAR>()>(&io.failed[off + e], (uint8_t)fail);
         }
     }
 }
