@@ -276,6 +276,79 @@ int mg_quadrotor_tasks_reset(const mg_quadrotor_config *cfg, const mg_quadrotor_
                              const mg_quadrotor_state *state, const uint8_t *mask, const double *init_vel,
                              const double *init_omega, float *obs, void *stream);
 
+/* Closed-loop rollouts: n_steps env steps in one launch with the controller inside it. Every env evaluates its
+ * own small MLP on the observation of the state it holds and steps with the result; the state stays in registers for the
+ * whole launch and, unless records are asked for, nothing of size n_steps x n_envs is written.
+ *
+ * The policy arithmetic is defined exactly. x[D] is the env's float32 observation (D = 16, or 19 for VELOCITY_CONTROL),
+ * H the number of hidden ReLU units, 0 <= H <= 256 (H = 0: a linear policy). Every operation is float32, rounded once,
+ * never fused, in this order:
+ *   H > 0:  for j in 0..H-1:  z = b1[j];  for i in 0..D-1: z = z + w1[j][i] * x[i];   h[j] = (z > 0) ? z : 0
+ *           for k in 0..3:    a[k] = b2[k];  for j in 0..H-1: a[k] = a[k] + w2[k][j] * h[j]
+ *   H = 0:  for k in 0..3:    a[k] = b[k];   for i in 0..D-1: a[k] = a[k] + w[k][i] * x[i]
+ * a[0..3] are the step's four voltages, unclamped (the step clamps them like any caller's action). x at a step is the
+ * observation row the previous step (or the reset) returned for the env: the kernel derives it from the state, so the
+ * call is right after the state arrays were rewritten by the caller. (One corner: VELOCITY_CONTROL without a fused
+ * reset, at the first step of a launch that follows an episode end. The step that ended the episode showed the target of
+ * the step counter before it was cleared; the launch derives the target from the stored, cleared counter, as
+ * mg_quadrotor_reset does.)
+ *
+ * Packed parameters, DEVICE f32, 16-byte aligned, mg_quadrotor_policy_param_count(H, D) floats per policy, policy p at
+ * params_d + p * count:
+ *   H > 0:  [0..3] b2[0..3]; then one record of 24 floats per hidden unit j, at 4 + 24 j:
+ *           [0..D-1] w1[j][0..D-1], [D] b1[j], zeros up to [19], [20..23] w2[0..3][j]        (count = 4 + 24 H)
+ *   H = 0:  [0..3] b[0..3]; then [4 + 4 i + k] = w[k][i]                                     (count = 4 + 4 D)
+ * so one 16-byte read feeds the four accumulators. Parameters must be finite and are read-only for the launch.
+ * Additive entry points; MG_ABI_VERSION is unchanged. */
+typedef struct mg_quadrotor_policy {
+    const float *params_d;             /* DEVICE f32 [n_policies][count] */
+    const int32_t *policy_id_d;        /* DEVICE int32 [n_envs], each in [0, n_policies): validated by the caller (the
+                                          kernel clamps an id, it never reads outside the parameters). A wave whose envs
+                                          all hold one id stages that policy in LDS; the result does not depend on it */
+    int32_t n_policies, hidden, obs_dim;
+} mg_quadrotor_policy;
+
+/* Optional per-step records, [n_steps][n_envs][...] each; NULL = not written. With all six NULL (or records == NULL) the
+ * launch stores nothing inside its step loop. actions holds the unclamped a[0..3]. */
+typedef struct mg_quadrotor_policy_records {
+    float *actions;      /* [n_steps][n][4] */
+    float *obs;          /* [n_steps][n][obs_dim] */
+    float *reward;       /* [n_steps][n] */
+    double *reward64;    /* [n_steps][n] */
+    uint8_t *done;       /* [n_steps][n] */
+    uint8_t *failed;     /* [n_steps][n] */
+} mg_quadrotor_policy_records;
+
+/* The last step's outputs, with mg_quadrotor_step's layouts and meanings: pass the buffers step() writes, and a
+ * following step or host-side policy loop continues coherently. obs and done are required. */
+typedef struct mg_quadrotor_policy_last {
+    float *obs;          /* [n][obs_dim] */
+    float *reward;       /* [n] or NULL */
+    double *reward64;    /* [n] or NULL */
+    uint8_t *done;       /* [n] */
+    uint8_t *failed;     /* [n] or NULL */
+} mg_quadrotor_policy_last;
+
+/* Floats per packed policy (host only); a negative error code for hidden outside [0, 256] or obs_dim not 16 / 19. */
+int32_t mg_quadrotor_policy_param_count(int32_t hidden, int32_t obs_dim);
+
+/* tasks == NULL: the uniform env of cfg; else the task table launch (one row per env, as mg_quadrotor_tasks_step).
+ * ar == NULL: no fused reset; else as mg_quadrotor_step_autoreset (with a table only seed and env_id_base are read).
+ * Per env, written once at the end of the launch:
+ *   ret_total   f64 [n]   the n_steps float64 rewards, added in step order from 0.0
+ *   ret_episode f64 [n]   the rewards up to and including the first done
+ *   episode_len i32 [n]   the number of steps added into ret_episode (n_steps if the env was never done)
+ * The final state and episode counters are stored as mg_quadrotor_rollout stores them.
+ * Refused on the host, before any device call: NULL required pointers (MG_ERR_NULL_POINTER); n_envs, n_steps or
+ * n_policies < 1, hidden outside [0, 256] (MG_ERR_BAD_SIZE); obs_dim not the task's, params_d not 16-byte aligned, and
+ * whatever the step entry points refuse about cfg and tasks (MG_ERR_BAD_CONFIG). Asynchronous on `stream`; no argument
+ * depends on a step counter, so the call is hipGraph-capturable as it stands. */
+int mg_quadrotor_policy_rollout(const mg_quadrotor_config *cfg, const mg_quadrotor_tasks *tasks, int32_t n_envs,
+                                int32_t n_steps, const mg_quadrotor_state *state, const mg_quadrotor_autoreset *ar,
+                                const mg_quadrotor_policy *policy, double *ret_total, double *ret_episode,
+                                int32_t *episode_len, const mg_quadrotor_policy_records *records,
+                                const mg_quadrotor_policy_last *last, void *stream);
+
 /* ========================================================================================
  * MetaMaze — replaces metagym/metamaze/envs/{maze_base,maze_2d,maze_discrete_3d,
  *            maze_continuous_3d,dynamics,ray_caster_utils}.py for N envs

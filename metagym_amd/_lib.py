@@ -75,6 +75,24 @@ class QuadrotorTaskFold(C.Structure):
                 ("init_velocity_noisy", C.c_double), ("init_angular_velocity_noisy", C.c_double)]
 
 
+class QuadrotorPolicyDesc(C.Structure):
+    """mg_quadrotor_policy (device pointers)"""
+    _fields_ = [("params_d", C.c_void_p), ("policy_id_d", C.c_void_p), ("n_policies", C.c_int32), ("hidden", C.c_int32),
+                ("obs_dim", C.c_int32)]
+
+
+class QuadrotorPolicyRecords(C.Structure):
+    """mg_quadrotor_policy_records (device pointers, each may be NULL)"""
+    _fields_ = [("actions", C.c_void_p), ("obs", C.c_void_p), ("reward", C.c_void_p), ("reward64", C.c_void_p),
+                ("done", C.c_void_p), ("failed", C.c_void_p)]
+
+
+class QuadrotorPolicyLast(C.Structure):
+    """mg_quadrotor_policy_last (device pointers)"""
+    _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("reward64", C.c_void_p), ("done", C.c_void_p),
+                ("failed", C.c_void_p)]
+
+
 class MazeTasks(C.Structure):
     """mg_maze_tasks (device pointers)"""
     _fields_ = [("n", C.c_int32), ("n_tasks", C.c_int32), ("start", C.c_void_p), ("goal", C.c_void_p),
@@ -307,6 +325,11 @@ SIGNATURES = {
                                           _P, _P, _P, _P, _P, _P, _P]),
     "mg_quadrotor_tasks_reset": (C.c_int, [C.POINTER(QuadrotorConfig), C.POINTER(QuadrotorTasks), C.c_int32,
                                            C.POINTER(QuadrotorState), _P, _P, _P, _P, _P]),
+    "mg_quadrotor_policy_param_count": (C.c_int32, [C.c_int32, C.c_int32]),
+    "mg_quadrotor_policy_rollout": (C.c_int, [C.POINTER(QuadrotorConfig), C.POINTER(QuadrotorTasks), C.c_int32, C.c_int32,
+                                              C.POINTER(QuadrotorState), C.POINTER(QuadrotorAutoReset),
+                                              C.POINTER(QuadrotorPolicyDesc), _P, _P, _P, C.POINTER(QuadrotorPolicyRecords),
+                                              C.POINTER(QuadrotorPolicyLast), _P]),
     "mg_quadrotor_rollout": (C.c_int, [C.POINTER(QuadrotorConfig), C.c_int32, C.c_int32,
                                        C.POINTER(QuadrotorState), _P, _P, _P, _P, _P, _P, _P]),
     "mg_maze_view_tables": (C.c_int, [C.c_int32, C.c_double, C.c_double, _P, _P]),

@@ -25,12 +25,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 # v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 (the dynamic VALU count does not change, round 4), and the step kernel is 1 % slower:
 # five alternating A/B pairs of `bench.py --steps 400 --launch eager`, 14.61 / 14.59 / 14.60 / 14.51 us per step with, 14.41 / 14.49 /
 # 14.52 / 14.37 without (round 6). Bit-identical results (packed float32 arithmetic is IEEE per lane); the GPU parity tests run on it.
-# quadrotor_tasks.hip is built from the same device functions (it includes quadrotor.hip) and takes the same flag.
-FILE_FLAGS = {"quadrotor.hip": ["-fno-slp-vectorize"], "quadrotor_tasks.hip": ["-fno-slp-vectorize"]}
+# quadrotor_tasks.hip and quadrotor_policy.hip are built from the same device functions (they include quadrotor.hip) and take the same flag.
+FILE_FLAGS = {"quadrotor.hip": ["-fno-slp-vectorize"], "quadrotor_tasks.hip": ["-fno-slp-vectorize"],
+              "quadrotor_policy.hip": ["-fno-slp-vectorize"]}
 
 
 # Sources a .hip includes besides the headers: its object is stale when one of them is newer.
-FILE_DEPS = {"quadrotor_tasks.hip": ["quadrotor.hip"]}
+FILE_DEPS = {"quadrotor_tasks.hip": ["quadrotor.hip"], "quadrotor_policy.hip": ["quadrotor.hip"]}
 
 
 def sources():

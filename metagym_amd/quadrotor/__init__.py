@@ -1,5 +1,6 @@
 """Batched Quadrotor (mirrors metagym/quadrotor/__init__.py: id 'quadrotor-v0')."""
 from .env import Quadrotor, DEFAULT_SIM_CONFIG
+from .policy import PolicyRollout, QuadrotorPolicy
 from .tasks import QuadrotorTaskTable, sample_tasks
 
-__all__ = ["Quadrotor", "DEFAULT_SIM_CONFIG", "QuadrotorTaskTable", "sample_tasks"]
+__all__ = ["Quadrotor", "DEFAULT_SIM_CONFIG", "QuadrotorTaskTable", "sample_tasks", "QuadrotorPolicy", "PolicyRollout"]

@@ -387,6 +387,73 @@ class Quadrotor(object):
         self._last_rollout_reward64 = rew64
         return obs, rew, done, failed
 
+    def rollout_policy(self, policy, steps, policy_ids=None, record=False):
+        """`steps` closed-loop env steps in one launch: env e evaluates policy `policy_ids[e]` of `policy` (a
+        `QuadrotorPolicy`; `policy_ids=None` = e % P) on its own observation inside the kernel and steps with the result.
+        Works on the uniform env and after `set_task(table)`, with and without `auto_reset`, for all three tasks.
+        Returns a `PolicyRollout`: ret_total, ret_episode, episode_len always; actions, obs, reward, reward64, done, failed
+        [steps, N, ...] when `record=True`, else None (the launch then writes nothing per step). The last step's outputs go
+        into the buffers step() returns, so a following step() continues coherently. Nothing synchronises when
+        `policy_ids` is None, a host array, or the device tensor of the previous call; any other device tensor is read
+        back once to validate it. A refused call (an id out of range, a policy for another observation width) raises and
+        leaves the env as it was."""
+        from .policy import PolicyRollout, QuadrotorPolicy
+        if not isinstance(policy, QuadrotorPolicy):
+            raise TypeError("policy must be a QuadrotorPolicy, got %s" % type(policy).__name__)
+        T, N, dev, P = int(steps), self.num_envs, self.device, policy.num_policies
+        if T < 1:
+            raise ValueError("steps must be at least 1, got %d" % T)
+        if policy.obs_dim != self.obs_dim:
+            raise ValueError("the policy reads %d observation entries, task %r has %d" % (policy.obs_dim, self.task, self.obs_dim))
+        ids_d = self._policy_ids(policy_ids, P)
+        params = policy.to(dev)
+        desc = _lib.QuadrotorPolicyDesc(params.data_ptr(), ids_d.data_ptr(), P, policy.hidden, policy.obs_dim)
+        res = PolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
+                            torch.empty(N, dtype=torch.int32, device=dev))
+        records = None
+        if record:
+            res.actions = torch.empty(T, N, 4, dtype=torch.float32, device=dev)
+            res.obs = torch.empty(T, N, self.obs_dim, dtype=torch.float32, device=dev)
+            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+            res.reward64 = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+            res.failed = torch.empty(T, N, dtype=torch.uint8, device=dev)
+            records = _lib.QuadrotorPolicyRecords(*[t.data_ptr() for t in (res.actions, res.obs, res.reward, res.reward64,
+                                                                            res.done, res.failed)])
+        last = _lib.QuadrotorPolicyLast(*self._out_ptrs)
+        rc = self._lib.mg_quadrotor_policy_rollout(self._cfg, self._tasks, N, T, self._state,
+                                                   self._ar if self.auto_reset else None, desc, _lib.ptr(res.ret_total),
+                                                   _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len), records, last,
+                                                   _raw_stream(self._dev_index))
+        _lib.check(rc, "mg_quadrotor_policy_rollout")
+        return res
+
+    def _policy_ids(self, policy_ids, P):
+        """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a
+        hipGraph capture after its warm-up) neither uploads nor reads back."""
+        N = self.num_envs
+        keep = getattr(self, "_policy_ids_keep", None)
+        if isinstance(policy_ids, torch.Tensor) and keep is not None and keep[0] == P and policy_ids is keep[2] and \
+                policy_ids._version == keep[3]:
+            return keep[1]
+        if policy_ids is None:
+            ids_h = np.arange(N, dtype=np.int64) % P
+        else:
+            ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
+            if ids_h.shape != (N,):
+                raise ValueError("policy_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
+            if ids_h.dtype.kind not in "iu":
+                raise ValueError("policy_ids must be integers, got %s" % ids_h.dtype)
+            if N and (int(ids_h.min()) < 0 or int(ids_h.max()) >= P):
+                raise ValueError("policy_ids must be in [0, %d)" % P)
+        ids_h = ids_h.astype(np.int32)
+        if keep is not None and keep[0] == P and keep[4] == ids_h.tobytes():
+            return keep[1]
+        ids_d = torch.as_tensor(ids_h, device=self.device).contiguous()
+        src = policy_ids if isinstance(policy_ids, torch.Tensor) else None
+        self._policy_ids_keep = (P, ids_d, src, src._version if src is not None else None, ids_h.tobytes())
+        return ids_d
+
     def render(self, mode="human"):
         raise NotImplementedError("rendering is out of scope for the batched engine (SURVEY.md §2 row 5)")
 
