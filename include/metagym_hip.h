@@ -797,6 +797,51 @@ int mg_walker_rollout(const mg_walker_topology *topo, const mg_walker_models *mo
                       int32_t n_envs, const mg_walker_state *state, int32_t n_steps, int32_t obs_every,
                       const float *actions, float *obs, float *reward, float *rewards5, uint8_t *done, void *stream);
 
+/* mg_walker_policy_rollout — mg_walker_rollout with the controller inside the launch: env e evaluates policy policy_id_d[e] on
+ * the observation row its last step produced and steps with the result, n_steps times in ONE launch. P policies with one hidden
+ * ReLU layer (or none), defined exactly: x[D] is the observation (D = 8 + 2 nj + nf), A = nj outputs, H hidden units
+ * (0 <= H <= 256). Every operation is float32, rounded once, never fused, in this order:
+ *     H > 0:  for j in 0..H-1:  z = b1[j];  for i in 0..D-1: z = z + w1[j][i] * x[i];   h[j] = (z > 0) ? z : 0
+ *             for k in 0..A-1:  a[k] = b2[k];  for j in 0..H-1: a[k] = a[k] + w2[k][j] * h[j]
+ *     H = 0:  for k in 0..A-1:  a[k] = b[k];   for i in 0..D-1: a[k] = a[k] + w[k][i] * x[i]
+ * `a` goes into the step unclamped; the step clamps it to [-1, 1] like any caller's action. Given the actions, the physics,
+ * rewards, dones, auto-resets and the end state are those of mg_walker_rollout on the same actions, bit for bit.
+ * Packed layout of ONE policy (params_d holds n_policies of them back to back, mg_walker_policy_param_count floats each), chosen
+ * so that the lanes of a wave read consecutive floats (hidden unit j on lane j % 64, output k on lane k):
+ *     H > 0:  b1[H], w1 input-major [D][H] (w1[j][i] at H + i H + j), b2[A], w2 hidden-major [H][A] (w2[k][j] at H + D H + A + j A + k)
+ *     H = 0:  b[A], w input-major [D][A] (w[k][i] at A + i A + k)
+ * policy_id_d: int32 [N], validated by the caller (the kernel clamps an id into [0, n_policies)). */
+typedef struct mg_walker_policy {
+    const float *params_d;
+    const int32_t *policy_id_d;
+    int32_t n_policies, hidden, obs_dim, n_act;
+} mg_walker_policy;
+
+/* Floats of one packed policy. Host only. A negative error code for hidden outside [0, 256], n_act outside
+ * [1, MG_WALKER_MAX_JOINTS] or obs_dim outside [1, 8 + 2 MG_WALKER_MAX_JOINTS + MG_WALKER_MAX_FEET]. */
+int32_t mg_walker_policy_param_count(int32_t hidden, int32_t obs_dim, int32_t n_act);
+
+/*   obs0 f32 [N][D]: x of step 0 — the observation the last reset / step / rollout returned. (The kernel cannot re-derive it: a
+ *   row carries the feet flags of the step before, which mg_walker_state does not hold.) From step 1 on x is the row the
+ *   previous step produced — with auto_reset the first observation of the new episode where one ended. obs0 may be the same
+ *   buffer as obs when obs_every == 0: an env's row is read before it is written, and by no other env.
+ *   obs f32 [K][N][D] and obs_every: as in mg_walker_rollout.
+ *   ret_total f64 [N]: the n_steps float32 rewards widened and added in step order. ret_episode f64 [N]: the rewards up to and
+ *   including the first done. episode_len i32 [N]: steps added into ret_episode; n_steps if the env was never done.
+ *   Optional per-step records, each may be NULL: actions f32 [n_steps][N][nj] (unclamped), reward f32 [n_steps][N], rewards5 f32
+ *   [n_steps][N][5], done u8 [n_steps][N]. With all four NULL the step loop stores nothing of size n_steps x N.
+ * Refused on the host before anything is launched: everything mg_walker_rollout refuses (the lane mapping, actuation != 0,
+ * substep_log, n_steps < 1, obs_every < 0, the descriptors, the terrain, the wave mapping's limits); a NULL policy, params_d,
+ * policy_id_d, obs0, obs, ret_total, ret_episode or episode_len (MG_ERR_NULL_POINTER); n_policies < 1 or hidden outside
+ * [0, 256] (MG_ERR_BAD_SIZE); obs_dim or n_act that are not the topology's (MG_ERR_BAD_CONFIG). Dynamic LDS: the step's, plus
+ * (D + H) floats rounded up to 16 bytes. Nothing is allocated and nothing synchronises (stream capture works as for the step).
+ * Additive entry points; MG_ABI_VERSION is unchanged. */
+int mg_walker_policy_rollout(const mg_walker_topology *topo, const mg_walker_models *models, const mg_walker_params *prm,
+                             int32_t n_envs, const mg_walker_state *state, int32_t n_steps, int32_t obs_every,
+                             const mg_walker_policy *policy, const float *obs0, float *obs, double *ret_total,
+                             double *ret_episode, int32_t *episode_len, float *actions, float *reward, float *rewards5,
+                             uint8_t *done, void *stream);
+
 /* ========================================================================================
  * Quadrupedal (Unitree A1) — the ACTUATION path of metagym/quadrupedal/robots/minitaur.py + a1.py +
  * laikago_motor.py for N robots: everything `Minitaur._StepInternal` (minitaur.py:232-238) does on either side of

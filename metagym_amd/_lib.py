@@ -187,6 +187,12 @@ class WalkerState(C.Structure):
                 ("feet_contact", C.c_void_p), ("steps", C.c_void_p), ("bad_contacts", C.c_void_p), ("foot_force", C.c_void_p)]
 
 
+class WalkerPolicyDesc(C.Structure):
+    """mg_walker_policy (device pointers)"""
+    _fields_ = [("params_d", C.c_void_p), ("policy_id_d", C.c_void_p), ("n_policies", C.c_int32), ("hidden", C.c_int32),
+                ("obs_dim", C.c_int32), ("n_act", C.c_int32)]
+
+
 A1_NUM_MOTORS, A1_OBS_DIM = 12, 43
 A1_MODE_POSITION, A1_MODE_TORQUE, A1_MODE_HYBRID = 1, 2, 3
 
@@ -353,6 +359,10 @@ SIGNATURES = {
                                  C.c_int32, C.POINTER(WalkerState), _P, _P, _P, _P, _P, _P]),
     "mg_walker_rollout": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
                                     C.c_int32, C.POINTER(WalkerState), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mg_walker_policy_param_count": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "mg_walker_policy_rollout": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
+                                           C.c_int32, C.POINTER(WalkerState), C.c_int32, C.c_int32, C.POINTER(WalkerPolicyDesc),
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mg_a1_apply_action": (C.c_int, [C.POINTER(A1ActuatorConfig), C.c_int32, C.POINTER(A1ActuatorState), _P, _P,
                                      C.c_double, _P, _P]),
     "mg_a1_receive_observation": (C.c_int, [C.POINTER(A1ActuatorConfig), C.c_int32, C.POINTER(A1ActuatorState),

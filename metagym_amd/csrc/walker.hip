@@ -549,6 +549,7 @@ __device__ void observe(const mg_walker_topology &tp, const ModelRef &m, const m
     for (int f = 0; f < nf; ++f) obs[8 + 2 * nj + f] = clip5(feet_contact[f]);
 }
 
+#ifndef MG_WALKER_POLICY_ONLY   // walker_policy.hip takes the wave kernel's text and wave_plan, and none of the other kernels
 __global__ __launch_bounds__(WK_BLOCK) void walker_step_kernel(mg_walker_topology tp, mg_walker_models ms,
                                                                mg_walker_params prm, mg_walker_state st, int n_envs,
                                                                const float *action, float *obs, float *reward,
@@ -655,6 +656,7 @@ __global__ __launch_bounds__(WK_BLOCK) void walker_reset_kernel(mg_walker_topolo
         for (int i = 0; i < obs_dim; ++i) obs[(size_t)e * obs_dim + i] = ob[i];
     store_env(st, n_envs, nj, e, s);
 }
+#endif   // MG_WALKER_POLICY_ONLY
 
 
 // ======================================================================================================
@@ -1842,6 +1844,40 @@ __device__ __forceinline__ void wave_substep(const mg_walker_topology &tp, const
     }
 }
 
+// The policy of include/metagym_hip.h (mg_walker_policy) for one env on one wave: p is the env's packed parameter block in
+// global memory, x[D] the observation row and h[H] the hidden layer in LDS. Hidden unit u runs on lane u % 64 (up to four units
+// per lane, one after the other), output k on lane k; every sum is one lane's sequential loop in the order of the definition
+// (no cross-lane reduction: it would change the association), one rounding per operation: contraction, which this file turns
+// on for the physics, is off here as it is for the actuators above, so no a + w * x is fused. Reads of x and h are same-address
+// broadcasts; the weights are laid out input-major, so the lanes of one iteration read consecutive floats. H = 0 is the output
+// layer applied to x. Lanes >= A return 0.
+#pragma clang fp contract(off)
+__device__ __forceinline__ float wave_policy_action(const float *__restrict__ p, int H, int D, int A, const float *x, float *h, int lane) {
+    WSYNC();                                  // x was written by other lanes: calc_state of the step before, or the copy of obs0
+    const float *in = x;
+    int n_in = D;
+    if (H > 0) {
+        for (int u = lane; u < H; u += WV) {
+            float z = p[u];
+            const float *w = p + H + u;
+            for (int i = 0; i < D; ++i) z = z + w[(size_t)i * H] * x[i];
+            h[u] = (z > 0.0f) ? z : 0.0f;     // a NaN or negative pre-activation gives +0.0
+        }
+        WSYNC();
+        p += (size_t)H + (size_t)D * H;
+        in = h;
+        n_in = H;
+    }
+    float a = 0.0f;
+    if (lane < A) {
+        a = p[lane];
+        const float *w = p + A + lane;
+        for (int j = 0; j < n_in; ++j) a = a + w[(size_t)j * A] * in[j];
+    }
+    return a;
+}
+#pragma clang fp contract(fast)
+
 // Waves per SIMD: two (<= 256 VGPRs) everywhere but in the tuned ant kernel — its 10.7 KB of LDS let 12 envs reside per CU, so
 // it is held to 168 VGPRs for a third wave (its 46 spilled VGPRs all sit after the sub-step loop): 0.402 -> 0.365 ms. The A1's
 // 18-slot kernel at 168 VGPRs spills inside the loop and loses (2.31 -> 2.45 ms); the humanoid is LDS-bound at 8 per CU.
@@ -1859,23 +1895,40 @@ template <int NMAX, class SH> constexpr bool WAVE_MODEL_IN_LDS = SH::nb == 0 && 
 // instantiation spilled 41 - 95 VGPRs to scratch (the sub-step loop's invariants stay live through calc_state once the code
 // jumps back), and a rollout may not use more scratch than its step (profiles/walker/rollout_resources.txt; DESIGN.md §3.12
 // has what that costs at large N).
-template <int NMAX, class SH, bool ROLL> constexpr int WAVE_WAVES_PER_EU =
+template <int NMAX, class SH, int ROLL> constexpr int WAVE_WAVES_PER_EU =
     ROLL ? ((NMAX <= 14 && SH::nb != 0) ? 2 : 1)
          : ((NMAX <= 14 && SH::nb != 0) ? 3 : (SH::nb != 0 ? MG_WALKER_HUM_WAVES : ((NMAX == 18 && SH::nj == 12) ? MG_WALKER_A1_WAVES : 2)));
-// ROLL = false: one env step per launch, walker_step_wave_kernel<NMAX, SH>. ROLL = true: the rollout form of the same code
-// (mg_walker_rollout), roll.n_steps env steps with the robot resident in LDS — the topology tables, the model tail, the
+// ROLL = WAVE_STEP: one env step per launch, walker_step_wave_kernel<NMAX, SH>. ROLL = WAVE_ROLLOUT: the rollout form of the same
+// code (mg_walker_rollout), roll.n_steps env steps with the robot resident in LDS — the topology tables, the model tail, the
 // per-robot lookups and the state load / store are paid once, the step loop holds what one step does. There `action`,
 // `reward`, `rewards5` and `done` are [n_steps] rows of the step's arrays (they advance by one row per step) and `obs` holds one
 // [N][obs_dim] slice per recorded step (roll.obs_every: the rule above mg_maze2d_rollout in the header).
-template <bool ROLL> struct WaveRoll { };
-template <> struct WaveRoll<true> { int n_steps, obs_every; };
-template <int NMAX, class SH, bool ROLL = false>
+// ROLL = WAVE_POLICY: the rollout form with the action computed in the launch (mg_walker_policy_rollout, instantiated in
+// walker_policy.hip): where the rollout loads action[e * nj + lane], the wave evaluates the env's policy on the observation row
+// it produced last, a copy of which it keeps in LDS behind the slab and the model tail (x[obs_dim], then h[hidden]). `action` is
+// unused; `reward`, `rewards5`, `done` and roll.actions are optional records, and lane 0 adds up the env's returns.
+constexpr int WAVE_STEP = 0, WAVE_ROLLOUT = 1, WAVE_POLICY = 2;
+template <int ROLL> struct WaveRoll { };
+template <> struct WaveRoll<WAVE_ROLLOUT> { int n_steps, obs_every; };
+template <> struct WaveRoll<WAVE_POLICY> {
+    int n_steps, obs_every;
+    const float *params;          // [n_policies][count]: the packed layout of include/metagym_hip.h (mg_walker_policy)
+    const int32_t *policy_id;     // [N]
+    int n_policies, hidden, count;
+    const float *obs0;            // [N][obs_dim]: x of step 0
+    float *actions;               // [n_steps][N][nj] or null
+    double *ret_total, *ret_episode;
+    int32_t *episode_len;
+};
+// bytes of the policy form's LDS tail: x[obs_dim] and h[hidden]
+__host__ __device__ inline size_t wave_policy_tail_bytes(int obs_dim, int hidden) { return (((size_t)obs_dim + hidden) * sizeof(float) + 15) & ~size_t(15); }
+template <int NMAX, class SH, int ROLL = WAVE_STEP>
 __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu(WAVE_WAVES_PER_EU<NMAX, SH, ROLL>))) void walker_step_wave_kernel(mg_walker_topology tp, mg_walker_models ms,
                                                               mg_walker_params prm, mg_walker_state st, int n_envs,
                                                               int plan_rows, int plan_scan, const float *action, float *obs,
                                                               float *reward, float *rewards5, uint8_t *done, WaveRoll<ROLL> roll) {
     int n_steps = 1, obs_every = 0;
-    if constexpr (ROLL) { n_steps = roll.n_steps; obs_every = roll.obs_every; }
+    if constexpr (ROLL != WAVE_STEP) { n_steps = roll.n_steps; obs_every = roll.obs_every; }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int e = mg::env_of_block(blockIdx.x, n_envs);
     int lane = threadIdx.x;       // (written again only by the rollout form, at the head of every env step)
@@ -2017,10 +2070,31 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu(WAVE_WAVES_P
     // barrier, so what a step derives from the lane or loads (addresses, model constants, tables) is derived in that step, as
     // in a launch of its own, and is not carried in registers across the whole rollout.
     int t = 0;
+    // the policy form: the env's parameter block (one id per wave, clamped like a task id), the LDS tail behind the slab and the
+    // model tail (x[obs_dim], h[hidden]; wave_plan sizes it), x of step 0, and the returns lane 0 adds up
+    const float *pol = nullptr;
+    float *xl = nullptr, *hl = nullptr;
+    double ret_total = 0.0, ret_episode = 0.0;
+    int episode_len = 0;
+    bool episode_over = false;
+    if constexpr (ROLL == WAVE_POLICY) {
+        int pid = __builtin_amdgcn_readfirstlane(roll.policy_id[e]);
+        pid = pid < 0 ? 0 : (pid >= roll.n_policies ? roll.n_policies - 1 : pid);
+        pol = roll.params + (size_t)pid * (size_t)roll.count;
+        xl = reinterpret_cast<float *>(slab + plan.tail + (WAVE_MODEL_IN_LDS<NMAX, SH> ? wave_model_doubles(nb, nj) * sizeof(double) : 0));
+        hl = xl + obs_dim;
+        for (int i = lane; i < obs_dim; i += WV) xl[i] = roll.obs0[(size_t)e * obs_dim + i];     // (read before any row of obs is written)
+    }
 env_step:
     if (ROLL) {
         asm volatile("" : "+v"(lane) : : "memory");
-        if (lane < nj) L.tau[lane] = motor_torque(prm, m.motor()[lane], action[(size_t)e * nj + lane]);
+        if constexpr (ROLL == WAVE_POLICY) {
+            const float a = wave_policy_action(pol, roll.hidden, obs_dim, nj, xl, hl, lane);
+            if (lane < nj) {
+                if (roll.actions != nullptr) roll.actions[((size_t)t * n_envs + e) * nj + lane] = a;
+                L.tau[lane] = motor_torque(prm, m.motor()[lane], a);
+            }
+        } else if (lane < nj) L.tau[lane] = motor_torque(prm, m.motor()[lane], action[(size_t)e * nj + lane]);
         touch[0] = 0ull; touch[1] = 0ull;
         WSYNC();
     }
@@ -2062,6 +2136,7 @@ env_step:
         }
         at_limit = __popcll(__ballot(lim));
         if (lane < nj) { ob[8 + 2 * lane] = clip5(jp); ob[9 + 2 * lane] = clip5(jv); }
+        if (ROLL == WAVE_POLICY && lane < nj) { xl[8 + 2 * lane] = clip5(jp); xl[9 + 2 * lane] = clip5(jv); }     // the next step's x
         bool finite = isfinite(jp) && isfinite(jv);
         // feet in contact now: one ballot per foot over the proxies (lane = proxy), not a loop over the proxies per foot
         float cnow = 0.0f;
@@ -2077,10 +2152,12 @@ env_step:
         if (lane < nf) {
             if (after_reset) {
                 ob[8 + 2 * nj + lane] = 0.0f;
+                if (ROLL == WAVE_POLICY) xl[8 + 2 * nj + lane] = 0.0f;
                 st.feet_contact[(size_t)lane * n_envs + e] = 0.0f;
             } else {
                 const float prev = st.feet_contact[(size_t)lane * n_envs + e];
                 ob[8 + 2 * nj + lane] = clip5(prev);
+                if (ROLL == WAVE_POLICY) xl[8 + 2 * nj + lane] = clip5(prev);
                 st.feet_contact[(size_t)lane * n_envs + e] = cnow;
             }
         }
@@ -2109,6 +2186,8 @@ env_step:
             head[3] = clip5((float)(0.3 * vx)); head[4] = clip5((float)(0.3 * vy)); head[5] = clip5((float)(0.3 * vz));
             head[6] = clip5((float)roll); head[7] = clip5((float)pitch);
             for (int i = 0; i < 8; ++i) { ob[i] = head[i]; finite = finite && isfinite(head[i]); }
+            if (ROLL == WAVE_POLICY)
+                for (int i = 0; i < 8; ++i) xl[i] = head[i];
         }
         all_finite = __all(finite);
     };
@@ -2137,13 +2216,22 @@ env_step:
             st.potential[e] = pot;
             const int steps = st.steps[e] + 1;
             st.steps[e] = steps;
-            reward[e] = (float)(alive + progress + 0.0 + limit_cost + 0.0);
+            const float rew = (float)(alive + progress + 0.0 + limit_cost + 0.0);
+            if (ROLL != WAVE_POLICY || reward != nullptr) reward[e] = rew;       // (the policy form's per-step records are optional)
             if (rewards5) {
                 float *r5 = rewards5 + (size_t)e * 5;
                 r5[0] = (float)alive; r5[1] = (float)progress; r5[2] = 0.0f; r5[3] = (float)limit_cost; r5[4] = 0.0f;
             }
             ended = (alive < 0) || !all_finite || (steps >= prm.max_steps);
-            done[e] = (uint8_t)ended;
+            if (ROLL != WAVE_POLICY || done != nullptr) done[e] = (uint8_t)ended;
+            if (ROLL == WAVE_POLICY) {      // the returns: the float32 rewards widened and added in step order; the episode's stops with the first done
+                ret_total = ret_total + (double)rew;
+                if (!episode_over) {
+                    ret_episode = ret_episode + (double)rew;
+                    episode_len += 1;
+                    episode_over = ended != 0;
+                }
+            }
         }
         ended = __builtin_amdgcn_readfirstlane(ended);
         if (!(prm.auto_reset && ended)) break;
@@ -2163,9 +2251,21 @@ env_step:
         WSYNC();
     }
     if (ROLL && ++t < n_steps) {       // row t of the per-step arrays
-        action += (size_t)n_envs * nj; reward += n_envs; done += n_envs;
+        if (ROLL == WAVE_POLICY) {
+            if (reward != nullptr) reward += n_envs;
+            if (done != nullptr) done += n_envs;
+        } else {
+            action += (size_t)n_envs * nj; reward += n_envs; done += n_envs;
+        }
         if (rewards5) rewards5 += (size_t)n_envs * 5;
         goto env_step;
+    }
+    if constexpr (ROLL == WAVE_POLICY) {
+        if (lane == 0) {
+            roll.ret_total[e] = ret_total;
+            roll.ret_episode[e] = ret_episode;
+            roll.episode_len[e] = episode_len;
+        }
     }
 #ifdef MG_WALKER_PROFILE
     if (lane == 0) atomicAdd(&mg_walker_phase_cycles[15], __builtin_readcyclecounter() - ph_k0);   // sub-steps + calc_state
@@ -2227,17 +2327,28 @@ int check_walker_terrain(const mg_walker_params *prm) {
     return MG_OK;
 }
 
-// One launch of the wave kernel: the instantiation, its plan and its dynamic LDS (the slab, + the model-constant tail)
+// One launch of the wave kernel: the instantiation, its plan and its dynamic LDS (the slab, + the model-constant tail, + the
+// policy form's x / h tail)
 struct WaveLaunch {
     decltype(&walker_step_wave_kernel<ND, ShapeAny>) kernel;
-    decltype(&walker_step_wave_kernel<ND, ShapeAny, true>) rollout;     // the same instantiation's n_steps-per-launch form
+    decltype(&walker_step_wave_kernel<ND, ShapeAny, WAVE_ROLLOUT>) rollout;     // the same instantiation's n_steps-per-launch form
+    decltype(&walker_step_wave_kernel<ND, ShapeAny, WAVE_POLICY>) policy;       // ... and its closed-loop form (walker_policy.hip)
     bool model_in_lds; WavePlan plan; size_t lds;
 };
+// (each translation unit instantiates the forms it launches: walker.hip the step and the rollout, walker_policy.hip the policy form)
 template <int NMAX, class SH>
-void wave_use(WaveLaunch *w) { w->kernel = walker_step_wave_kernel<NMAX, SH>; w->rollout = walker_step_wave_kernel<NMAX, SH, true>; w->model_in_lds = WAVE_MODEL_IN_LDS<NMAX, SH>; w->plan.fd = SH::fd; }
+void wave_use(WaveLaunch *w) {
+#ifdef MG_WALKER_POLICY_ONLY
+    w->kernel = nullptr; w->rollout = nullptr; w->policy = walker_step_wave_kernel<NMAX, SH, WAVE_POLICY>;
+#else
+    w->kernel = walker_step_wave_kernel<NMAX, SH>; w->rollout = walker_step_wave_kernel<NMAX, SH, WAVE_ROLLOUT>; w->policy = nullptr;
+#endif
+    w->model_in_lds = WAVE_MODEL_IN_LDS<NMAX, SH>; w->plan.fd = SH::fd;
+}
 
-// Every decision of a wave-mapping step, made on the host before anything is launched.
-int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const mg_walker_state *st, WaveLaunch *w) {
+// Every decision of a wave-mapping step, made on the host before anything is launched. policy_hidden >= 0: a launch of the
+// policy form with that many hidden units (its LDS tail, wave_policy_tail_bytes, comes behind the model tail).
+int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const mg_walker_state *st, WaveLaunch *w, int policy_hidden = -1) {
     const int nb = tp->n_bodies, nj = tp->n_joints, ns = tp->n_spheres, ndof = 6 + nj;
     if (ns > 128 || ndof > 64)
         return mg::set_error(MG_ERR_BAD_SIZE, "wave mapping needs <= 128 collision proxies and <= 58 joints");
@@ -2314,6 +2425,7 @@ int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const m
                              "mapping has %zu: use mapping = lane", (size_t)scan, (size_t)room);
     p.tail = (int)((lay.dend * sizeof(double) + lay.iend * sizeof(int) + 15) & ~size_t(15));
     w->lds = p.tail + (w->model_in_lds ? wave_model_doubles(nb, nj) * sizeof(double) : 0);
+    if (policy_hidden >= 0) w->lds += wave_policy_tail_bytes(8 + 2 * nj + tp->n_feet, policy_hidden);
 #ifdef MG_WALKER_LDS_FLOOR      /* timing experiment only (scripts/walker_occupancy_probe.py): fewer resident envs per CU */
     if (const char *fl = getenv("MG_WALKER_LDS_FLOOR")) { const size_t f = (size_t)atol(fl); if (f > w->lds && f <= 64 * 1024) w->lds = f; }
 #endif
@@ -2323,6 +2435,7 @@ int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const m
 
 }  // namespace
 
+#ifndef MG_WALKER_POLICY_ONLY   // (walker_policy.hip defines its own entry points on top of the text above)
 #ifdef MG_WALKER_PROFILE
 extern "C" int mg_walker_profile_read(unsigned long long *out16, int clear) {
     if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(mg_walker_phase_cycles), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
@@ -2371,7 +2484,7 @@ extern "C" int mg_walker_step(const mg_walker_topology *tp, const mg_walker_mode
     if (int rc = wave_plan(tp, prm, st, &w)) return rc;
     const WavePlanArgs a = pack(w.plan);
     hipLaunchKernelGGL(w.kernel, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan, action, obs,
-                       reward, rewards5, done, WaveRoll<false>{});
+                       reward, rewards5, done, WaveRoll<WAVE_STEP>{});
     return mg::check_launch("walker_step_wave_kernel");
 }
 
@@ -2400,6 +2513,7 @@ extern "C" int mg_walker_rollout(const mg_walker_topology *tp, const mg_walker_m
     mg::DeviceGuard guard(mg::device_of(st->pos));
     const WavePlanArgs a = pack(w.plan);
     hipLaunchKernelGGL(w.rollout, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan, actions, obs,
-                       reward, rewards5, done, WaveRoll<true>{n_steps, obs_every});
+                       reward, rewards5, done, WaveRoll<WAVE_ROLLOUT>{n_steps, obs_every});
     return mg::check_launch("walker_step_wave_kernel (rollout)");
 }
+#endif   // MG_WALKER_POLICY_ONLY

@@ -4,5 +4,6 @@ see DESIGN.md §3.5."""
 from . import variants
 from .mjcf import Model, load_mjcf
 from .walker_env import MetaHumanoidEnv, MetaAntEnv, WalkerBatchEnv
+from .policy import WalkerPolicy, WalkerPolicyRollout
 
-__all__ = ["MetaHumanoidEnv", "MetaAntEnv", "WalkerBatchEnv", "Model", "load_mjcf", "variants"]
+__all__ = ["MetaHumanoidEnv", "MetaAntEnv", "WalkerBatchEnv", "WalkerPolicy", "WalkerPolicyRollout", "Model", "load_mjcf", "variants"]

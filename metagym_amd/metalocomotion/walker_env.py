@@ -424,6 +424,89 @@ class WalkerBatchEnv(object):
             info["rewards"] = r5
         return obs, reward, done, info
 
+    def rollout_policy(self, policy, steps, policy_ids=None, record=False, obs_every=0, obs0=None):
+        """`steps` closed-loop env steps in ONE launch: env e evaluates policy `policy_ids[e]` of `policy` (a `WalkerPolicy`;
+        `policy_ids=None` = e % P, else `num_envs` integers in [0, P), checked on the host) on its own observation inside the
+        kernel and steps with the result, the robot staying in LDS. Given the actions the policy produces, everything else is
+        `rollout(actions)`: same physics, rewards, dones, fused auto-resets (an env that ends an episode goes on with the first
+        observation of the next one) and end state, bit for bit; works after `set_task` with the Models of any robot the wave
+        mapping accepts, with and without `auto_reset`. Returns a `WalkerPolicyRollout`: ret_total, ret_episode, episode_len,
+        obs and obs_steps always (`obs_every` as in `rollout`: 0 = the persistent [N, obs_dim] buffer with the last
+        observation, k >= 1 = a fresh [K, N, obs_dim] tensor); actions [T,N,nj] (unclamped), reward [T,N], done [T,N] bool and
+        rewards5 [T,N,5] when `record=True`, else None (the launch then writes nothing per step). `obs0` is the observation
+        step 0 evaluates the policy on: float32 [N, obs_dim]; None takes the persistent observation buffer, i.e. what the last
+        `reset` / `step` / `rollout` / `rollout_policy` returned. `load_state_dict` does NOT restore that buffer (an
+        observation carries the feet flags of the step before, which are not part of the state): after it, pass the
+        observation that belongs to the checkpoint as `obs0`. `global_step` advances by `steps`; the persistent reward and
+        done buffers of `step` are not written. Nothing synchronises when `policy_ids` is None, a host array, or the device
+        tensor of the previous call; any other device tensor is read back once to validate it. A refused call (an id out of
+        range, a policy of another observation or action width) raises and leaves the env as it was."""
+        from .policy import WalkerPolicy, WalkerPolicyRollout
+        if not isinstance(policy, WalkerPolicy):
+            raise TypeError("policy must be a WalkerPolicy, got %s" % type(policy).__name__)
+        if not self._robot_set:
+            raise Exception("BaseBulletEnv::_reset: must call set_robot and set_scene first")   # env_bases.py:68-69
+        T, N, dev, P = int(steps), self.num_envs, self.device, policy.num_policies
+        if T < 1:
+            raise ValueError("steps must be at least 1, got %d" % T)
+        if policy.obs_dim != self.obs_dim or policy.n_act != self.n_joints:
+            raise ValueError("the policy maps %d observation entries to %d actions, this robot has %d and %d"
+                             % (policy.obs_dim, policy.n_act, self.obs_dim, self.n_joints))
+        if obs0 is None:
+            x0 = self._obs
+        else:
+            x0 = obs0 if isinstance(obs0, torch.Tensor) else torch.as_tensor(np.asarray(obs0))
+            if tuple(x0.shape) != (N, self.obs_dim) or x0.dtype != torch.float32:
+                raise ValueError("obs0 must be float32 [%d, %d], got %s %s" % (N, self.obs_dim, x0.dtype, tuple(x0.shape)))
+            x0 = x0.to(dev).contiguous()
+        ids_d = self._policy_ids(policy_ids, P)
+        params = policy.to(dev)
+        desc = _lib.WalkerPolicyDesc(params.data_ptr(), ids_d.data_ptr(), P, policy.hidden, policy.obs_dim, policy.n_act)
+        idx = rollout_obs_steps(T, obs_every)
+        obs = self._obs if int(obs_every) == 0 else torch.empty(len(idx), N, self.obs_dim, dtype=torch.float32, device=dev)
+        res = WalkerPolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
+                                  torch.empty(N, dtype=torch.int32, device=dev), obs, idx)
+        if record:
+            res.actions = torch.empty(T, N, self.n_joints, dtype=torch.float32, device=dev)
+            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+            res.rewards5 = torch.empty(T, N, 5, dtype=torch.float32, device=dev)
+        self._params_c.step_index = self.global_step
+        rc = self._lib.mg_walker_policy_rollout(self._topo, self._models_c, self._params_c, N, self._state_c, T, int(obs_every),
+                                                desc, _lib.ptr(x0), _lib.ptr(obs), _lib.ptr(res.ret_total),
+                                                _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len), _lib.ptr(res.actions),
+                                                _lib.ptr(res.reward), _lib.ptr(res.rewards5), _lib.ptr(res.done),
+                                                _lib.current_stream(dev))
+        _lib.check(rc, "mg_walker_policy_rollout")
+        self.global_step += T
+        return res
+
+    def _policy_ids(self, policy_ids, P):
+        """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a hipGraph
+        capture after its warm-up) neither uploads nor reads back."""
+        N = self.num_envs
+        keep = getattr(self, "_policy_ids_keep", None)
+        if isinstance(policy_ids, torch.Tensor) and keep is not None and keep[0] == P and policy_ids is keep[2] and \
+                policy_ids._version == keep[3]:
+            return keep[1]
+        if policy_ids is None:
+            ids_h = np.arange(N, dtype=np.int64) % P
+        else:
+            ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
+            if ids_h.shape != (N,):
+                raise ValueError("policy_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
+            if ids_h.dtype.kind not in "iu":
+                raise ValueError("policy_ids must be integers, got %s" % ids_h.dtype)
+            if N and (int(ids_h.min()) < 0 or int(ids_h.max()) >= P):
+                raise ValueError("policy_ids must be in [0, %d)" % P)
+        ids_h = ids_h.astype(np.int32)
+        if keep is not None and keep[0] == P and keep[4] == ids_h.tobytes():
+            return keep[1]
+        ids_d = torch.as_tensor(ids_h, device=self.device).contiguous()
+        src = policy_ids if isinstance(policy_ids, torch.Tensor) else None
+        self._policy_ids_keep = (P, ids_d, src, src._version if src is not None else None, ids_h.tobytes())
+        return ids_d
+
     def set_external_wrench(self, wrench):
         """A push on the base body during the first sub-step of every following env step (mg_walker_params.ext_wrench): float64
         `[6, num_envs]` — force and application point in the base body frame — or None. The tensor is read at launch time, so
