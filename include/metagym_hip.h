@@ -554,6 +554,89 @@ int mg_maze3d_rollout(const mg_maze_tasks *tasks, const mg_maze_view *view, int3
                       int32_t obs_every, const void *actions, void *obs, float *reward, double *reward64, uint8_t *done,
                       void *stream);
 
+/* MetaMaze 2-D closed-loop rollouts: n_steps steps per launch with the actions computed inside it. Every env evaluates its
+ * own small RECURRENT policy on the window of the state it holds, its previous action, reward and done, and steps with the
+ * result; task and agent stay in registers for the whole launch and, unless records are asked for, nothing of size
+ * n_steps x n_envs is written. The step is mg_maze2d_rollout's, so replaying the recorded actions through mg_maze2d_rollout
+ * from the same state gives the same rewards, dones, observations and end state bit for bit.
+ *
+ * The policy arithmetic is defined exactly. w = 2 * view_grid + 1 with view_grid in {1, 2, 3}, D = w * w + 6 (15, 31, 55),
+ * H hidden units, 1 <= H <= 64. The input x[D] of an env at a step:
+ *   x[0 .. w*w-1]   the env's current window, row-major: the floats mg_maze2d_step writes (update_observation
+ *                   maze_2d.py:89-121), the SURVIVAL life entry in the centre included
+ *   x[w*w + k]      prev_action == k ? 1 : 0 for k = 0..3 (prev_action = -1: none)
+ *   x[w*w + 4]      prev_reward, the float32 the reward record holds
+ *   x[w*w + 5]      prev_done ? 1 : 0
+ * Every operation is float32, rounded once, never fused, in this order (h: the recurrent state before the step):
+ *   for j in 0..H-1:  z = b[j]
+ *                     for i in 0..D-1: z = z + wx[j][i] * x[i]
+ *                     for i in 0..H-1: z = z + wh[j][i] * h[i]
+ *                     hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+ *   h = hn
+ *   for k in 0..3:    l[k] = bo[k];  for j in 0..H-1: l[k] = l[k] + wo[k][j] * h[j]
+ *   greedy = 0;  for k in 1..3: if l[k] > l[greedy]: greedy = k
+ * so a NaN pre-activation stays NaN, -0 stays -0, and ties and NaN logits resolve to the lowest index.
+ * Exploration is integer arithmetic only: thr = eps_threshold[p] (uint32; the host computes min(floor(epsilon * 2^32),
+ * 2^32 - 1)); for env e at carry step n = step0 + t,
+ *   out = philox4x32_10(c0 = e, c1 = n & 0xFFFFFFFF, c2 = n >> 32, c3 = 0x4D5A, k0 = seed & 0xFFFFFFFF, k1 = seed >> 32)
+ *   action = (out[0] < thr) ? (out[1] & 3) : greedy
+ * (Philox4x32-10, Salmon et al. SC'11, the generator of the fused auto-resets; mg_selftest_philox exposes it). A policy
+ * with thr = 0 never explores and draws nothing; eps_threshold == NULL is thr = 0 for all.
+ *
+ * After the step: prev_action = action, prev_reward = (float)reward, prev_done = done. With auto_reset the step after a
+ * done therefore sees the next episode's first window, prev_done = 1 and the ending step's reward and action, and h
+ * survives the episode (the RL^2 trial). episodic != 0: at a done with auto_reset the carry is cleared instead (h = 0,
+ * prev_action = -1, prev_reward = 0, prev_done = 0). Without auto_reset an env stepped past done goes on stepping, as in
+ * mg_maze2d_step.
+ *
+ * Packed parameters, DEVICE f32, 16-byte aligned, mg_maze2d_policy_param_count(H, view_grid) floats per policy, policy p at
+ * params + p * count. With HP = H rounded up to a multiple of 4 and R = D + 1 + HP + 4 (D + 1 is 16, 32 or 56):
+ *   [0..3] bo[0..3]; then one record of R floats per hidden unit j, at 4 + R j:
+ *   [0..D-1] wx[j][0..D-1], [D] b[j], [D+1 .. D+H] wh[j][0..H-1], zeros up to [D+HP], [D+1+HP .. D+4+HP] wo[0..3][j]
+ *   (count = 4 + H R)
+ * so every read is 16 bytes and one of them feeds the four logits. Parameters must be finite and are read-only for the
+ * launch. Additive entry points; MG_ABI_VERSION is unchanged. */
+typedef struct mg_maze_policy {
+    int32_t n_policies, hidden, view_grid;
+    const float *params;               /* DEVICE f32 [n_policies][count] */
+    const uint32_t *eps_threshold;     /* DEVICE u32 [n_policies], or NULL: no exploration */
+} mg_maze_policy;
+
+/* The carry between launches, updated in place: the policy's memory of each env. A fresh one is zeros with prev_action -1. */
+typedef struct mg_maze_policy_carry {
+    float *h;                /* DEVICE f32 [N][hidden] */
+    int32_t *prev_action;    /* DEVICE i32 [N], -1 = none */
+    float *prev_reward;      /* DEVICE f32 [N] */
+    uint8_t *prev_done;      /* DEVICE u8 [N] */
+} mg_maze_policy_carry;
+
+/* Floats per packed policy (host only); a negative error code for hidden outside [1, 64] or view_grid outside [1, 3]. */
+int32_t mg_maze2d_policy_param_count(int32_t hidden, int32_t view_grid);
+
+/* One launch: one lane per env, one wave per workgroup. policy_ids i32 [N], each in [0, n_policies): validated by the
+ * caller (the kernel clamps an id, it never reads outside the parameters). A wave whose envs all hold one id stages that
+ * policy in LDS; the result does not depend on it. step0 is the carry step of the launch's first step.
+ * Per env, written once at the end of the launch, all required:
+ *   obs_last    f32 [N][w][w]  the window after the last step (the buffer mg_maze2d_step writes)
+ *   ret_total   f64 [N]   the n_steps float64 rewards, added in step order from 0.0
+ *   ret_episode f64 [N]   the rewards up to and including the first done
+ *   episode_len i32 [N]   the number of steps added into ret_episode (n_steps if the env was never done)
+ *   episodes    i32 [N]   the number of steps with done
+ * and the final agent into `state`, the end carry into `carry`. Optional records, NULL = not written (with all five NULL
+ * the launch stores nothing inside its step loop): actions i32, reward f32, reward64 f64, done u8, each [n_steps][N];
+ * obs f32 [K][N][w][w], the K slices obs_every selects exactly as for mg_maze2d_rollout.
+ * Refused on the host, before anything is launched: NULL required pointers (MG_ERR_NULL_POINTER); n_envs, n_steps or
+ * n_policies < 1, obs_every < 0, hidden outside [1, 64], an LDS need above the 160 KiB of a workgroup (MG_ERR_BAD_SIZE);
+ * view_grid outside [1, 3] or not the policy's, params not 16-byte aligned (MG_ERR_BAD_CONFIG); and whatever mg_maze2d_step
+ * refuses. Nothing is allocated and nothing synchronises: the call is hipGraph-capturable as it stands. */
+int mg_maze2d_policy_rollout(const mg_maze_tasks *tasks, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                             int32_t auto_reset, int32_t n_envs, const mg_maze_state *state, int32_t n_steps,
+                             int32_t obs_every, const mg_maze_policy *policy, const int32_t *policy_ids,
+                             const mg_maze_policy_carry *carry, uint64_t seed, uint64_t step0, int32_t episodic,
+                             float *obs_last, double *ret_total, double *ret_episode, int32_t *episode_len,
+                             int32_t *episodes, int32_t *actions, float *reward, double *reward64, uint8_t *done,
+                             float *obs, void *stream);
+
 /* ========================================================================================
  * MetaLocomotion walkers (humanoid / ant) — replaces, for N envs, WalkerBaseEnv.step
  * (metalocomotion/envs/utils/walker_base_env.py:43-82) including the physics the reference

@@ -120,6 +120,17 @@ class MazeState(C.Structure):
                 ("food_env_stride", C.c_int64), ("food_cell_stride", C.c_int64), ("food_by_slot", C.c_int32)]
 
 
+class MazePolicyDesc(C.Structure):
+    """mg_maze_policy (device pointers)"""
+    _fields_ = [("n_policies", C.c_int32), ("hidden", C.c_int32), ("view_grid", C.c_int32), ("params", C.c_void_p),
+                ("eps_threshold", C.c_void_p)]
+
+
+class MazePolicyCarry(C.Structure):
+    """mg_maze_policy_carry (device pointers)"""
+    _fields_ = [("h", C.c_void_p), ("prev_action", C.c_void_p), ("prev_reward", C.c_void_p), ("prev_done", C.c_void_p)]
+
+
 class MazeView(C.Structure):
     """mg_maze_view"""
     _fields_ = [("res_h", C.c_int32), ("res_v", C.c_int32), ("max_vision", C.c_double), ("l_focal", C.c_double),
@@ -353,6 +364,11 @@ SIGNATURES = {
     "mg_maze3d_rollout": (C.c_int, [C.POINTER(MazeTasks), C.POINTER(MazeView), C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.POINTER(MazeState), C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                     _P]),
+    "mg_maze2d_policy_param_count": (C.c_int32, [C.c_int32, C.c_int32]),
+    "mg_maze2d_policy_rollout": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(MazeState), C.c_int32, C.c_int32, C.POINTER(MazePolicyDesc), _P,
+                                           C.POINTER(MazePolicyCarry), C.c_uint64, C.c_uint64, C.c_int32,
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mg_walker_reset": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
                                   C.c_int32, C.POINTER(WalkerState), _P, _P, _P, _P]),
     "mg_walker_step": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),

@@ -1267,6 +1267,7 @@ int check_slots(const mg_maze_tasks *T, const mg_maze_state *s, int task_type) {
 
 }  // namespace
 
+#ifndef MG_MAZE_CORE_ONLY   // maze_policy.hip takes the device functions and the host checks above, and none of what follows
 extern "C" int mg_maze_view_tables(int32_t res_h, double tan_half_fov, double l_focal, double *col_cos,
                                    double *col_sin) {
     MG_REQUIRE_PTR(col_cos);
@@ -1631,3 +1632,4 @@ extern "C" int mg_maze3d_rollout(const mg_maze_tasks *T, const mg_maze_view *vie
     }
     return MG_OK;
 }
+#endif   // MG_MAZE_CORE_ONLY

@@ -1,0 +1,315 @@
+// maze_policy.hip — MetaMaze 2-D closed-loop rollouts: per-env recurrent policies inside the launch (mg_maze2d_policy_*).
+//
+// A translation unit of its own, like quadrotor_policy.hip and walker_policy.hip and for the same reason: it takes maze.hip's
+// device functions (load_task, load_agent, eval_scalar, eval_cells, reset_cells, reset_agent, observe_2d, rollout_records)
+// and host checks by including it with MG_MAZE_CORE_ONLY, so the step and rollout kernels are compiled from the text they
+// were compiled from before. Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes the policy definition
+// of include/metagym_hip.h hold (one rounding per operation).
+//
+// Mapping: maze2d_rollout_kernel's — one lane per env, one wave per workgroup, task and agent in registers for n_steps steps.
+// The policy input x (the window, the previous action one-hot, the previous reward and done) lives in registers (the kernel is
+// templated on view_grid, so D is a compile-time constant); the recurrent state h and its successor live in LDS lane-minor
+// (buf[j * 64 + lane]: the 64 lanes of a ds_read_b32 fall on 64 consecutive dwords, no bank is hit twice in a 32-lane group).
+// Weights: a wave whose lanes all hold one policy id stages that policy in LDS once and reads it with same-address
+// (broadcast) 16-byte reads; a wave with mixed ids reads per lane from global memory. Both inline policy_eval, so the bits
+// are equal.
+#define MG_MAZE_CORE_ONLY
+#include "maze.hip"
+
+#include "mg_philox.h"
+
+namespace {
+
+constexpr int MP_BLOCK = mg::WAVE;
+constexpr int MP_MAX_HIDDEN = 64;
+constexpr size_t MP_LDS_LIMIT = 160 * 1024;      // gfx950: LDS per CU, the most one workgroup can have
+constexpr uint32_t MP_PHILOX_TAG = 0x4D5Au;      // c3 of the exploration draw
+
+typedef float mp_v4f __attribute__((ext_vector_type(4)));
+
+__host__ __device__ constexpr int mp_input_dim(int vg) { return (2 * vg + 1) * (2 * vg + 1) + 6; }
+__host__ __device__ constexpr int mp_hidden_pad(int hidden) { return (hidden + 3) & ~3; }
+// floats of one hidden unit's record: wx[j][0..D-1], b[j], wh[j][0..H-1], zeros up to a multiple of four, wo[0..3][j]
+__host__ __device__ constexpr int mp_record(int hidden, int d) { return d + 1 + mp_hidden_pad(hidden) + 4; }
+// floats of one packed policy: bo[0..3], then H records (D + 1 is a multiple of four for every view_grid: 16, 32, 56)
+__host__ __device__ constexpr int mp_count(int hidden, int d) { return 4 + hidden * mp_record(hidden, d); }
+
+// The dynamic LDS of one workgroup, in bytes from its 16-byte aligned base: the staged policy, the two lane-minor state
+// buffers, and (only when observation slices are recorded) the wave's 64 windows. One function for the launch and the kernel.
+struct MpLds { int policy, h0, h1, tile, bytes; };
+__host__ __device__ inline MpLds mp_lds_layout(int hidden, int vg, bool tile) {
+    const int ww = (2 * vg + 1) * (2 * vg + 1);
+    MpLds l;
+    l.policy = 0;
+    l.h0 = mp_count(hidden, mp_input_dim(vg)) * (int)sizeof(float);           // (a multiple of 16)
+    l.h1 = l.h0 + hidden * MP_BLOCK * (int)sizeof(float);
+    l.tile = l.h1 + hidden * MP_BLOCK * (int)sizeof(float);
+    l.bytes = l.tile + (tile ? MP_BLOCK * ww * (int)sizeof(float) : 0);
+    return l;
+}
+
+struct MpPolicy {
+    const float *__restrict__ params;       // [n_policies][count]
+    const uint32_t *__restrict__ thr;       // [n_policies] or null (no exploration)
+    const int32_t *__restrict__ ids;        // [n]
+    int n_policies, hidden;
+};
+struct MpOut {
+    float *obs_last;                        // [n][w][w]
+    double *ret_total, *ret_episode;        // [n]
+    int32_t *episode_len, *episodes;        // [n]
+};
+struct MpRec {                              // [T][n] each, obs [K][n][w][w]; each may be null
+    int32_t *actions;
+    float *reward;
+    double *reward64;
+    uint8_t *done;
+    float *obs;
+};
+
+// The policy of include/metagym_hip.h on one packed parameter block, from LDS (every lane the same address: broadcast reads)
+// or from global memory (each lane its own block). h and hn are the lane's columns of the two LDS state buffers. The j loop
+// runs at run time; the x loop is unrolled, the h loop reads four recurrent weights per 16-byte read and skips the padding
+// (0 * h added to a pre-activation of -0 would turn it into +0). hn[j] goes into the four logits as soon as it is known: for
+// every k that is the sum over j in ascending order, as defined. Returns the greedy action.
+template <int D>
+__device__ __forceinline__ int policy_eval(const float *__restrict__ p, int hidden, const float *x, const float *h, float *hn) {
+    static_assert((D + 1) % 4 == 0, "the x part of a record is read in 16-byte pieces");
+    const int hp = mp_hidden_pad(hidden), rec = mp_record(hidden, D);
+    const mp_v4f bo = *reinterpret_cast<const mp_v4f *>(p);
+    float l0 = bo.x, l1 = bo.y, l2 = bo.z, l3 = bo.w;
+#pragma unroll 1
+    for (int j = 0; j < hidden; ++j) {
+        const float *r = p + 4 + rec * j;
+        float w[D + 1];
+#pragma unroll
+        for (int q = 0; q < (D + 1) / 4; ++q) {
+            const mp_v4f v = *reinterpret_cast<const mp_v4f *>(r + 4 * q);
+            w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+        }
+        float z = w[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) z = z + w[i] * x[i];
+        const float *rh = r + D + 1;
+#pragma unroll 1
+        for (int i = 0; i < hp; i += 4) {
+            const mp_v4f v = *reinterpret_cast<const mp_v4f *>(rh + i);
+            z = z + v.x * h[i * MP_BLOCK];
+            if (i + 1 < hidden) z = z + v.y * h[(i + 1) * MP_BLOCK];
+            if (i + 2 < hidden) z = z + v.z * h[(i + 2) * MP_BLOCK];
+            if (i + 3 < hidden) z = z + v.w * h[(i + 3) * MP_BLOCK];
+        }
+        const float a = z > 1.0f ? 1.0f : (z < -1.0f ? -1.0f : z);      // a NaN stays NaN, -0 stays -0
+        hn[j * MP_BLOCK] = a;
+        const mp_v4f wo = *reinterpret_cast<const mp_v4f *>(rh + hp);
+        l0 = l0 + wo.x * a; l1 = l1 + wo.y * a; l2 = l2 + wo.z * a; l3 = l3 + wo.w * a;
+    }
+    int g = 0;                                                           // ties and NaN logits: the lowest index
+    float best = l0;
+    if (l1 > best) { g = 1; best = l1; }
+    if (l2 > best) { g = 2; best = l2; }
+    if (l3 > best) { g = 3; }
+    return g;
+}
+
+// maze2d_rollout_kernel's step body in its order, with the action load replaced by the policy. x is computed from the state
+// the lane holds (observe_2d into registers) before the loop and after every step: the observation buffer is never read.
+// Inside the step loop the kernel stores only what `rec` asks for; the agent, the carry, the four per-env results and the
+// last window go out once, at the end.
+template <int VG>
+__global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze_tasks T, mg_maze_state st, int task_type,
+                                                                         int max_steps, int auto_reset, int n_envs, int n_steps,
+                                                                         int obs_every, MpPolicy pa, mg_maze_policy_carry ca,
+                                                                         uint64_t seed, uint64_t step0, int episodic, MpOut po,
+                                                                         MpRec rec) {
+    constexpr int W = 2 * VG + 1, WW = W * W, D = WW + 6;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int H = pa.hidden;
+    const MpLds lds = mp_lds_layout(H, VG, rec.obs != nullptr);
+    const int lane = threadIdx.x;
+    const float *policy_lds = reinterpret_cast<const float *>(smem + lds.policy);
+    float *hc = reinterpret_cast<float *>(smem + lds.h0) + lane;           // the lane's column: h[j] at hc[j * 64]
+    float *hx = reinterpret_cast<float *>(smem + lds.h1) + lane;
+    float *tile = reinterpret_cast<float *>(smem + lds.tile);              // [64][WW] lane-major, as maze2d_rollout_kernel's
+    const int e0 = blockIdx.x * MP_BLOCK;
+    const int e = e0 + lane;
+    const bool live = e < n_envs;
+    const int el = live ? e : n_envs - 1;   // spare lanes shadow the last env and its policy id; they step nothing and store nothing
+
+    // The env's policy, clamped. One id in the whole wave (a ballot: wave-uniform): stage it in LDS once.
+    const int count = mp_count(H, D);
+    int pid = pa.ids[el];
+    pid = pid < 0 ? 0 : (pid >= pa.n_policies ? pa.n_policies - 1 : pid);
+    const int pid0 = __builtin_amdgcn_readfirstlane(pid);
+    const bool staged = __builtin_amdgcn_ballot_w64(pid != pid0) == 0;
+    const float *__restrict__ own = pa.params + (size_t)pid * (size_t)count;
+    if (staged) {
+        const mp_v4f *src = reinterpret_cast<const mp_v4f *>(pa.params + (size_t)pid0 * (size_t)count);
+        mp_v4f *dst = reinterpret_cast<mp_v4f *>(smem + lds.policy);
+        for (int i = lane; i < count / 4; i += MP_BLOCK) dst[i] = src[i];
+    }
+    const uint32_t thr = pa.thr != nullptr ? pa.thr[pid] : 0u;
+
+    const Task t = load_task(T, st.task_id[el]);
+    Agent a = load_agent(st, n_envs, el);
+    for (int j = 0; j < H; ++j) hc[j * MP_BLOCK] = ca.h[(size_t)el * H + j];
+    int prev_action = ca.prev_action[el];
+    float prev_reward = ca.prev_reward[el];
+    int prev_done = ca.prev_done[el] != 0;
+    __syncthreads();                                                       // (one wave) the staged policy is in place
+
+    float x[D];
+    observe_2d(t, st, el, task_type, VG, a, [&](int i, float v) { x[i] = v; });
+    double ret_total = 0.0, ret_episode = 0.0;
+    int episode_len = 0, episodes = 0;
+    bool ended = false;
+    const int run = min(MP_BLOCK, n_envs - e0) * WW;                       // floats this wave owns in a slice of obs
+    const size_t slice = (size_t)n_envs * WW;
+    float *out = rec.obs;
+
+    for (int s = 0; s < n_steps; ++s) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[WW + k] = prev_action == k ? 1.0f : 0.0f;
+        x[WW + 4] = prev_reward;
+        x[WW + 5] = prev_done ? 1.0f : 0.0f;
+        int act = staged ? policy_eval<D>(policy_lds, H, x, hc, hx) : policy_eval<D>(own, H, x, hc, hx);
+        { float *sw = hc; hc = hx; hx = sw; }                              // h = hn
+        if (thr != 0u) {
+            const uint64_t n = step0 + (uint64_t)s;
+            uint32_t o[4];
+            philox4x32_10((uint32_t)el, (uint32_t)n, (uint32_t)(n >> 32), MP_PHILOX_TAG, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+            if (o[0] < thr) act = (int)(o[1] & 3u);
+        }
+        if (live) {
+            const size_t r_at = (size_t)s * n_envs + e;
+            if (rec.actions) rec.actions[r_at] = act;
+            // DISCRETE_ACTIONS maze_env.py:14 = [(-1,0),(1,0),(0,-1),(0,1)]; maze_2d.py:24-29
+            const int ti = a.gx + (act == 0 ? -1 : (act == 1 ? 1 : 0));
+            const int tj = a.gy + (act == 2 ? -1 : (act == 3 ? 1 : 0));
+            const int wi = ti < 0 ? ti + t.n : ti, wj = tj < 0 ? tj + t.n : tj;   // python negative index
+            if (wi < t.n && wj < t.n && t.walls[wi * t.n + wj] < 1) { a.gx = ti; a.gy = tj; }
+            double r;
+            const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
+            if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);
+            if (rec.reward) rec.reward[r_at] = (float)r;
+            if (rec.reward64) rec.reward64[r_at] = r;
+            if (rec.done) rec.done[r_at] = (uint8_t)d;
+            if (d && auto_reset) {
+                reset_agent(t, task_type, a);
+                if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
+            }
+            // the returns: float64 sums in step order; the episode's stops with the first done
+            ret_total = ret_total + r;
+            if (!ended) {
+                ret_episode = ret_episode + r;
+                episode_len += 1;
+                ended = d != 0;
+            }
+            episodes += d;
+            prev_action = act;
+            prev_reward = (float)r;
+            prev_done = d;
+            if (episodic && d && auto_reset) {                             // the next episode starts from a fresh carry
+                for (int j = 0; j < H; ++j) hc[j * MP_BLOCK] = 0.0f;
+                prev_action = -1;
+                prev_reward = 0.0f;
+                prev_done = 0;
+            }
+        }
+        // this step's window is the next step's x (with auto_reset, the next episode's first window)
+        observe_2d(t, st, el, task_type, VG, a, [&](int i, float v) { x[i] = v; });
+        if (out == nullptr || !rollout_records(s, n_steps, obs_every)) continue;   // (uniform: every lane is at step s)
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < WW; ++i) tile[lane * WW + i] = x[i];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float *dst = out + (size_t)e0 * WW;
+        for (int i = lane; i < run; i += MP_BLOCK) dst[i] = tile[i];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");             // the next recorded step overwrites the tile
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        out += slice;
+    }
+    if (!live) return;
+    store_agent(st, n_envs, e, a);
+    for (int j = 0; j < H; ++j) ca.h[(size_t)e * H + j] = hc[j * MP_BLOCK];
+    ca.prev_action[e] = prev_action;
+    ca.prev_reward[e] = prev_reward;
+    ca.prev_done[e] = (uint8_t)prev_done;
+    float *o = po.obs_last + (size_t)e * WW;
+#pragma unroll
+    for (int i = 0; i < WW; ++i) o[i] = x[i];
+    po.ret_total[e] = ret_total;
+    po.ret_episode[e] = ret_episode;
+    po.episode_len[e] = episode_len;
+    po.episodes[e] = episodes;
+}
+
+typedef decltype(&maze2d_policy_rollout_kernel<1>) MpKernel;
+MpKernel pick_policy_kernel(int vg) {
+    return vg == 1 ? maze2d_policy_rollout_kernel<1> : (vg == 2 ? maze2d_policy_rollout_kernel<2> : maze2d_policy_rollout_kernel<3>);
+}
+
+}  // namespace
+
+extern "C" int32_t mg_maze2d_policy_param_count(int32_t hidden, int32_t view_grid) {
+    if (hidden < 1 || hidden > MP_MAX_HIDDEN) return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d is outside [1, %d]", hidden, MP_MAX_HIDDEN);
+    if (view_grid < 1 || view_grid > 3) return mg::set_error(MG_ERR_BAD_CONFIG, "view_grid=%d is outside [1, 3]", view_grid);
+    return mp_count(hidden, mp_input_dim(view_grid));
+}
+
+extern "C" int mg_maze2d_policy_rollout(const mg_maze_tasks *T, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                                        int32_t auto_reset, int32_t n, const mg_maze_state *st, int32_t n_steps,
+                                        int32_t obs_every, const mg_maze_policy *policy, const int32_t *policy_ids,
+                                        const mg_maze_policy_carry *carry, uint64_t seed, uint64_t step0, int32_t episodic,
+                                        float *obs_last, double *ret_total, double *ret_episode, int32_t *episode_len,
+                                        int32_t *episodes, int32_t *actions, float *reward, double *reward64, uint8_t *done,
+                                        float *obs, void *stream) {
+    MG_REQUIRE_PTR(T);
+    MG_REQUIRE_PTR(st);
+    MG_REQUIRE_PTR(policy);
+    MG_REQUIRE_PTR(policy_ids);
+    MG_REQUIRE_PTR(carry);
+    MG_REQUIRE_PTR(obs_last);
+    MG_REQUIRE_PTR(ret_total);
+    MG_REQUIRE_PTR(ret_episode);
+    MG_REQUIRE_PTR(episode_len);
+    MG_REQUIRE_PTR(episodes);
+    if (policy->params == nullptr) return mg::set_error(MG_ERR_NULL_POINTER, "mg_maze_policy needs params");
+    if (!carry->h || !carry->prev_action || !carry->prev_reward || !carry->prev_done)
+        return mg::set_error(MG_ERR_NULL_POINTER, "mg_maze_policy_carry has a NULL array");
+    if (n <= 0) return mg::set_error(MG_ERR_BAD_SIZE, "n_envs=%d", n);
+    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze2d_policy_rollout: n_steps=%d (at least 1)", n_steps);
+    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze2d_policy_rollout: obs_every=%d (0 = the last step only, k >= 1 = every k-th)", obs_every);
+    if (view_grid < 1 || view_grid > 3)
+        return mg::set_error(MG_ERR_BAD_CONFIG, "mg_maze2d_policy_rollout: view_grid=%d is outside [1, 3]", view_grid);
+    if (policy->n_policies < 1) return mg::set_error(MG_ERR_BAD_SIZE, "n_policies=%d", policy->n_policies);
+    if (policy->hidden < 1 || policy->hidden > MP_MAX_HIDDEN)
+        return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d is outside [1, %d]", policy->hidden, MP_MAX_HIDDEN);
+    if (policy->view_grid != view_grid)
+        return mg::set_error(MG_ERR_BAD_CONFIG, "the policy was built for view_grid=%d, the env has %d", policy->view_grid, view_grid);
+    if (((uintptr_t)policy->params & 15u) != 0)
+        return mg::set_error(MG_ERR_BAD_CONFIG, "mg_maze_policy.params must be 16-byte aligned");
+    if (int rc = check_tasks(T, task_type)) return rc;
+    if (int rc = check_mstate(st, task_type)) return rc;
+    if (int rc = check_slots(T, st, task_type)) return rc;
+    const MpLds lds = mp_lds_layout(policy->hidden, view_grid, obs != nullptr);
+    if ((size_t)lds.bytes > MP_LDS_LIMIT)
+        return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d view_grid=%d needs %d B of LDS (> 160 KiB)", policy->hidden, view_grid, lds.bytes);
+    const MpKernel kernel = pick_policy_kernel(view_grid);
+    mg::DeviceGuard guard(mg::device_of(st->grid));
+    if (lds.bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes);
+        if (e != hipSuccess) return mg::check_hip(e, "hipFuncSetAttribute(maze2d_policy_rollout_kernel)");
+    }
+    MpPolicy pa{policy->params, policy->eps_threshold, policy_ids, policy->n_policies, policy->hidden};
+    MpOut po{obs_last, ret_total, ret_episode, episode_len, episodes};
+    MpRec rec{actions, reward, reward64, done, obs};
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + MP_BLOCK - 1) / MP_BLOCK)), dim3(MP_BLOCK), (size_t)lds.bytes,
+                       (hipStream_t)stream, *T, *st, task_type, max_steps, auto_reset, n, n_steps, obs_every, pa, *carry, seed, step0,
+                       episodic, po, rec);
+    return mg::check_launch("maze2d_policy_rollout_kernel");
+}

@@ -2,6 +2,8 @@
 meta-maze-discrete-3D-v0, meta-maze-continuous-3D-v0)."""
 from .maze_env import MetaMaze2D, MetaMazeDiscrete3D, MetaMazeContinuous3D, rollout_obs_steps
 from .maze_task import MAZE_TASK_MANAGER, DeviceTaskTable, MazeTaskManager, MazeTaskSampler, TaskConfig
+from .policy import MazePolicy, MazePolicyRollout, MazePolicyState
 
 __all__ = ["MetaMaze2D", "MetaMazeDiscrete3D", "MetaMazeContinuous3D", "MazeTaskSampler", "MazeTaskManager",
-           "MAZE_TASK_MANAGER", "TaskConfig", "DeviceTaskTable", "rollout_obs_steps"]
+           "MAZE_TASK_MANAGER", "TaskConfig", "DeviceTaskTable", "rollout_obs_steps", "MazePolicy", "MazePolicyState",
+           "MazePolicyRollout"]
