@@ -1241,6 +1241,93 @@ int mg_bandits_step(const mg_bandits_config *cfg, int32_t n_envs, const mg_bandi
                     const int32_t *actions, float *reward, uint8_t *done, int32_t *info_steps, double *expected_gain,
                     uint8_t *invalid, void *stream);
 
+/* Closed-loop rollouts: per-env recurrent policies inside the launch (csrc/bandits_policy.hip).
+ *
+ * n_steps Bandits.step calls of every env in one launch, the action of env e at every step chosen inside the kernel by
+ * policy policy_ids[e] of P recurrent policies from the env's previous action, reward and done (the bandit has no
+ * observation). The step is mg_bandits_step's, draw for draw, so replaying the recorded actions through mg_bandits_step from
+ * the same state gives the same records and end state bit for bit.
+ *
+ * The policy arithmetic is defined exactly. K = arms (2 <= K <= 64; the policy's own limit), H hidden units (1 <= H <= 64).
+ * Every operation is float32, rounded once, never fused, in this order (h: the recurrent state before the step):
+ *   for j in 0..H-1:  z = b[j]
+ *                     if prev_action >= 0: z = z + wa[j][prev_action]
+ *                     z = z + wr[j] * prev_reward
+ *                     z = z + wd[j] * (prev_done ? 1 : 0)
+ *                     for i in 0..H-1: z = z + wh[j][i] * h[i]
+ *                     hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+ *   h = hn
+ *   for k in 0..K-1:  l[k] = bo[k];  for j in 0..H-1: l[k] = l[k] + wo[k][j] * h[j]
+ *   greedy = 0;  for k in 1..K-1: if l[k] > l[greedy]: greedy = k
+ * The one-hot of the previous action is a lookup (one add, or none for prev_action = -1), not K multiply-adds: a
+ * pre-activation of -0 stays -0 whatever wa holds. A NaN stays NaN, -0 stays -0, ties and NaN logits resolve to the lowest
+ * index. prev_action must be in [-1, K); the kernel reads nothing for a value outside (as for -1).
+ * Exploration is integer arithmetic only: thr = eps_threshold[p] (uint32; the host computes min(floor(epsilon * 2^32),
+ * 2^32 - 1)); for env e at carry step n = step0 + t,
+ *   out = philox4x32_10(c0 = e, c1 = n & 0xFFFFFFFF, c2 = n >> 32, c3 = 0x4241, k0 = seed & 0xFFFFFFFF, k1 = seed >> 32)
+ *   action = (out[0] < thr) ? (out[1] % K) : greedy        (unsigned modulo)
+ * A policy with thr = 0 never explores; eps_threshold == NULL is thr = 0 for all. The counter n advances for every env at
+ * every step, whether or not the env stepped.
+ *
+ * One step of env e:
+ *   - over[e] != 0 when the step begins (never reset, or finished without auto_reset): the env does nothing. Its policy
+ *     memory, stream, gains, steps and returns stay as they are; the records get action = -1, reward = 0, done = 0,
+ *     info_steps = steps, expected_gain = 0, best_gain = 0, invalid = 2 (what mg_bandits_step records for such a step).
+ *   - otherwise: the policy is evaluated (h = hn), the action drawn; mg_bandits_step's body runs with it (one legacy double
+ *     against gains[action]; at the end of an episode with auto_reset the task draw from the env's own stream when a
+ *     distribution is set, then steps = 0); then prev_action = action, prev_reward = reward, prev_done = done. The policy's
+ *     memory survives a done (the RL^2 trial; the next step sees prev_done = 1). episodic != 0: at a done with auto_reset
+ *     the carry is cleared instead (h = 0, prev_action = -1, prev_reward = 0, prev_done = 0).
+ *
+ * Packed parameters, DEVICE f32, 16-byte aligned, mg_bandits_policy_param_count(H, K) floats per policy, policy p at
+ * params + p * count. With HP and KP = H and K rounded up to a multiple of 4, RU = 4 + KP + HP and RA = 4 + HP:
+ *   one record of RU floats per hidden unit j, at RU j:
+ *     [0] b[j], [1] wr[j], [2] wd[j], [3] 0, [4 .. 3+K] wa[j][0..K-1], zeros up to [3+KP],
+ *     [4+KP .. 3+KP+H] wh[j][0..H-1], zeros up to [3+KP+HP]
+ *   then one record of RA floats per arm k, at H RU + RA k:
+ *     [0] bo[k], [1..3] 0, [4 .. 3+H] wo[k][0..H-1], zeros up to [3+HP]
+ *   (count = H RU + K RA)
+ * so every record and every 16-byte read starts on a multiple of four floats. Parameters must be finite and are read-only
+ * for the launch. Additive entry points; MG_ABI_VERSION is unchanged. */
+typedef struct mg_bandits_policy {
+    const float *params;               /* DEVICE f32 [n_policies][count] */
+    const uint32_t *eps_threshold;     /* DEVICE u32 [n_policies], or NULL: no exploration */
+    int32_t n_policies, hidden, arms;
+} mg_bandits_policy;
+
+/* The carry between launches, updated in place: mg_maze_policy_carry as it stands (h f32 [N][hidden], prev_action i32 [N]
+ * with -1 = none, prev_reward f32 [N], prev_done u8 [N]); the struct is reused, not declared again. */
+typedef mg_maze_policy_carry mg_bandits_policy_carry;
+
+/* Floats per packed policy (host only); MG_ERR_BAD_SIZE for hidden outside [1, 64] or arms outside [2, 64]. */
+int32_t mg_bandits_policy_param_count(int32_t hidden, int32_t arms);
+
+/* One launch: one lane per env, one wave per workgroup. policy_ids i32 [N], each in [0, n_policies): validated by the
+ * caller (the kernel clamps an id, it never reads outside the parameters). A wave whose envs all hold one id stages that
+ * policy in LDS; the result does not depend on it. step0 is the carry step of the launch's first step.
+ * Per env, written once at the end of the launch, all required:
+ *   ret_total   f64 [N]   the rewards of the steps the env took, added in step order from 0.0
+ *   ret_episode f64 [N]   the rewards up to and including the first done
+ *   episode_len i32 [N]   the number of steps added into ret_episode (0 for an env that was over from the start)
+ *   episodes    i32 [N]   the number of steps with done
+ *   regret      f64 [N]   over the steps the env took, in step order from 0.0: regret = regret + (best - gain), gain =
+ *                         gains[action], best the maximum of the row in force at that step (best = row[0]; for k >= 1: if
+ *                         row[k] > best), found when the launch begins and again after every task draw
+ * and the env into `state`, the end carry into `carry`. Optional records, NULL = not written (with all seven NULL the launch
+ * stores nothing inside its step loop), each [n_steps][N]: actions i32, reward f32, done u8, info_steps i32,
+ * expected_gain f64, best_gain f64, invalid u8 (0 = the step ran, 2 = the env was over).
+ * Refused on the host, before anything is launched: NULL required pointers (MG_ERR_NULL_POINTER); what mg_bandits_step
+ * refuses in cfg (MG_ERR_BAD_CONFIG); n_envs <= 0, n_steps < 1, n_policies < 1, hidden outside [1, 64], arms outside
+ * [2, 64], an LDS need above the 160 KiB of a workgroup (MG_ERR_BAD_SIZE; H = K = 64 needs 86 464 B); policy->arms !=
+ * cfg->arms, params not 16-byte aligned (MG_ERR_BAD_CONFIG). Nothing is allocated and nothing synchronises: the call is
+ * hipGraph-capturable as it stands. */
+int mg_bandits_policy_rollout(const mg_bandits_config *cfg, int32_t n_envs, const mg_bandits_state *state, int32_t n_steps,
+                              const mg_bandits_policy *policy, const int32_t *policy_ids,
+                              const mg_bandits_policy_carry *carry, uint64_t seed, uint64_t step0, int32_t episodic,
+                              double *ret_total, double *ret_episode, int32_t *episode_len, int32_t *episodes,
+                              double *regret, int32_t *actions, float *reward, uint8_t *done, int32_t *info_steps,
+                              double *expected_gain, double *best_gain, uint8_t *invalid, void *stream);
+
 /* ========================================================================================
  * LiftSim — replaces metagym/liftsim/environment/env.py LiftSim (ABI 10)
  * ======================================================================================== */

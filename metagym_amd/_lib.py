@@ -296,6 +296,15 @@ class BanditsState(C.Structure):
                 ("steps", C.c_void_p), ("over", C.c_void_p)]
 
 
+class BanditsPolicyDesc(C.Structure):
+    """mg_bandits_policy (device pointers)"""
+    _fields_ = [("params", C.c_void_p), ("eps_threshold", C.c_void_p), ("n_policies", C.c_int32), ("hidden", C.c_int32),
+                ("arms", C.c_int32)]
+
+
+BanditsPolicyCarry = MazePolicyCarry   # mg_bandits_policy_carry is mg_maze_policy_carry
+
+
 class LiftsimConfig(C.Structure):
     """mg_liftsim_config"""
     _fields_ = [("floors", C.c_int32), ("elevators", C.c_int32), ("generator", C.c_int32), ("queue_capacity", C.c_int32),
@@ -411,6 +420,10 @@ SIGNATURES = {
     "mg_bandits_reset": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P]),
     "mg_bandits_step": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), C.c_int32, _P, _P, _P, _P,
                                   _P, _P, _P]),
+    "mg_bandits_policy_param_count": (C.c_int32, [C.c_int32, C.c_int32]),
+    "mg_bandits_policy_rollout": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), C.c_int32,
+                                            C.POINTER(BanditsPolicyDesc), _P, C.POINTER(BanditsPolicyCarry), C.c_uint64,
+                                            C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

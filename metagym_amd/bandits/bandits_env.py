@@ -249,6 +249,95 @@ class Bandits(object):
             self._raise_invalid(invalid, a)
         return reward, done, {"steps": info_steps, "expected_gain": gain, "invalid": invalid}
 
+    def rollout_policy(self, policy, steps, policy_ids=None, state=None, seed=0, record=False, episodic=False):
+        """`steps` closed-loop env steps in ONE launch: env e evaluates policy `policy_ids[e]` of `policy` (a `BanditPolicy`;
+        `policy_ids=None` = e % P) on its previous action, reward and done inside the kernel and pulls the arm it chooses
+        (bandits/policy.py defines the arithmetic exactly). `state` is the carry of the previous call (a `BanditPolicyState`;
+        None = a fresh one); it is not written, the end carry comes back as `.state` of the result with `step` advanced by
+        `steps`. `seed` keys the exploration draws of a policy with epsilon. The step is `rollout`'s, draw for draw, with
+        `auto_reset` and `resample_task` as the env was built. The policy's memory survives a done (the next step sees
+        prev_done = 1 and the ending step's reward and action); `episodic=True` clears the carry at a done with auto_reset
+        instead. An env that is over when a step begins (never reset, or finished without auto_reset) does nothing in that
+        step: its memory, stream and returns stay, its records are action -1, reward 0, done 0, invalid 2. Returns a
+        `BanditsPolicyRollout`: ret_total, ret_episode, episode_len, episodes, regret and state always; actions, reward,
+        done, info_steps, expected_gain, best_gain, invalid [steps, N] when `record=True`, else None (the launch then writes
+        nothing per step). Nothing synchronises when `policy_ids` is None or the array of the previous call, so after
+        `policy.to(device)` the call can be captured in a hipGraph. A refused call (a policy of another K, an id out of range,
+        a carry of another N or H, steps < 1) raises and launches nothing."""
+        import torch
+        from .policy import BanditPolicy, BanditPolicyState, BanditsPolicyRollout
+        if not isinstance(policy, BanditPolicy):
+            raise TypeError("policy must be a BanditPolicy, got %s" % type(policy).__name__)
+        T, N, dev, P, H = int(steps), self.num_envs, self.device, policy.num_policies, policy.hidden
+        if T < 1:
+            raise ValueError("steps must be at least 1, got %d" % T)
+        if policy.arms != self.K:
+            raise ValueError("the policy was built for %d arms, the env has %d" % (policy.arms, self.K))
+        seed = int(seed)
+        if not (0 <= seed < 2 ** 64):
+            raise ValueError("seed must be in [0, 2^64), got %d" % seed)
+        if state is None:
+            state = BanditPolicyState.zeros(N, H, dev)
+        elif not isinstance(state, BanditPolicyState):
+            raise TypeError("state must be a BanditPolicyState, got %s" % type(state).__name__)
+        want = (("h", (N, H), torch.float32), ("prev_action", (N,), torch.int32), ("prev_reward", (N,), torch.float32),
+                ("prev_done", (N,), torch.uint8))
+        for name, shape, dtype in want:
+            v = getattr(state, name)
+            if not isinstance(v, torch.Tensor) or tuple(v.shape) != shape or v.dtype != dtype:
+                raise ValueError("state.%s must be a %s tensor of shape %s (this env has %d envs, the policy %d hidden units)"
+                                 % (name, dtype, shape, N, H))
+        if not (0 <= state.step < 2 ** 64 - T):
+            raise ValueError("state.step = %d is outside [0, 2^64 - steps)" % state.step)
+        ids_d = self._policy_ids(policy_ids, P)
+        params, thr = policy.to(dev)
+        # everything is checked: from here on the env and the new carry are written
+        carry = BanditPolicyState(*[getattr(state, name).to(dev).clone().contiguous() for name, _, _ in want], step=state.step + T)
+        desc = _lib.BanditsPolicyDesc(params.data_ptr(), thr.data_ptr() if thr is not None else None, P, H, policy.arms)
+        carry_c = _lib.BanditsPolicyCarry(carry.h.data_ptr(), carry.prev_action.data_ptr(), carry.prev_reward.data_ptr(),
+                                          carry.prev_done.data_ptr())
+        f64 = lambda: torch.empty(N, dtype=torch.float64, device=dev)
+        i32 = lambda: torch.empty(N, dtype=torch.int32, device=dev)
+        res = BanditsPolicyRollout(f64(), f64(), i32(), i32(), f64(), carry)
+        if record:
+            res.actions = torch.empty(T, N, dtype=torch.int32, device=dev)
+            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+            res.info_steps = torch.empty(T, N, dtype=torch.int32, device=dev)
+            res.expected_gain = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.best_gain = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.invalid = torch.empty(T, N, dtype=torch.uint8, device=dev)
+        cfg = self._cfg(*(self.resample_task or (None,)))
+        rc = self._lib.mg_bandits_policy_rollout(cfg, N, self._state, T, desc, _lib.ptr(ids_d), carry_c, seed, state.step,
+                                                 int(bool(episodic)), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
+                                                 _lib.ptr(res.episode_len), _lib.ptr(res.episodes), _lib.ptr(res.regret),
+                                                 _lib.ptr(res.actions), _lib.ptr(res.reward), _lib.ptr(res.done),
+                                                 _lib.ptr(res.info_steps), _lib.ptr(res.expected_gain), _lib.ptr(res.best_gain),
+                                                 _lib.ptr(res.invalid), self._stream())
+        _lib.check(rc, "mg_bandits_policy_rollout")
+        return res
+
+    def _policy_ids(self, policy_ids, P):
+        """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a hipGraph
+        capture after its warm-up) neither uploads nor reads back."""
+        import torch
+        N = self.num_envs
+        if policy_ids is None:
+            ids_h = np.arange(N, dtype=np.int64) % P
+        else:
+            ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
+            if ids_h.shape != (N,):
+                raise ValueError("policy_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
+            if ids_h.dtype.kind not in "iu":
+                raise ValueError("policy_ids must be integers, got %s" % ids_h.dtype)
+            if int(ids_h.min()) < 0 or int(ids_h.max()) >= P:
+                raise ValueError("policy_ids must be in [0, %d)" % P)
+        key = (P, ids_h.astype(np.int32).tobytes())
+        keep = getattr(self, "_policy_ids_keep", None)
+        if keep is None or keep[0] != key:
+            keep = self._policy_ids_keep = (key, torch.as_tensor(ids_h.astype(np.int32), device=self.device).contiguous())
+        return keep[1]
+
     def expected_upperbound(self):
         """max_steps * max(gains), float64 [N]."""
         return self.max_steps * self.gains.max(dim=1).values

@@ -251,6 +251,7 @@ BanditsK fold(const mg_bandits_config *c) {
         MG_REQUIRE_PTR((s)->gains); MG_REQUIRE_PTR((s)->steps); MG_REQUIRE_PTR((s)->over);                    \
     } while (0)
 
+#ifndef MG_BANDITS_CORE_ONLY   // bandits_policy.hip takes the device functions and the host checks above, and none of what follows
 extern "C" int mg_bandits_seed(int32_t n_envs, uint32_t seed_base, const uint32_t *seeds, const mg_bandits_state *state,
                                void *stream) {
     MG_REQUIRE_PTR(state);
@@ -307,3 +308,4 @@ extern "C" int mg_bandits_step(const mg_bandits_config *cfg, int32_t n_envs, con
                        fold(cfg), n_envs, n_steps, *state, actions, reward, done, info_steps, expected_gain, invalid);
     return mg::check_launch("bandits_step_kernel");
 }
+#endif   // MG_BANDITS_CORE_ONLY
