@@ -9,7 +9,12 @@ golden generators). Records:
   - the text of one small generate_to_file after numpy.random.seed(seed)
 These pin tests/metalm_oracle.py (CPU) and mg_metalm_generate (GPU) bit for bit.
 
-    python scripts/gen_golden_metalm.py
+A second, small fixture, tests/golden/metalm_edges.npz, holds the rows of the edge table tests/metalm_cases.py (token and
+element-index ranges, the Poisson switch, V at the int32 limit, long elements, mask_ratio and e at their ends), recorded the
+same way with `mask_ratio` set on the reference's generator where the case has one.
+
+    python scripts/gen_golden_metalm.py            # both fixtures
+    python scripts/gen_golden_metalm.py edges      # one of them: "metalm" or "edges"
 """
 import json
 import os
@@ -20,7 +25,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gen_golden  # noqa: E402  (reference import shims)
+import metalm_cases  # noqa: E402  (the edge table)
 
 D = dict(V=64, n=10, l=64, e=0.10, L=2048)
 SEEDS = [0, 1, 7, 2 ** 32 - 1]
@@ -41,9 +48,7 @@ BATCHES = [(D, 5, 4), (dict(D, V=5, n=3, l=12.5, L=700), 2 ** 31, 9)]   # (cfg, 
 TEXT = (dict(V=8, n=3, l=4, e=0.3, L=20), 11, 3)
 
 
-def main():
-    gen_golden._import_reference()
-    import metagym.metalm as ref
+def write_metalm(ref):
     out = {"numpy_version": np.str_(np.__version__)}
     rows = []
     for ci, (cfg, seeds) in enumerate(CASES):
@@ -76,6 +81,35 @@ def main():
     dst = os.path.join(ROOT, "tests", "golden", "metalm.npz")
     np.savez_compressed(dst, **out)
     print("wrote", dst, os.path.getsize(dst), "bytes")
+
+
+def write_edges(ref):
+    out = {"numpy_version": np.str_(np.__version__)}
+    rows = []
+    for ci, _, cfg, s in metalm_cases.table_rows():
+        gen = ref.MetaLM(**metalm_cases.ctor_kwargs(cfg))
+        gen.mask_ratio = metalm_cases.mask_ratio(cfg)
+        np.random.seed(s)
+        f, lb = gen.data_generator()
+        out["row_%d_%d_features" % (ci, s)] = f.astype(np.int32)
+        out["row_%d_%d_labels" % (ci, s)] = lb.astype(np.int32)
+        rows.append([ci, s])
+    out["cases"] = np.str_(json.dumps([[name, cfg] for name, cfg, _ in metalm_cases.CASES]))
+    out["rows"] = np.asarray(rows, np.int64)
+    dst = os.path.join(ROOT, "tests", "golden", "metalm_edges.npz")
+    np.savez_compressed(dst, **out)
+    print("wrote", dst, os.path.getsize(dst), "bytes")
+
+
+def main():
+    which = sys.argv[1:] or ["metalm", "edges"]
+    assert set(which) <= {"metalm", "edges"}, which
+    gen_golden._import_reference()
+    import metagym.metalm as ref
+    if "metalm" in which:
+        write_metalm(ref)
+    if "edges" in which:
+        write_edges(ref)
 
 
 if __name__ == "__main__":
