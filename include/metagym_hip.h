@@ -349,6 +349,56 @@ int mg_quadrotor_policy_rollout(const mg_quadrotor_config *cfg, const mg_quadrot
                                 int32_t *episode_len, const mg_quadrotor_policy_records *records,
                                 const mg_quadrotor_policy_last *last, void *stream);
 
+/* Closed-loop rollouts with recurrent policies and a carry: mg_quadrotor_policy_rollout with a controller that remembers.
+ * Besides the observation x[D] (the same x the MLP form reads) a policy reads pa[4], the previous *unclamped* action (the
+ * value the actions record holds), pr, the float32 of the previous step's reward record, pd, the previous done, and its
+ * memory h[H], 1 <= H <= 64. Every operation is float32, rounded once, never fused, in this order:
+ *   for j in 0..H-1:  z = b[j]
+ *                     for i in 0..D-1: z = z + wx[j][i] * x[i]
+ *                     for k in 0..3:   z = z + wa[j][k] * pa[k]
+ *                     z = z + wr[j] * pr
+ *                     z = z + wd[j] * (pd ? 1 : 0)
+ *                     for i in 0..H-1: z = z + wh[j][i] * h[i]
+ *                     hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+ *   h = hn
+ *   for k in 0..3:    a[k] = bo[k];  for j in 0..H-1: a[k] = a[k] + wo[k][j] * h[j]
+ * a[0..3] go into the step unclamped. A NaN pre-activation stays NaN and -0 stays -0; padding entries of a packed record
+ * are never multiplied in (0 * h added to -0 would give +0).
+ *
+ * Packed parameters, DEVICE f32, 16-byte aligned, mg_quadrotor_rpolicy_param_count(H, D) floats per policy, policy p at
+ * params_d + p * count. DP = D rounded up to a multiple of 4 (16 or 20), HP = H rounded up to a multiple of 4:
+ *   [0..3] bo[0..3]; then one record of DP + HP + 12 floats per hidden unit j, at 4 + (DP + HP + 12) j:
+ *   [0..D-1] wx[j][0..D-1], zeros up to DP; [DP..DP+3] b[j], wr[j], wd[j], 0; [DP+4..DP+7] wa[j][0..3];
+ *   [DP+8..DP+8+H-1] wh[j][0..H-1], zeros up to HP; [DP+8+HP..DP+11+HP] wo[0..3][j]
+ * The descriptor is mg_quadrotor_policy with `hidden` = H and the parameters in this layout.
+ *
+ * The carry, DEVICE, updated in place by a launch; all zero = fresh. n_steps1 steps and then n_steps2 steps with the same
+ * carry equal n_steps1 + n_steps2 steps in one call. At a done the memory survives: the next step sees the new episode's
+ * first observation (with a fused reset), pd = 1 and the ending step's reward and action. episodic != 0 (ar required)
+ * zeroes all four fields of an env at a done instead. Without a fused reset an env goes on stepping past a done as in
+ * mg_quadrotor_policy_rollout and the carry is updated like on any other step. */
+typedef struct mg_quadrotor_rpolicy_carry {
+    float *h;             /* [n][hidden] */
+    float *prev_action;   /* [n][4], 16-byte aligned */
+    float *prev_reward;   /* [n] */
+    uint8_t *prev_done;   /* [n] */
+} mg_quadrotor_rpolicy_carry;
+
+/* Floats per packed recurrent policy (host only); a negative error code for hidden outside [1, 64] or obs_dim not 16 / 19. */
+int32_t mg_quadrotor_rpolicy_param_count(int32_t hidden, int32_t obs_dim);
+
+/* Arguments, outputs and semantics of mg_quadrotor_policy_rollout, plus the carry and `episodic`. The same host-side
+ * refusals, made before any device call, and: a NULL carry array (MG_ERR_NULL_POINTER), hidden outside [1, 64]
+ * (MG_ERR_BAD_SIZE), prev_action not 16-byte aligned, episodic != 0 with ar == NULL (MG_ERR_BAD_CONFIG). The launch uses at
+ * most 57 360 bytes of dynamic LDS (H = 64, D = 19), so no limit is raised. Asynchronous on `stream`; no argument depends on
+ * a step counter, so the call is hipGraph-capturable as it stands. Additive; MG_ABI_VERSION is unchanged. */
+int mg_quadrotor_rpolicy_rollout(const mg_quadrotor_config *cfg, const mg_quadrotor_tasks *tasks, int32_t n_envs,
+                                 int32_t n_steps, const mg_quadrotor_state *state, const mg_quadrotor_autoreset *ar,
+                                 const mg_quadrotor_policy *policy, const mg_quadrotor_rpolicy_carry *carry, int32_t episodic,
+                                 double *ret_total, double *ret_episode, int32_t *episode_len,
+                                 const mg_quadrotor_policy_records *records, const mg_quadrotor_policy_last *last,
+                                 void *stream);
+
 /* ========================================================================================
  * MetaMaze — replaces metagym/metamaze/envs/{maze_base,maze_2d,maze_discrete_3d,
  *            maze_continuous_3d,dynamics,ray_caster_utils}.py for N envs

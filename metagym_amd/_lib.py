@@ -93,6 +93,11 @@ class QuadrotorPolicyLast(C.Structure):
                 ("failed", C.c_void_p)]
 
 
+class QuadrotorRPolicyCarry(C.Structure):
+    """mg_quadrotor_rpolicy_carry (device pointers)"""
+    _fields_ = [("h", C.c_void_p), ("prev_action", C.c_void_p), ("prev_reward", C.c_void_p), ("prev_done", C.c_void_p)]
+
+
 class MazeTasks(C.Structure):
     """mg_maze_tasks (device pointers)"""
     _fields_ = [("n", C.c_int32), ("n_tasks", C.c_int32), ("start", C.c_void_p), ("goal", C.c_void_p),
@@ -356,6 +361,12 @@ SIGNATURES = {
                                               C.POINTER(QuadrotorState), C.POINTER(QuadrotorAutoReset),
                                               C.POINTER(QuadrotorPolicyDesc), _P, _P, _P, C.POINTER(QuadrotorPolicyRecords),
                                               C.POINTER(QuadrotorPolicyLast), _P]),
+    "mg_quadrotor_rpolicy_param_count": (C.c_int32, [C.c_int32, C.c_int32]),
+    "mg_quadrotor_rpolicy_rollout": (C.c_int, [C.POINTER(QuadrotorConfig), C.POINTER(QuadrotorTasks), C.c_int32, C.c_int32,
+                                               C.POINTER(QuadrotorState), C.POINTER(QuadrotorAutoReset),
+                                               C.POINTER(QuadrotorPolicyDesc), C.POINTER(QuadrotorRPolicyCarry), C.c_int32,
+                                               _P, _P, _P, C.POINTER(QuadrotorPolicyRecords),
+                                               C.POINTER(QuadrotorPolicyLast), _P]),
     "mg_quadrotor_rollout": (C.c_int, [C.POINTER(QuadrotorConfig), C.c_int32, C.c_int32,
                                        C.POINTER(QuadrotorState), _P, _P, _P, _P, _P, _P, _P]),
     "mg_maze_view_tables": (C.c_int, [C.c_int32, C.c_double, C.c_double, _P, _P]),

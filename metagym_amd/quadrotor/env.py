@@ -387,24 +387,50 @@ class Quadrotor(object):
         self._last_rollout_reward64 = rew64
         return obs, rew, done, failed
 
-    def rollout_policy(self, policy, steps, policy_ids=None, record=False):
+    def rollout_policy(self, policy, steps, policy_ids=None, record=False, state=None, episodic=False):
         """`steps` closed-loop env steps in one launch: env e evaluates policy `policy_ids[e]` of `policy` (a
-        `QuadrotorPolicy`; `policy_ids=None` = e % P) on its own observation inside the kernel and steps with the result.
+        `QuadrotorPolicy` or a `QuadrotorRecurrentPolicy`; `policy_ids=None` = e % P) on its own observation inside the
+        kernel and steps with the result.
         Works on the uniform env and after `set_task(table)`, with and without `auto_reset`, for all three tasks.
         Returns a `PolicyRollout`: ret_total, ret_episode, episode_len always; actions, obs, reward, reward64, done, failed
         [steps, N, ...] when `record=True`, else None (the launch then writes nothing per step). The last step's outputs go
         into the buffers step() returns, so a following step() continues coherently. Nothing synchronises when
         `policy_ids` is None, a host array, or the device tensor of the previous call; any other device tensor is read
         back once to validate it. A refused call (an id out of range, a policy for another observation width) raises and
-        leaves the env as it was."""
-        from .policy import PolicyRollout, QuadrotorPolicy
-        if not isinstance(policy, QuadrotorPolicy):
-            raise TypeError("policy must be a QuadrotorPolicy, got %s" % type(policy).__name__)
+        leaves the env as it was.
+
+        With a `QuadrotorRecurrentPolicy`, `state` is the carry (a `QuadrotorPolicyState` on the env's device, updated in
+        place; None = a fresh zero carry) and the result's `state` is the end carry: the caller's own object if one was
+        passed. The memory survives a done; `episodic=True` (only with `auto_reset`) clears the carry of an env at its done
+        instead. A refused call leaves the carry as it was too. `state` and `episodic` belong to the recurrent form: with a
+        `QuadrotorPolicy` they raise TypeError."""
+        from .policy import PolicyRollout, QuadrotorPolicy, QuadrotorPolicyState, QuadrotorRecurrentPolicy
+        recurrent = isinstance(policy, QuadrotorRecurrentPolicy)
+        if not recurrent and not isinstance(policy, QuadrotorPolicy):
+            raise TypeError("policy must be a QuadrotorPolicy or a QuadrotorRecurrentPolicy, got %s" % type(policy).__name__)
+        if not recurrent and (state is not None or episodic):
+            raise TypeError("state and episodic belong to a QuadrotorRecurrentPolicy; a QuadrotorPolicy has no memory")
         T, N, dev, P = int(steps), self.num_envs, self.device, policy.num_policies
         if T < 1:
             raise ValueError("steps must be at least 1, got %d" % T)
         if policy.obs_dim != self.obs_dim:
             raise ValueError("the policy reads %d observation entries, task %r has %d" % (policy.obs_dim, self.task, self.obs_dim))
+        if recurrent:
+            if episodic and not self.auto_reset:
+                raise ValueError("episodic=True clears the carry at a fused reset: it needs an env built with auto_reset=True")
+            if state is not None:
+                if not isinstance(state, QuadrotorPolicyState):
+                    raise TypeError("state must be a QuadrotorPolicyState, got %s" % type(state).__name__)
+                fields = (state.h, state.prev_action, state.prev_reward, state.prev_done)
+                if not all(isinstance(t, torch.Tensor) for t in fields):
+                    raise ValueError("state must hold torch tensors on %s (QuadrotorPolicyState.zeros(N, H, device))" % dev)
+                if any(t.device != dev for t in fields):
+                    raise ValueError("state lives on %s, the env on %s" % (state.h.device, dev))
+                want = (((N, policy.hidden), torch.float32), ((N, 4), torch.float32), ((N,), torch.float32), ((N,), torch.uint8))
+                for t, (shape, dtype), name in zip(fields, want, QuadrotorPolicyState.__slots__):
+                    if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                        raise ValueError("state.%s must be a contiguous %s tensor of shape %s (num_envs=%d, hidden=%d), got %s %s"
+                                         % (name, dtype, shape, N, policy.hidden, t.dtype, tuple(t.shape)))
         ids_d = self._policy_ids(policy_ids, P)
         params = policy.to(dev)
         desc = _lib.QuadrotorPolicyDesc(params.data_ptr(), ids_d.data_ptr(), P, policy.hidden, policy.obs_dim)
@@ -421,6 +447,18 @@ class Quadrotor(object):
             records = _lib.QuadrotorPolicyRecords(*[t.data_ptr() for t in (res.actions, res.obs, res.reward, res.reward64,
                                                                             res.done, res.failed)])
         last = _lib.QuadrotorPolicyLast(*self._out_ptrs)
+        if recurrent:
+            if state is None:
+                state = QuadrotorPolicyState.zeros(N, policy.hidden, dev)
+            carry = _lib.QuadrotorRPolicyCarry(state.h.data_ptr(), state.prev_action.data_ptr(), state.prev_reward.data_ptr(),
+                                               state.prev_done.data_ptr())
+            rc = self._lib.mg_quadrotor_rpolicy_rollout(self._cfg, self._tasks, N, T, self._state,
+                                                        self._ar if self.auto_reset else None, desc, carry, int(bool(episodic)),
+                                                        _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
+                                                        _lib.ptr(res.episode_len), records, last, _raw_stream(self._dev_index))
+            _lib.check(rc, "mg_quadrotor_rpolicy_rollout")
+            res.state = state
+            return res
         rc = self._lib.mg_quadrotor_policy_rollout(self._cfg, self._tasks, N, T, self._state,
                                                    self._ar if self.auto_reset else None, desc, _lib.ptr(res.ret_total),
                                                    _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len), records, last,

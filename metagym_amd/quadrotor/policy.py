@@ -14,10 +14,34 @@ is float32, rounded once, never fused, in this order:
 
     pol = QuadrotorPolicy.linear(w, b)                     # w [P, 4, 16], b [P, 4], float32
     res = env.rollout_policy(pol, steps=64)                # env e flies policy e % P
+
+`QuadrotorRecurrentPolicy` is the form with a memory (mg_quadrotor_rpolicy_rollout). Besides x it reads pa[4], the previous
+*unclamped* action (the value the `actions` record holds), pr, the float32 of the previous step's reward record, pd, the
+previous done, and its memory h[H], 1 <= H <= 64. Again every operation is float32, rounded once, never fused, in this order:
+
+    for j in 0..H-1:  z = b[j]
+                      for i in 0..D-1: z = z + wx[j][i] * x[i]
+                      for k in 0..3:   z = z + wa[j][k] * pa[k]
+                      z = z + wr[j] * pr
+                      z = z + wd[j] * (pd ? 1 : 0)
+                      for i in 0..H-1: z = z + wh[j][i] * h[i]
+                      hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+    h = hn
+    for k in 0..3:    a[k] = bo[k];  for j in 0..H-1: a[k] = a[k] + wo[k][j] * h[j]
+
+A NaN pre-activation stays NaN, -0 stays -0, and the padding of a packed record is never multiplied in. The carry
+(`QuadrotorPolicyState`: h, prev_action, prev_reward, prev_done) lives on the device, is updated in place by a launch and is
+all zero when fresh: T1 steps and then T2 steps with one state object equal T1 + T2 steps in one call. The memory survives a
+done; `episodic=True` (with `auto_reset`) clears the carry of an env at its done instead.
+
+    pol = QuadrotorRecurrentPolicy(wx, wa, wr, wd, wh, b, wo, bo)
+    res = env.rollout_policy(pol, steps=64)                       # from a fresh carry
+    res = env.rollout_policy(pol, steps=64, state=res.state)      # and goes on, memory kept
 """
 import numpy as np
 
 MAX_HIDDEN = 256
+MAX_RECURRENT_HIDDEN = 64
 OBS_DIMS = (16, 19)
 _HEAD, _REC, _W2_AT = 4, 24, 20     # packed layout, see param_count / pack
 
@@ -154,14 +178,216 @@ class QuadrotorPolicy(object):
         return a
 
 
+def _pad4(v):
+    return (int(v) + 3) & ~3
+
+
+def _rrecord(hidden, obs_dim):
+    return _pad4(obs_dim) + _pad4(hidden) + 12
+
+
+def recurrent_param_count(hidden, obs_dim):
+    """Floats per packed recurrent policy (what mg_quadrotor_rpolicy_param_count returns): 4 + H (DP + HP + 12), DP and HP
+    being D and H rounded up to a multiple of four."""
+    if not (1 <= int(hidden) <= MAX_RECURRENT_HIDDEN):
+        raise ValueError("hidden units must be in [1, %d], got %r" % (MAX_RECURRENT_HIDDEN, hidden))
+    if obs_dim not in OBS_DIMS:
+        raise ValueError("the observation has 16 entries (19 for velocity_control), got %r" % (obs_dim,))
+    return _HEAD + int(hidden) * _rrecord(hidden, obs_dim)
+
+
+def _np(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+class QuadrotorPolicyState(object):
+    """The carry of a recurrent closed-loop rollout, the policy's memory of each env: h float32 [N, H], prev_action float32
+    [N, 4] (unclamped), prev_reward float32 [N], prev_done uint8 [N]. Torch tensors on the env's device, updated in place by
+    a launch (or numpy arrays, for `QuadrotorRecurrentPolicy.reference`). All zero when fresh."""
+    __slots__ = ("h", "prev_action", "prev_reward", "prev_done")
+
+    def __init__(self, h, prev_action, prev_reward, prev_done):
+        self.h, self.prev_action, self.prev_reward, self.prev_done = h, prev_action, prev_reward, prev_done
+
+    @classmethod
+    def zeros(cls, num_envs, hidden, device=None):
+        """The fresh carry: zeros everywhere. device None: numpy arrays."""
+        N, H = int(num_envs), int(hidden)
+        if N < 1 or not (1 <= H <= MAX_RECURRENT_HIDDEN):
+            raise ValueError("a carry needs num_envs >= 1 and hidden in [1, %d], got %d and %d" % (MAX_RECURRENT_HIDDEN, N, H))
+        if device is None:
+            return cls(np.zeros((N, H), np.float32), np.zeros((N, 4), np.float32), np.zeros(N, np.float32), np.zeros(N, np.uint8))
+        import torch
+        return cls(torch.zeros(N, H, dtype=torch.float32, device=device), torch.zeros(N, 4, dtype=torch.float32, device=device),
+                   torch.zeros(N, dtype=torch.float32, device=device), torch.zeros(N, dtype=torch.uint8, device=device))
+
+    @property
+    def num_envs(self):
+        return int(self.h.shape[0])
+
+    @property
+    def hidden(self):
+        return int(self.h.shape[1])
+
+    @property
+    def device(self):
+        """The torch device of the arrays; None for a numpy carry."""
+        return getattr(self.h, "device", None) if hasattr(self.h, "detach") else None
+
+    def clone(self):
+        c = (lambda v: v.clone()) if hasattr(self.h, "clone") else (lambda v: v.copy())
+        return QuadrotorPolicyState(c(self.h), c(self.prev_action), c(self.prev_reward), c(self.prev_done))
+
+    def numpy(self):
+        """A host copy, as numpy arrays: what `QuadrotorRecurrentPolicy.reference` takes."""
+        return QuadrotorPolicyState(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.float32),
+                                    _np(self.prev_reward).astype(np.float32), _np(self.prev_done).astype(np.uint8))
+
+    def observed(self, reward, done, clear=None):
+        """The numpy carry after the env step that followed `reference`: prev_reward = float32(reward), prev_done = done, h
+        and prev_action kept. `clear` (bool [N] or None): the envs whose four fields are zeroed afterwards, which is what
+        `episodic=True` does at a done with `auto_reset`."""
+        out = QuadrotorPolicyState(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.float32),
+                                   _np(reward).astype(np.float32), (_np(done) != 0).astype(np.uint8))
+        if out.prev_reward.shape != (self.num_envs,) or out.prev_done.shape != (self.num_envs,):
+            raise ValueError("reward and done must have shape (%d,)" % self.num_envs)
+        if clear is not None:
+            c = _np(clear).astype(bool)
+            out.h[c] = 0.0
+            out.prev_action[c] = 0.0
+            out.prev_reward[c] = 0.0
+            out.prev_done[c] = 0
+        return out
+
+
+class QuadrotorRecurrentPolicy(object):
+    """P recurrent policies: wx [P, H, D], wa [P, H, 4], wr [P, H], wd [P, H], wh [P, H, H], b [P, H], wo [P, 4, H], bo [P, 4],
+    all float32 and finite. 1 <= H <= 64, D = 16, or 19 for velocity_control."""
+
+    def __init__(self, wx, wa, wr, wd, wh, b, wo, bo):
+        wx, wa, wr, wd = _f32("wx", wx, 3), _f32("wa", wa, 3), _f32("wr", wr, 2), _f32("wd", wd, 2)
+        wh, b, wo, bo = _f32("wh", wh, 3), _f32("b", b, 2), _f32("wo", wo, 3), _f32("bo", bo, 2)
+        P, H, D = wx.shape
+        if P < 1:
+            raise ValueError("a policy set needs at least one policy")
+        if not (1 <= H <= MAX_RECURRENT_HIDDEN):
+            raise ValueError("hidden units must be in [1, %d], got %d" % (MAX_RECURRENT_HIDDEN, H))
+        if D not in OBS_DIMS:
+            raise ValueError("the observation has 16 entries (19 for velocity_control), wx has %d" % D)
+        if wa.shape != (P, H, 4) or wr.shape != (P, H) or wd.shape != (P, H) or wh.shape != (P, H, H) or b.shape != (P, H) or \
+                wo.shape != (P, 4, H) or bo.shape != (P, 4):
+            raise ValueError("shapes must be wx [P,H,D], wa [P,H,4], wr [P,H], wd [P,H], wh [P,H,H], b [P,H], wo [P,4,H], bo [P,4]; "
+                             "got %s %s %s %s %s %s %s %s" % (wx.shape, wa.shape, wr.shape, wd.shape, wh.shape, b.shape, wo.shape,
+                                                              bo.shape))
+        self.wx, self.wa, self.wr, self.wd, self.wh, self.b, self.wo, self.bo = wx, wa, wr, wd, wh, b, wo, bo
+        self.num_policies, self.hidden, self.obs_dim = P, H, D
+        self._device = {}
+
+    def __len__(self):
+        return self.num_policies
+
+    @property
+    def param_count(self):
+        return recurrent_param_count(self.hidden, self.obs_dim)
+
+    def pack(self):
+        """float32 [P, param_count]: the layout the kernel reads (documented in include/metagym_hip.h). bo[0..3], then per
+        hidden unit j a record of DP + HP + 12 floats (DP, HP: D, H rounded up to a multiple of 4): wx[j][0..D-1], zeros up
+        to DP; b[j], wr[j], wd[j], 0; wa[j][0..3]; wh[j][0..H-1], zeros up to HP; wo[0..3][j]. Every piece starts on a
+        multiple of four floats, so every 16-byte read is aligned."""
+        P, H, D = self.num_policies, self.hidden, self.obs_dim
+        DP, HP = _pad4(D), _pad4(H)
+        out = np.zeros((P, self.param_count), np.float32)
+        out[:, :_HEAD] = self.bo
+        rec = out[:, _HEAD:].reshape(P, H, _rrecord(H, D))
+        rec[:, :, :D] = self.wx
+        rec[:, :, DP] = self.b
+        rec[:, :, DP + 1] = self.wr
+        rec[:, :, DP + 2] = self.wd
+        rec[:, :, DP + 4:DP + 8] = self.wa
+        rec[:, :, DP + 8:DP + 8 + H] = self.wh
+        rec[:, :, DP + 8 + HP:] = self.wo.transpose(0, 2, 1)
+        return out
+
+    @classmethod
+    def unpack(cls, packed, hidden, obs_dim):
+        """The inverse of `pack`."""
+        packed = _f32("packed", packed, 2)
+        P, H, D = packed.shape[0], int(hidden), obs_dim
+        if packed.shape[1] != recurrent_param_count(H, D):
+            raise ValueError("packed has shape %s, hidden=%d and obs_dim=%d need [P, %d]"
+                             % (packed.shape, H, D, recurrent_param_count(H, D)))
+        DP, HP = _pad4(D), _pad4(H)
+        rec = packed[:, _HEAD:].reshape(P, H, _rrecord(H, D))
+        return cls(rec[:, :, :D].copy(), rec[:, :, DP + 4:DP + 8].copy(), rec[:, :, DP + 1].copy(), rec[:, :, DP + 2].copy(),
+                   rec[:, :, DP + 8:DP + 8 + H].copy(), rec[:, :, DP].copy(), rec[:, :, DP + 8 + HP:].transpose(0, 2, 1).copy(),
+                   packed[:, :_HEAD].copy())
+
+    def to(self, device):
+        """The packed parameters as a torch tensor on `device` (uploaded once per device)."""
+        import torch
+        from .. import _lib
+        key = str(_lib.canonical_device(device))
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.pack()).to(_lib.canonical_device(device)).contiguous()
+        return self._device[key]
+
+    def reference(self, obs, policy_ids, state):
+        """One step of the definition above in numpy float32, with exactly that association: the sums run one term at a
+        time over arrays of envs (x units), as in `QuadrotorPolicy.reference`. obs float32 [N, D], policy_ids [N], state a
+        `QuadrotorPolicyState` (read, never written). Returns (actions float32 [N, 4], new state): the new state is a numpy
+        carry with h = hn and prev_action = the actions; its prev_reward and prev_done are still the old ones, since they
+        come from the env step that follows (`QuadrotorPolicyState.observed`). The oracle of the policy half of a
+        recurrent closed-loop rollout."""
+        x = _np(obs)
+        ids = _np(policy_ids)
+        P, H, D = self.num_policies, self.hidden, self.obs_dim
+        if x.dtype != np.float32 or x.ndim != 2 or x.shape[1] != D:
+            raise ValueError("obs must be float32 [N, %d], got %s %s" % (D, x.dtype, x.shape))
+        N = x.shape[0]
+        if ids.shape != (N,) or ids.dtype.kind not in "iu":
+            raise ValueError("policy_ids must be %d integers" % N)
+        if N and (int(ids.min()) < 0 or int(ids.max()) >= P):
+            raise ValueError("policy_ids must be in [0, %d)" % P)
+        h, pa, pr, pd = _np(state.h), _np(state.prev_action), _np(state.prev_reward), _np(state.prev_done)
+        if h.shape != (N, H) or h.dtype != np.float32:
+            raise ValueError("state.h must be float32 [%d, %d], got %s %s" % (N, H, h.dtype, h.shape))
+        if pa.shape != (N, 4) or pa.dtype != np.float32 or pr.shape != (N,) or pr.dtype != np.float32 or pd.shape != (N,):
+            raise ValueError("state.prev_action (float32 [N, 4]) / prev_reward (float32 [N]) / prev_done ([N]) for N = %d" % N)
+        pdf = (pd != 0).astype(np.float32)
+        wx, wa, wr, wd, wh, b = self.wx[ids], self.wa[ids], self.wr[ids], self.wd[ids], self.wh[ids], self.b[ids]
+        wo = self.wo[ids]
+        one = np.float32(1.0)
+        hn = np.empty((N, H), np.float32)
+        a = self.bo[ids].copy()                            # [N, 4]
+        with np.errstate(all="ignore"):
+            for j in range(H):
+                z = b[:, j].copy()
+                for i in range(D):
+                    z = z + wx[:, j, i] * x[:, i]
+                for k in range(4):
+                    z = z + wa[:, j, k] * pa[:, k]
+                z = z + wr[:, j] * pr
+                z = z + wd[:, j] * pdf
+                for i in range(H):
+                    z = z + wh[:, j, i] * h[:, i]
+                hn[:, j] = np.where(z > one, one, np.where(z < -one, -one, z))
+            for j in range(H):
+                a = a + wo[:, :, j] * hn[:, j:j + 1]
+        assert a.dtype == np.float32 and a.shape == (N, 4) and hn.dtype == np.float32
+        return a, QuadrotorPolicyState(hn, a.copy(), pr.astype(np.float32), (pd != 0).astype(np.uint8))
+
+
 class PolicyRollout(object):
     """What `Quadrotor.rollout_policy` returns. Always: ret_total f64 [N] (the T float64 rewards added in step order),
     ret_episode f64 [N] (the rewards up to and including the first done), episode_len int32 [N] (steps added into
     ret_episode; T if the env was never done). With record=True also actions [T,N,4] (unclamped), obs [T,N,D],
-    reward [T,N], reward64 [T,N], done [T,N] bool, failed [T,N] uint8; otherwise those are None."""
-    __slots__ = ("ret_total", "ret_episode", "episode_len", "actions", "obs", "reward", "reward64", "done", "failed")
+    reward [T,N], reward64 [T,N], done [T,N] bool, failed [T,N] uint8; otherwise those are None. state: the end carry
+    (a `QuadrotorPolicyState`) of a call with a `QuadrotorRecurrentPolicy`, else None."""
+    __slots__ = ("ret_total", "ret_episode", "episode_len", "actions", "obs", "reward", "reward64", "done", "failed", "state")
 
     def __init__(self, ret_total, ret_episode, episode_len, actions=None, obs=None, reward=None, reward64=None, done=None,
-                 failed=None):
+                 failed=None, state=None):
         self.ret_total, self.ret_episode, self.episode_len = ret_total, ret_episode, episode_len
         self.actions, self.obs, self.reward, self.reward64, self.done, self.failed = actions, obs, reward, reward64, done, failed
+        self.state = state

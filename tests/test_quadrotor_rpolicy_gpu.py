@@ -1,0 +1,436 @@
+"""Quadrotor closed-loop rollouts with recurrent policies and a carry, on the GPU (Quadrotor.rollout_policy with a
+QuadrotorRecurrentPolicy). The central check is the replay identity of test_quadrotor_policy_gpu.py with the carry in it:
+QuadrotorRecurrentPolicy.reference, fed the recorded observations, rewards and dones step by step from the start carry,
+reproduces every recorded action and the end carry bit for bit (policy half), and the existing rollout(recorded actions)
+from the same state reproduces every record and the final state bit for bit (environment half)."""
+import numpy as np
+import pytest
+import torch
+
+import quadrotor_policy_cases as pc
+import quadrotor_rpolicy_cases as rc
+import quadrotor_tasks_cases as qc
+from test_quadrotor_gpu import _load_state
+
+pytestmark = pytest.mark.gpu
+N, T = rc.N, rc.T
+DEV = "cuda:0"
+RECORDS = ("actions", "obs", "reward", "reward64", "done", "failed")
+RETURNS = ("ret_total", "ret_episode", "episode_len")
+CARRY = ("h", "prev_action", "prev_reward", "prev_done")
+NEG0 = 0x80000000
+
+
+def _env(n=N, **kw):
+    import metagym_amd
+    kw.setdefault("task", "hovering_control")
+    return metagym_amd.make("quadrotor-v0", num_envs=n, device=DEV, **kw)
+
+
+def _fresh(n, hidden):
+    from metagym_amd.quadrotor import QuadrotorPolicyState
+    return QuadrotorPolicyState.zeros(n, hidden, DEV)
+
+
+def _same_state(a, b):
+    sa, sb = a.state_dict(), b.state_dict()
+    assert sorted(sa) == sorted(sb)
+    for k in sa:
+        if torch.is_tensor(sa[k]):
+            assert torch.equal(sa[k], sb[k]), k
+        else:                                              # np_random: (name, keys, pos, has_gauss, cached)
+            assert all(np.array_equal(u, v) for u, v in zip(sa[k], sb[k])), k
+
+
+def _bits(x):
+    return np.ascontiguousarray(x).view(np.uint32)
+
+
+def _same_carry(a, b):
+    """two carries (device or host) hold the same bits"""
+    a, b = a.numpy(), b.numpy()
+    for k in ("h", "prev_action", "prev_reward"):
+        assert np.array_equal(_bits(getattr(a, k)), _bits(getattr(b, k))), k
+    assert np.array_equal(a.prev_done, b.prev_done)
+
+
+def _returns(reward64, done):
+    """ret_total, ret_episode, episode_len as sequential float64 sums over the records, on the host"""
+    steps, n = reward64.shape
+    total, ep, length, ended = np.zeros(n), np.zeros(n), np.zeros(n, np.int32), np.zeros(n, bool)
+    for t in range(steps):
+        total = total + reward64[t]
+        ep = np.where(ended, ep, ep + reward64[t])
+        length = np.where(ended, length, length + 1).astype(np.int32)
+        ended = ended | done[t].astype(bool)
+    return total, ep, length
+
+
+def _check_returns(res):
+    total, ep, length = _returns(res.reward64.cpu().numpy(), res.done.cpu().numpy())
+    assert np.array_equal(res.ret_total.cpu().numpy().view(np.uint64), total.view(np.uint64))
+    assert np.array_equal(res.ret_episode.cpu().numpy().view(np.uint64), ep.view(np.uint64))
+    assert res.episode_len.dtype == torch.int32 and np.array_equal(res.episode_len.cpu().numpy(), length)
+
+
+def _policy_half(policy, ids, x0, start, res, episodic=False):
+    """`reference` fed the records step by step from the host carry `start`; returns the end carry it arrives at.
+    episodic: the carry of an env is cleared at its done (the caller's env has auto_reset)."""
+    obs_h, act_h = res.obs.cpu().numpy(), res.actions.cpu().numpy()
+    rew_h, done_h = res.reward.cpu().numpy(), res.done.cpu().numpy()
+    x, state = x0, start
+    for t in range(act_h.shape[0]):
+        a, state = policy.reference(x, ids, state)
+        assert np.array_equal(_bits(a), _bits(act_h[t])), t
+        state = state.observed(rew_h[t], done_h[t], clear=done_h[t] if episodic else None)
+        x = obs_h[t]
+    return state
+
+
+def _replay_identity(make, prepare, policy, ids, steps=T, episodic=False):
+    """make(): a fresh env; prepare(env): brings it to the start state and returns the observation it then holds."""
+    a = make()
+    x0 = prepare(a).clone()
+    sd = a.state_dict()
+    carry = _fresh(a.num_envs, policy.hidden)
+    res = a.rollout_policy(policy, steps, ids, record=True, state=carry, episodic=episodic)
+    assert res.state is carry                              # the caller's own object, updated in place
+    n, D = a.num_envs, a.obs_dim
+    assert res.actions.shape == (steps, n, 4) and res.obs.shape == (steps, n, D)
+    # policy half, the end carry included
+    end = _policy_half(policy, ids, x0.cpu().numpy(), _fresh(n, policy.hidden).numpy(), res, episodic)
+    _same_carry(end, carry)
+    # environment half: the existing open-loop rollout on the recorded actions
+    b = make()
+    prepare(b)
+    b.load_state_dict(sd)
+    obs, rew, done, failed = b.rollout(res.actions)
+    assert torch.equal(obs, res.obs) and torch.equal(rew, res.reward) and torch.equal(done, res.done)
+    assert torch.equal(failed, res.failed) and torch.equal(b._last_rollout_reward64, res.reward64)
+    _same_state(a, b)
+    # the persistent output buffers hold the last step
+    assert torch.equal(a._obs, res.obs[-1]) and torch.equal(a._reward, res.reward[-1]) and torch.equal(a._done, res.done[-1])
+    assert torch.equal(a._failed, res.failed[-1]) and torch.equal(a.reward64, res.reward64[-1])
+    _check_returns(res)
+    return a, res
+
+
+def _reset(seed=3):
+    return lambda env: env.reset(seed=seed)
+
+
+@pytest.mark.parametrize("hidden", rc.HIDDEN)
+def test_replay_identity_hovering(hidden):
+    env, res = _replay_identity(lambda: _env(), _reset(), rc.make_rpolicy(hidden), pc.layout_ids())
+    h = res.state.h.cpu().numpy()
+    assert (np.abs(h) == 1).any() and (np.abs(h) < 1).any()                # saturated and unsaturated memories at the end
+
+
+def test_replay_identity_velocity_control():
+    env, res = _replay_identity(lambda: _env(task="velocity_control", nt=40, seed=6), _reset(), rc.make_rpolicy(5, 19),
+                                pc.layout_ids())
+    assert res.obs.shape[2] == 19 and torch.equal(res.obs[0, :, 16:], env.velocity_targets[1].expand(N, 3))
+
+
+def test_replay_identity_velocity_control_largest_lds():
+    """H = 64 with D = 19: the largest dynamic LDS a launch asks for (57 360 bytes)"""
+    _replay_identity(lambda: _env(task="velocity_control", nt=40, seed=6), _reset(), rc.make_rpolicy(64, 19), pc.layout_ids())
+
+
+def test_replay_identity_no_collision_with_a_map(tmp_path):
+    p = tmp_path / "map.txt"
+    p.write_text(qc.map_text(qc.small_map()))
+    _replay_identity(lambda: _env(task="no_collision", map_file=str(p)), _reset(), rc.make_rpolicy(5), pc.layout_ids())
+
+
+def test_replay_identity_with_fused_auto_reset():
+    """nt = 4: every env ends at least two episodes in 12 steps. The memory survives each done, and the step after one
+    sees prev_done = 1 with the ending step's reward and action: that is what `reference` is fed here."""
+    env, res = _replay_identity(lambda: _env(nt=4, auto_reset=True, seed=11), _reset(), rc.make_rpolicy(5), pc.layout_ids())
+    assert int(env.episode.min()) >= 2
+    never_failed = (res.failed[:4] == 0).all(0)
+    assert bool(never_failed.any()) and bool((res.episode_len[never_failed] == 4).all())
+    # T = 12 ends on a done for those envs: the carry holds it, not a cleared one
+    st = res.state
+    ended = res.done[-1]
+    assert bool(ended.any()) and bool((st.prev_done[ended] == 1).all()) and bool((st.prev_done[~ended] == 0).all())
+    assert torch.equal(st.prev_reward, res.reward[-1]) and torch.equal(st.prev_action, res.actions[-1])
+    assert bool((st.h[ended] != 0).any())
+
+
+@pytest.fixture(scope="module")
+def mixed_run():
+    """auto_reset=False with the mixed task table, from random states: the tight row freezes some envs next to live ones."""
+    from metagym_amd.quadrotor import QuadrotorTaskTable
+    ids_t, ids_p, pol = qc.mixed_ids(), pc.layout_ids(), rc.make_rpolicy(5)
+    state = qc.random_batch(N, qc.STATE_SEED)
+    table = QuadrotorTaskTable(qc.mixed_configs())
+
+    def make():
+        env = _env()
+        env.set_task(table, ids_t)
+        return env
+
+    def prepare(env):
+        _load_state(env, *state)
+        return env.step(torch.as_tensor(pc.PRIME_ACTION))[0]
+
+    env, res = _replay_identity(make, prepare, pol, ids_p)
+    return dict(make=make, prepare=prepare, env=env, res=res, ids_t=ids_t, ids_p=ids_p, pol=pol, state=state)
+
+
+def test_mixed_table_freezes_failed_lanes_next_to_live_ones(mixed_run):
+    res, ids_t = mixed_run["res"], mixed_run["ids_t"]
+    failed_any = (res.failed != 0).any(0).cpu().numpy()
+    tight = failed_any[ids_t == 4]
+    assert tight.any() and (~tight).any()
+    assert not failed_any[ids_t != 4].any()
+
+
+def test_memory_is_live():
+    """With wh, wa, wr and wd zeroed the same policy gives different actions from step 2 on, and the zeroed form equals a
+    call-by-call evaluation that ignores the carry: a kernel that never swapped h and hn, or never loaded the previous
+    action, reward or done, would make the two agree."""
+    pol, ids = rc.make_rpolicy(5), pc.layout_ids()
+    flat = rc.without_memory(pol)
+    a, b = _env(nt=4, auto_reset=True, seed=11), _env(nt=4, auto_reset=True, seed=11)
+    x0 = a.reset(seed=3).cpu().numpy()
+    b.reset(seed=3)
+    ra = a.rollout_policy(pol, T, ids, record=True)
+    rb = b.rollout_policy(flat, T, ids, record=True)
+    assert torch.equal(ra.actions[0], rb.actions[0])                       # a fresh carry is all zero
+    for t in range(1, T):
+        assert not torch.equal(ra.actions[t], rb.actions[t]), t
+    zero = _fresh(N, 5).numpy()
+    x, act_h, obs_h = x0, rb.actions.cpu().numpy(), rb.obs.cpu().numpy()
+    for t in range(T):
+        assert np.array_equal(_bits(flat.reference(x, ids, zero)[0]), _bits(act_h[t])), t
+        x = obs_h[t]
+    # and with the memory, ignoring the carry is wrong from step 2 on
+    got, obs_a = ra.actions.cpu().numpy(), ra.obs.cpu().numpy()
+    assert all((_bits(pol.reference(obs_a[t - 1], ids, zero)[0]) != _bits(got[t])).any() for t in range(1, T))
+    assert bool((ra.state.h != 0).any()) and ra.state.h.shape == (N, 5)
+
+
+def test_record_off_and_splitting():
+    pol, ids = rc.make_rpolicy(5), pc.layout_ids()
+    mk = lambda: _env(nt=4, auto_reset=True, seed=13)
+    full, quiet, split = mk(), mk(), mk()
+    for env in (full, quiet, split):
+        env.reset(seed=2)
+    rf = full.rollout_policy(pol, T, ids, record=True)
+    rq = quiet.rollout_policy(pol, T, ids)
+    assert all(getattr(rq, k) is None for k in RECORDS)
+    for k in RETURNS:
+        assert torch.equal(getattr(rf, k), getattr(rq, k)), k
+    _same_state(full, quiet)
+    _same_carry(rf.state, rq.state)
+    assert torch.equal(full._obs, quiet._obs) and torch.equal(full.reward64, quiet.reward64)
+    # 12 = 5 + 7 through one state object
+    carry = _fresh(N, 5)
+    r5 = split.rollout_policy(pol, 5, ids, record=True, state=carry)
+    mid = carry.clone()
+    r7 = split.rollout_policy(pol, 7, ids, record=True, state=carry)
+    assert r5.state is carry and r7.state is carry
+    _same_state(full, split)
+    _same_carry(rf.state, carry)
+    for k in RECORDS:
+        assert torch.equal(torch.cat([getattr(r5, k), getattr(r7, k)]), getattr(rf, k)), k
+    _check_returns(r5)
+    _check_returns(r7)
+    _check_returns(rf)
+    # the clone taken in between was not touched by the second call
+    assert torch.equal(mid.prev_action, r5.actions[-1]) and not torch.equal(mid.h, carry.h)
+
+
+def test_staged_and_per_lane_policy_reads_give_the_same_bits():
+    """The same (env, policy) pairs laid out so that every wave holds one id (LDS route) and so that every wave holds
+    several (each lane reads global memory): each env gets the same bits, in the records, the state and the carry."""
+    pol = rc.make_rpolicy(64)
+    n = 192
+    ids_u = np.repeat(np.arange(3), 64)                    # wave w flies policy w
+    perm = (np.arange(n) % 3) * 64 + np.arange(n) // 3     # position i holds the pair perm[i]: ids 0, 1, 2, 0, 1, 2, ...
+    assert sorted(perm.tolist()) == list(range(n))
+    ids_m = ids_u[perm]
+    assert all(len(set(ids_u[w * 64:(w + 1) * 64])) == 1 and len(set(ids_m[w * 64:(w + 1) * 64])) == 3 for w in range(3))
+    rs = np.random.RandomState(21)
+    v, w = rs.uniform(-2, 2, (n, 3)), rs.uniform(-5, 5, (n, 3))
+    out = []
+    for ids, order in ((ids_u, np.arange(n)), (ids_m, perm)):
+        env = _env(n)
+        env.reset(init_velocity=v[order], init_angular_velocity=w[order])
+        out.append((env.rollout_policy(pol, T, ids, record=True), env.state_dict()))
+    (ru, su), (rm, sm) = out
+    p = torch.as_tensor(perm).cuda()
+    for k in RECORDS:
+        assert torch.equal(getattr(ru, k)[:, p], getattr(rm, k)), k
+    for k in RETURNS:
+        assert torch.equal(getattr(ru, k)[p], getattr(rm, k)), k
+    for k in CARRY:
+        assert torch.equal(getattr(ru.state, k)[p], getattr(rm.state, k)), k
+    for k in ("pos", "vel", "omega", "propw", "rot"):
+        assert torch.equal(su[k][:, p], sm[k]), k
+    assert torch.equal(su["ct"][p], sm["ct"])
+
+
+def test_episodic_clears_the_carry_at_a_done():
+    pol, ids = rc.make_rpolicy(5), pc.layout_ids()
+    mk = lambda: _env(nt=4, auto_reset=True, seed=11)
+    # the whole run equals `reference` with the clear applied at every done
+    env, res = _replay_identity(mk, _reset(), pol, ids, episodic=True)
+    st, ended = res.state, res.done[-1]
+    assert bool(ended.any())
+    for k in CARRY:                                        # all zero right after a done
+        assert not bool(getattr(st, k)[ended].any()), k
+    # one step further the cleared envs act as from a fresh carry on their new episode's first observation, and an env
+    # that is not done then keeps its carry
+    x = res.obs[-1].cpu().numpy()
+    nxt = env.rollout_policy(pol, 1, ids, record=True, state=st, episodic=True)
+    want = pol.reference(x, ids, _fresh(N, 5).numpy())[0]
+    e = ended.cpu().numpy()
+    assert np.array_equal(_bits(nxt.actions[0].cpu().numpy())[e], _bits(want)[e])
+    live = ~nxt.done[0]
+    assert bool(live.any()) and bool((st.h[live] != 0).any()) and torch.equal(st.prev_action[live], nxt.actions[0][live])
+    assert torch.equal(st.prev_reward[live], nxt.reward[0][live]) and not bool(st.prev_done[live].any())
+    # episodic=False from the same start: the same first episode, another action right after the first done
+    keep = mk()
+    keep.reset(seed=3)
+    rk = keep.rollout_policy(pol, T, ids, record=True)
+    first = int(res.done.any(1).nonzero()[0])
+    assert torch.equal(rk.actions[:first + 1], res.actions[:first + 1])
+    assert not torch.equal(rk.actions[first + 1], res.actions[first + 1])
+    with pytest.raises(ValueError):
+        _env(nt=4).rollout_policy(pol, 2, ids, episodic=True)              # nothing resets: nothing to clear at
+
+
+def test_negative_zero_pre_activation_on_the_device():
+    """test_quadrotor_rpolicy.py's signed-zero case through the launch, on all five units of an H = 5 policy (three padding
+    entries behind wh). From a fresh carry every input but x is +0; with b = -0 and every weight a zero signed against its
+    input each product is -0, so every z, every hn and, with bo = -0 and wo = 1, every action is -0. One padding term
+    0 * h multiplied in would turn a z into +0."""
+    from metagym_amd.quadrotor import QuadrotorRecurrentPolicy
+    f = np.float32
+    env = _env(70)
+    x0 = env.reset(init_velocity=np.zeros((70, 3)), init_angular_velocity=np.zeros((70, 3))).cpu().numpy()
+    assert np.array_equal(_bits(x0), np.tile(_bits(x0[:1]), (70, 1)))        # one state, one sign pattern
+    wx = np.tile(np.where(np.signbit(x0[0]), f(0.0), f(-0.0)).astype(f), (1, 5, 1))
+    neg = lambda *s: np.full(s, -0.0, f)
+    pol = QuadrotorRecurrentPolicy(wx, neg(1, 5, 4), neg(1, 5), neg(1, 5), neg(1, 5, 5), neg(1, 5), np.ones((1, 4, 5), f),
+                                   neg(1, 4))
+    res = env.rollout_policy(pol, 1, record=True)
+    assert np.array_equal(_bits(res.actions.cpu().numpy()), np.full((1, 70, 4), NEG0, np.uint32))
+    assert np.array_equal(_bits(res.state.h.cpu().numpy()), np.full((70, 5), NEG0, np.uint32))
+    a, new = pol.reference(x0, np.zeros(70, int), _fresh(70, 5).numpy())
+    assert np.array_equal(_bits(a), np.full((70, 4), NEG0, np.uint32)) and np.array_equal(_bits(new.h), np.full((70, 5), NEG0, np.uint32))
+
+
+def test_after_load_state_dict_the_launch_uses_the_state_not_the_stale_buffer():
+    pol, ids = rc.make_rpolicy(5), pc.layout_ids()
+    a, b = _env(), _env()
+    a.reset(seed=3)
+    x_true = a.step(torch.full((N, 4), 6.0))[0].clone()
+    sd = a.state_dict()
+    b.reset(seed=4)
+    stale = b.step(torch.full((N, 4), 9.0))[0].clone()
+    b.load_state_dict(sd)
+    assert torch.equal(b._obs, stale) and not torch.equal(stale, x_true)   # the buffer still shows the other state
+    ra = a.rollout_policy(pol, 3, ids, record=True)
+    rb = b.rollout_policy(pol, 3, ids, record=True)
+    want = pol.reference(x_true.cpu().numpy(), ids, _fresh(N, 5).numpy())[0]
+    assert np.array_equal(_bits(rb.actions[0].cpu().numpy()), _bits(want))
+    for k in RECORDS:
+        assert torch.equal(getattr(ra, k), getattr(rb, k)), k
+    _same_carry(ra.state, rb.state)
+
+
+def test_graph_capture_of_a_recurrent_rollout():
+    pol, ids = rc.make_rpolicy(5), pc.layout_ids()
+    mk = lambda: _env(nt=4, auto_reset=True, seed=8)
+    eager, graphed = mk(), mk()
+    for env in (eager, graphed):
+        env.reset(seed=5)
+    sd0 = graphed.state_dict()
+    carry_e, carry_g = _fresh(N, 5), _fresh(N, 5)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):                          # warm-up outside capture: module load, parameter and id upload
+        graphed.rollout_policy(pol, 6, ids, state=carry_g)
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):                              # one stream, one launch: no parallel branches
+        res = graphed.rollout_policy(pol, 6, ids, state=carry_g)
+    assert res.state is carry_g
+    graphed.load_state_dict(sd0)                           # the warm-up and the capture pass advanced the state ...
+    for k in CARRY:
+        getattr(carry_g, k).zero_()                        # ... and the carry
+    for i in range(2):
+        g.replay()
+        want = eager.rollout_policy(pol, 6, ids, state=carry_e)
+        for k in RETURNS:
+            assert torch.equal(getattr(res, k), getattr(want, k)), (k, i)
+        assert torch.equal(graphed._obs, eager._obs) and torch.equal(graphed.reward64, eager.reward64), i
+        _same_carry(carry_g, carry_e)
+    _same_state(eager, graphed)
+    assert bool((carry_g.h != 0).any())
+
+
+def test_refused_calls_leave_the_env_and_the_carry_untouched():
+    from metagym_amd.quadrotor import QuadrotorPolicyState
+    env = _env(70)
+    env.reset(seed=9)
+    pol = rc.make_rpolicy(5)
+    carry = env.rollout_policy(pol, 2).state                               # a carry that is not all zero
+    assert bool((carry.h != 0).any())
+    sd = env.state_dict()
+    outs = [t.clone() for t in (env._obs, env._reward, env._reward64, env._done, env._failed)]
+    kept = carry.clone()
+    for bad in (np.full(70, 3), np.full(70, -1), np.zeros(69, int)):       # an id out of range, too few ids
+        with pytest.raises(ValueError):
+            env.rollout_policy(pol, 4, bad, state=carry)
+    with pytest.raises(ValueError):
+        env.rollout_policy(rc.make_rpolicy(5, 19), 4, state=carry)         # a policy for velocity_control's 19 entries
+    with pytest.raises(ValueError):
+        env.rollout_policy(pol, 0, state=carry)
+    with pytest.raises(ValueError):
+        env.rollout_policy(pol, 4, state=_fresh(69, 5))                    # a state with another N
+    with pytest.raises(ValueError):
+        env.rollout_policy(rc.make_rpolicy(1), 4, state=carry)             # ... with another H
+    with pytest.raises(ValueError):
+        env.rollout_policy(pol, 4, state=QuadrotorPolicyState(*[getattr(carry, k).cpu() for k in CARRY]))   # another device
+    with pytest.raises(ValueError):
+        env.rollout_policy(pol, 4, state=QuadrotorPolicyState.zeros(70, 5))                                 # numpy arrays
+    with pytest.raises(ValueError):
+        env.rollout_policy(pol, 4, state=carry, episodic=True)             # the env has no auto_reset
+    with pytest.raises(TypeError):
+        env.rollout_policy(pol, 4, state=object())
+    torch.cuda.synchronize()
+    after = env.state_dict()
+    for k in sd:
+        if torch.is_tensor(sd[k]):
+            assert torch.equal(sd[k], after[k]), k
+    for u, v in zip(outs, (env._obs, env._reward, env._reward64, env._done, env._failed)):
+        assert torch.equal(u, v)
+    for k in CARRY:
+        assert torch.equal(getattr(kept, k), getattr(carry, k)), k
+    # and the env still runs from that carry: default ids are e % P
+    res = env.rollout_policy(pol, 3, record=True, state=carry)
+    want = pol.reference(outs[0].cpu().numpy(), np.arange(70) % rc.P, kept.numpy())[0]
+    assert np.array_equal(_bits(want), _bits(res.actions[0].cpu().numpy()))
+
+
+def test_the_mlp_path_is_untouched():
+    from metagym_amd.quadrotor import PolicyRollout
+    pol, ids = pc.make_policy(5), pc.layout_ids()
+    env = _env()
+    x0 = env.reset(seed=3).cpu().numpy()
+    res = env.rollout_policy(pol, 3, ids, record=True)
+    assert isinstance(res, PolicyRollout) and res.state is None
+    assert all(torch.is_tensor(getattr(res, k)) for k in RECORDS + RETURNS)
+    assert np.array_equal(_bits(pol.reference(x0, ids)), _bits(res.actions[0].cpu().numpy()))
+    sd = env.state_dict()
+    with pytest.raises(TypeError):
+        env.rollout_policy(pol, 3, ids, state=_fresh(N, 5))
+    with pytest.raises(TypeError):
+        env.rollout_policy(pol, 3, ids, episodic=True)
+    after = env.state_dict()
+    assert all(torch.equal(sd[k], after[k]) for k in sd if torch.is_tensor(sd[k]))
