@@ -975,6 +975,52 @@ int mg_walker_policy_rollout(const mg_walker_topology *topo, const mg_walker_mod
                              double *ret_episode, int32_t *episode_len, float *actions, float *reward, float *rewards5,
                              uint8_t *done, void *stream);
 
+/* mg_walker_rpolicy_rollout — mg_walker_policy_rollout with a policy that remembers: env e evaluates recurrent policy
+ * policy_id_d[e] on the observation row its last step produced, its previous action, reward and done, and a memory h that is
+ * carried from step to step, across episode ends and from call to call. Defined exactly: x[D] is the observation row the env's
+ * last step produced (obs0 at step 0), pa[A] the previous UNCLAMPED action (the value the `actions` record holds), pr the previous
+ * step's float32 reward record, pd the previous done, h[H] the memory (1 <= H <= 256). Every operation is float32, rounded
+ * once, never fused, in this order:
+ *     for j in 0..H-1:  z = b[j];  for i in 0..D-1: z = z + wx[j][i] * x[i];  for k in 0..A-1: z = z + wa[j][k] * pa[k]
+ *                       z = z + wr[j] * pr;  z = z + wd[j] * (pd ? 1 : 0);  for i in 0..H-1: z = z + wh[j][i] * h[i]
+ *                       hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+ *     h = hn
+ *     for k in 0..A-1:  a[k] = bo[k];  for j in 0..H-1: a[k] = a[k] + wo[k][j] * h[j]
+ * `a` goes into the step unclamped; the step clamps it to [-1, 1] like any caller's action. The clamp of hn is compares and
+ * selects: -0 stays -0 and a NaN pre-activation stays NaN. Given the actions, everything else is mg_walker_rollout on them.
+ * The carry (mg_walker_rpolicy_carry: h f32 [N][H], prev_action f32 [N][A], prev_reward f32 [N], prev_done u8 [N], device
+ * pointers, all zero for a fresh one) is read before the first step and written after the last, in place: n1 then n2 steps
+ * through one carry equal n1 + n2 steps in one call. With auto_reset the memory survives a done: the next step sees the new
+ * episode's first observation, pd = 1 and the ending step's reward and action. episodic != 0 zeroes all four fields of the env
+ * at that done instead. Without auto_reset an env steps on past its done and the carry is updated as on any other step.
+ * `policy` is an mg_walker_policy with 1 <= hidden <= 256 whose params_d holds n_policies blocks of
+ * mg_walker_rpolicy_param_count floats in this layout, input-major like mg_walker_policy's so that the lanes of a wave read
+ * consecutive floats (hidden unit j on lane j % 64, output k on lane k), with NO padding anywhere:
+ *     b[H], wx [D][H] (wx[j][i] at H + i H + j), wa [A][H], wr[H], wd[H], wh [H_in][H_out] (wh[j][i] at
+ *     H + (D + A + 2 + i) H + j), bo[A], wo [H][A] (wo[k][j] at H + (D + A + 2 + H) H + A + j A + k)
+ * obs0, obs, obs_every, the returns and the optional per-step records: as in mg_walker_policy_rollout.
+ * Refused on the host before anything is launched: everything mg_walker_policy_rollout refuses, with hidden outside [1, 256]
+ * (MG_ERR_BAD_SIZE); a NULL carry or a NULL pointer in it (MG_ERR_NULL_POINTER); episodic != 0 without prm->auto_reset
+ * (MG_ERR_BAD_CONFIG). Dynamic LDS: the step's, plus (D + A + 2 + 2 H) floats rounded up to 16 bytes: x, pa, pr, pd, h and hn
+ * (2 304 bytes for the humanoid at H = 256). Nothing is allocated and nothing synchronises (stream capture works as for the
+ * step). Additive entry points; MG_ABI_VERSION is unchanged. */
+typedef struct mg_walker_rpolicy_carry {
+    float *h;
+    float *prev_action;
+    float *prev_reward;
+    uint8_t *prev_done;
+} mg_walker_rpolicy_carry;
+
+/* Floats of one packed recurrent policy: H + (D + A + 2 + H) H + A + H A. Host only. A negative error code for hidden outside
+ * [1, 256], n_act outside [1, MG_WALKER_MAX_JOINTS] or obs_dim outside [1, 8 + 2 MG_WALKER_MAX_JOINTS + MG_WALKER_MAX_FEET]. */
+int32_t mg_walker_rpolicy_param_count(int32_t hidden, int32_t obs_dim, int32_t n_act);
+
+int mg_walker_rpolicy_rollout(const mg_walker_topology *topo, const mg_walker_models *models, const mg_walker_params *prm,
+                              int32_t n_envs, const mg_walker_state *state, int32_t n_steps, int32_t obs_every,
+                              const mg_walker_policy *policy, const mg_walker_rpolicy_carry *carry, int32_t episodic,
+                              const float *obs0, float *obs, double *ret_total, double *ret_episode, int32_t *episode_len,
+                              float *actions, float *reward, float *rewards5, uint8_t *done, void *stream);
+
 /* ========================================================================================
  * Quadrupedal (Unitree A1) — the ACTUATION path of metagym/quadrupedal/robots/minitaur.py + a1.py +
  * laikago_motor.py for N robots: everything `Minitaur._StepInternal` (minitaur.py:232-238) does on either side of

@@ -209,6 +209,11 @@ class WalkerPolicyDesc(C.Structure):
                 ("obs_dim", C.c_int32), ("n_act", C.c_int32)]
 
 
+class WalkerRPolicyCarry(C.Structure):
+    """mg_walker_rpolicy_carry (device pointers)"""
+    _fields_ = [("h", C.c_void_p), ("prev_action", C.c_void_p), ("prev_reward", C.c_void_p), ("prev_done", C.c_void_p)]
+
+
 A1_NUM_MOTORS, A1_OBS_DIM = 12, 43
 A1_MODE_POSITION, A1_MODE_TORQUE, A1_MODE_HYBRID = 1, 2, 3
 
@@ -399,6 +404,10 @@ SIGNATURES = {
     "mg_walker_policy_rollout": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
                                            C.c_int32, C.POINTER(WalkerState), C.c_int32, C.c_int32, C.POINTER(WalkerPolicyDesc),
                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mg_walker_rpolicy_param_count": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "mg_walker_rpolicy_rollout": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
+                                            C.c_int32, C.POINTER(WalkerState), C.c_int32, C.c_int32, C.POINTER(WalkerPolicyDesc),
+                                            C.POINTER(WalkerRPolicyCarry), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mg_a1_apply_action": (C.c_int, [C.POINTER(A1ActuatorConfig), C.c_int32, C.POINTER(A1ActuatorState), _P, _P,
                                      C.c_double, _P, _P]),
     "mg_a1_receive_observation": (C.c_int, [C.POINTER(A1ActuatorConfig), C.c_int32, C.POINTER(A1ActuatorState),

@@ -1876,6 +1876,44 @@ __device__ __forceinline__ float wave_policy_action(const float *__restrict__ p,
     }
     return a;
 }
+
+// The recurrent policy of include/metagym_hip.h (mg_walker_rpolicy_rollout), same mapping: hidden unit u on lane u % 64, output k
+// on lane k, every sum one lane's sequential loop in the order of the definition. The packed block is b[H], then ONE input-major
+// matrix [D + A + 2 + H][H] (the rows of wx, wa, wr, wd, wh in that order), then bo[A] and wo [H][A]; in[] = x[D], pa[A], pr, pd
+// (0.0f or 1.0f) lie in that order in LDS, so a unit's sum is two runs: over in[] and over h[]. hn is a second buffer: other
+// lanes still read h while a lane writes its unit. wave_rpolicy_sum reads a group of weights (L2) and inputs (LDS broadcasts)
+// ahead of the group's dependent adds, so that their latencies overlap at one wave per SIMD; the sum itself stays one term at a
+// time. The clamp is compares and selects: a NaN stays NaN, -0 stays -0.
+#ifndef MG_WALKER_RP_GROUP
+#define MG_WALKER_RP_GROUP 32     // weights and inputs read ahead of the sum (same bits for any value: the sum stays one term at a time)
+#endif
+__device__ __forceinline__ float wave_rpolicy_sum(float z, const float *__restrict__ w, int stride, const float *in, int n) {
+    constexpr int G = MG_WALKER_RP_GROUP;
+    int i = 0;
+    for (; i + G <= n; i += G) {
+        float wv[G], xv[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) { wv[g] = w[(size_t)(i + g) * stride]; xv[g] = in[i + g]; }
+#pragma unroll
+        for (int g = 0; g < G; ++g) z = z + wv[g] * xv[g];
+    }
+    for (; i < n; ++i) z = z + w[(size_t)i * stride] * in[i];
+    return z;
+}
+__device__ __forceinline__ float wave_rpolicy_action(const float *__restrict__ p, int H, int D, int A, const float *in, const float *h, float *hn, int lane) {
+    WSYNC();                                  // in[] and h[] were written by other lanes
+    const int n_in = D + A + 2;
+    for (int u = lane; u < H; u += WV) {
+        float z = wave_rpolicy_sum(p[u], p + H + u, H, in, n_in);
+        z = wave_rpolicy_sum(z, p + H + (size_t)n_in * H + u, H, h, H);
+        hn[u] = z > 1.0f ? 1.0f : (z < -1.0f ? -1.0f : z);
+    }
+    WSYNC();
+    p += (size_t)H + ((size_t)n_in + H) * H;
+    float a = 0.0f;
+    if (lane < A) a = wave_rpolicy_sum(p[lane], p + A + lane, A, hn, H);
+    return a;
+}
 #pragma clang fp contract(fast)
 
 // Waves per SIMD: two (<= 256 VGPRs) everywhere but in the tuned ant kernel — its 10.7 KB of LDS let 12 envs reside per CU, so
@@ -1907,7 +1945,10 @@ template <int NMAX, class SH, int ROLL> constexpr int WAVE_WAVES_PER_EU =
 // walker_policy.hip): where the rollout loads action[e * nj + lane], the wave evaluates the env's policy on the observation row
 // it produced last, a copy of which it keeps in LDS behind the slab and the model tail (x[obs_dim], then h[hidden]). `action` is
 // unused; `reward`, `rewards5`, `done` and roll.actions are optional records, and lane 0 adds up the env's returns.
-constexpr int WAVE_STEP = 0, WAVE_ROLLOUT = 1, WAVE_POLICY = 2;
+// ROLL = WAVE_RPOLICY: the policy form with a recurrent policy and its carry (mg_walker_rpolicy_rollout, instantiated in
+// walker_rpolicy.hip): the LDS tail is WaveRTail's, the carry is loaded into it before the step loop and stored after it.
+constexpr int WAVE_STEP = 0, WAVE_ROLLOUT = 1, WAVE_POLICY = 2, WAVE_RPOLICY = 3;
+constexpr bool wave_has_policy(int roll) { return roll == WAVE_POLICY || roll == WAVE_RPOLICY; }     // either closed-loop form
 template <int ROLL> struct WaveRoll { };
 template <> struct WaveRoll<WAVE_ROLLOUT> { int n_steps, obs_every; };
 template <> struct WaveRoll<WAVE_POLICY> {
@@ -1920,8 +1961,31 @@ template <> struct WaveRoll<WAVE_POLICY> {
     double *ret_total, *ret_episode;
     int32_t *episode_len;
 };
+template <> struct WaveRoll<WAVE_RPOLICY> {
+    int n_steps, obs_every;
+    const float *params;          // [n_policies][count]: the packed layout of include/metagym_hip.h (mg_walker_rpolicy_rollout)
+    const int32_t *policy_id;     // [N]
+    int n_policies, hidden, count;
+    const float *obs0;            // [N][obs_dim]: x of step 0
+    float *actions;               // [n_steps][N][nj] or null
+    double *ret_total, *ret_episode;
+    int32_t *episode_len;
+    float *h, *prev_action, *prev_reward;     // the carry: [N][hidden], [N][nj], [N]
+    uint8_t *prev_done;                       // [N]
+    int episodic;                 // != 0: a fused auto-reset zeroes the env's carry
+};
 // bytes of the policy form's LDS tail: x[obs_dim] and h[hidden]
 __host__ __device__ inline size_t wave_policy_tail_bytes(int obs_dim, int hidden) { return (((size_t)obs_dim + hidden) * sizeof(float) + 15) & ~size_t(15); }
+// The recurrent form's LDS tail, in floats from its start: x[obs_dim] at 0, pa[n_act] (the previous unclamped action), pr, pd (the
+// previous reward; the previous done as 0.0f / 1.0f), then the two memory buffers h[hidden] — buffer t & 1 holds h at step t,
+// the other takes hn. One function for wave_plan and the kernel.
+struct WaveRTail { int pa, pr, h, end; };
+__host__ __device__ inline WaveRTail wave_rpolicy_tail(int obs_dim, int n_act, int hidden) {
+    return WaveRTail{obs_dim, obs_dim + n_act, obs_dim + n_act + 2, obs_dim + n_act + 2 + 2 * hidden};
+}
+__host__ __device__ inline size_t wave_rpolicy_tail_bytes(int obs_dim, int n_act, int hidden) {
+    return ((size_t)wave_rpolicy_tail(obs_dim, n_act, hidden).end * sizeof(float) + 15) & ~size_t(15);
+}
 template <int NMAX, class SH, int ROLL = WAVE_STEP>
 __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu(WAVE_WAVES_PER_EU<NMAX, SH, ROLL>))) void walker_step_wave_kernel(mg_walker_topology tp, mg_walker_models ms,
                                                               mg_walker_params prm, mg_walker_state st, int n_envs,
@@ -2077,13 +2141,21 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu(WAVE_WAVES_P
     double ret_total = 0.0, ret_episode = 0.0;
     int episode_len = 0;
     bool episode_over = false;
-    if constexpr (ROLL == WAVE_POLICY) {
+    if constexpr (wave_has_policy(ROLL)) {
         int pid = __builtin_amdgcn_readfirstlane(roll.policy_id[e]);
         pid = pid < 0 ? 0 : (pid >= roll.n_policies ? roll.n_policies - 1 : pid);
         pol = roll.params + (size_t)pid * (size_t)roll.count;
         xl = reinterpret_cast<float *>(slab + plan.tail + (WAVE_MODEL_IN_LDS<NMAX, SH> ? wave_model_doubles(nb, nj) * sizeof(double) : 0));
         hl = xl + obs_dim;
         for (int i = lane; i < obs_dim; i += WV) xl[i] = roll.obs0[(size_t)e * obs_dim + i];     // (read before any row of obs is written)
+    }
+    // the recurrent form: the carry comes into the tail here and goes back after the step loop, which writes none of it to memory
+    WaveRTail rt{0, 0, 0, 0};
+    if constexpr (ROLL == WAVE_RPOLICY) {
+        rt = wave_rpolicy_tail(obs_dim, nj, roll.hidden);
+        for (int i = lane; i < roll.hidden; i += WV) xl[rt.h + i] = roll.h[(size_t)e * roll.hidden + i];
+        if (lane < nj) xl[rt.pa + lane] = roll.prev_action[(size_t)e * nj + lane];
+        if (lane == 0) { xl[rt.pr] = roll.prev_reward[e]; xl[rt.pr + 1] = roll.prev_done[e] != 0 ? 1.0f : 0.0f; }
     }
 env_step:
     if (ROLL) {
@@ -2092,6 +2164,14 @@ env_step:
             const float a = wave_policy_action(pol, roll.hidden, obs_dim, nj, xl, hl, lane);
             if (lane < nj) {
                 if (roll.actions != nullptr) roll.actions[((size_t)t * n_envs + e) * nj + lane] = a;
+                L.tau[lane] = motor_torque(prm, m.motor()[lane], a);
+            }
+        } else if constexpr (ROLL == WAVE_RPOLICY) {
+            float *hcur = xl + rt.h + ((t & 1) ? roll.hidden : 0), *hnew = xl + rt.h + ((t & 1) ? 0 : roll.hidden);
+            const float a = wave_rpolicy_action(pol, roll.hidden, obs_dim, nj, xl, hcur, hnew, lane);
+            if (lane < nj) {
+                if (roll.actions != nullptr) roll.actions[((size_t)t * n_envs + e) * nj + lane] = a;
+                xl[rt.pa + lane] = a;          // the next step's pa (every lane is past its hidden units: the WSYNC inside)
                 L.tau[lane] = motor_torque(prm, m.motor()[lane], a);
             }
         } else if (lane < nj) L.tau[lane] = motor_torque(prm, m.motor()[lane], action[(size_t)e * nj + lane]);
@@ -2136,7 +2216,7 @@ env_step:
         }
         at_limit = __popcll(__ballot(lim));
         if (lane < nj) { ob[8 + 2 * lane] = clip5(jp); ob[9 + 2 * lane] = clip5(jv); }
-        if (ROLL == WAVE_POLICY && lane < nj) { xl[8 + 2 * lane] = clip5(jp); xl[9 + 2 * lane] = clip5(jv); }     // the next step's x
+        if (wave_has_policy(ROLL) && lane < nj) { xl[8 + 2 * lane] = clip5(jp); xl[9 + 2 * lane] = clip5(jv); }     // the next step's x
         bool finite = isfinite(jp) && isfinite(jv);
         // feet in contact now: one ballot per foot over the proxies (lane = proxy), not a loop over the proxies per foot
         float cnow = 0.0f;
@@ -2152,12 +2232,12 @@ env_step:
         if (lane < nf) {
             if (after_reset) {
                 ob[8 + 2 * nj + lane] = 0.0f;
-                if (ROLL == WAVE_POLICY) xl[8 + 2 * nj + lane] = 0.0f;
+                if (wave_has_policy(ROLL)) xl[8 + 2 * nj + lane] = 0.0f;
                 st.feet_contact[(size_t)lane * n_envs + e] = 0.0f;
             } else {
                 const float prev = st.feet_contact[(size_t)lane * n_envs + e];
                 ob[8 + 2 * nj + lane] = clip5(prev);
-                if (ROLL == WAVE_POLICY) xl[8 + 2 * nj + lane] = clip5(prev);
+                if (wave_has_policy(ROLL)) xl[8 + 2 * nj + lane] = clip5(prev);
                 st.feet_contact[(size_t)lane * n_envs + e] = cnow;
             }
         }
@@ -2186,7 +2266,7 @@ env_step:
             head[3] = clip5((float)(0.3 * vx)); head[4] = clip5((float)(0.3 * vy)); head[5] = clip5((float)(0.3 * vz));
             head[6] = clip5((float)roll); head[7] = clip5((float)pitch);
             for (int i = 0; i < 8; ++i) { ob[i] = head[i]; finite = finite && isfinite(head[i]); }
-            if (ROLL == WAVE_POLICY)
+            if (wave_has_policy(ROLL))
                 for (int i = 0; i < 8; ++i) xl[i] = head[i];
         }
         all_finite = __all(finite);
@@ -2217,14 +2297,15 @@ env_step:
             const int steps = st.steps[e] + 1;
             st.steps[e] = steps;
             const float rew = (float)(alive + progress + 0.0 + limit_cost + 0.0);
-            if (ROLL != WAVE_POLICY || reward != nullptr) reward[e] = rew;       // (the policy form's per-step records are optional)
+            if (!wave_has_policy(ROLL) || reward != nullptr) reward[e] = rew;       // (the policy form's per-step records are optional)
             if (rewards5) {
                 float *r5 = rewards5 + (size_t)e * 5;
                 r5[0] = (float)alive; r5[1] = (float)progress; r5[2] = 0.0f; r5[3] = (float)limit_cost; r5[4] = 0.0f;
             }
             ended = (alive < 0) || !all_finite || (steps >= prm.max_steps);
-            if (ROLL != WAVE_POLICY || done != nullptr) done[e] = (uint8_t)ended;
-            if (ROLL == WAVE_POLICY) {      // the returns: the float32 rewards widened and added in step order; the episode's stops with the first done
+            if (!wave_has_policy(ROLL) || done != nullptr) done[e] = (uint8_t)ended;
+            if constexpr (ROLL == WAVE_RPOLICY) { xl[rt.pr] = rew; xl[rt.pr + 1] = ended ? 1.0f : 0.0f; }     // the next step's pr and pd
+            if (wave_has_policy(ROLL)) {      // the returns: the float32 rewards widened and added in step order; the episode's stops with the first done
                 ret_total = ret_total + (double)rew;
                 if (!episode_over) {
                     ret_episode = ret_episode + (double)rew;
@@ -2238,6 +2319,14 @@ env_step:
         // fused auto-reset: robot_specific_reset (walker_base.py:13-24) with device-side joint noise; the
         // returned obs row is the first observation of the next episode (vector-env convention)
         WSYNC();
+        if constexpr (ROLL == WAVE_RPOLICY) {
+            if (roll.episodic) {       // the new episode starts from the fresh carry: h (the buffer the next step reads), pa, pr, pd
+                float *hnext = xl + rt.h + ((t & 1) ? 0 : roll.hidden);
+                for (int i = lane; i < roll.hidden; i += WV) hnext[i] = 0.0f;
+                if (lane < nj) xl[rt.pa + lane] = 0.0f;
+                if (lane == 0) { xl[rt.pr] = 0.0f; xl[rt.pr + 1] = 0.0f; }
+            }
+        }
         if (lane < 3) {
             L.base[lane] = m.body_pos()[lane];
             L.base[12 + lane] = 0.0;
@@ -2251,7 +2340,7 @@ env_step:
         WSYNC();
     }
     if (ROLL && ++t < n_steps) {       // row t of the per-step arrays
-        if (ROLL == WAVE_POLICY) {
+        if (wave_has_policy(ROLL)) {
             if (reward != nullptr) reward += n_envs;
             if (done != nullptr) done += n_envs;
         } else {
@@ -2260,12 +2349,19 @@ env_step:
         if (rewards5) rewards5 += (size_t)n_envs * 5;
         goto env_step;
     }
-    if constexpr (ROLL == WAVE_POLICY) {
+    if constexpr (wave_has_policy(ROLL)) {
         if (lane == 0) {
             roll.ret_total[e] = ret_total;
             roll.ret_episode[e] = ret_episode;
             roll.episode_len[e] = episode_len;
         }
+    }
+    if constexpr (ROLL == WAVE_RPOLICY) {      // the end carry: t == n_steps here, so buffer t & 1 holds h
+        WSYNC();
+        const float *hend = xl + rt.h + ((t & 1) ? roll.hidden : 0);
+        for (int i = lane; i < roll.hidden; i += WV) roll.h[(size_t)e * roll.hidden + i] = hend[i];
+        if (lane < nj) roll.prev_action[(size_t)e * nj + lane] = xl[rt.pa + lane];
+        if (lane == 0) { roll.prev_reward[e] = xl[rt.pr]; roll.prev_done[e] = (uint8_t)(xl[rt.pr + 1] != 0.0f); }
     }
 #ifdef MG_WALKER_PROFILE
     if (lane == 0) atomicAdd(&mg_walker_phase_cycles[15], __builtin_readcyclecounter() - ph_k0);   // sub-steps + calc_state
@@ -2333,22 +2429,29 @@ struct WaveLaunch {
     decltype(&walker_step_wave_kernel<ND, ShapeAny>) kernel;
     decltype(&walker_step_wave_kernel<ND, ShapeAny, WAVE_ROLLOUT>) rollout;     // the same instantiation's n_steps-per-launch form
     decltype(&walker_step_wave_kernel<ND, ShapeAny, WAVE_POLICY>) policy;       // ... and its closed-loop form (walker_policy.hip)
+    decltype(&walker_step_wave_kernel<ND, ShapeAny, WAVE_RPOLICY>) rpolicy;     // ... with a recurrent policy (walker_rpolicy.hip)
     bool model_in_lds; WavePlan plan; size_t lds;
 };
-// (each translation unit instantiates the forms it launches: walker.hip the step and the rollout, walker_policy.hip the policy form)
+// (each translation unit instantiates the forms it launches: walker.hip the step and the rollout, walker_policy.hip the policy
+// form, walker_rpolicy.hip — which defines MG_WALKER_RPOLICY_ONLY besides MG_WALKER_POLICY_ONLY — the recurrent policy form)
 template <int NMAX, class SH>
 void wave_use(WaveLaunch *w) {
-#ifdef MG_WALKER_POLICY_ONLY
-    w->kernel = nullptr; w->rollout = nullptr; w->policy = walker_step_wave_kernel<NMAX, SH, WAVE_POLICY>;
+    w->kernel = nullptr; w->rollout = nullptr; w->policy = nullptr; w->rpolicy = nullptr;
+#if defined(MG_WALKER_RPOLICY_ONLY)
+    w->rpolicy = walker_step_wave_kernel<NMAX, SH, WAVE_RPOLICY>;
+#elif defined(MG_WALKER_POLICY_ONLY)
+    w->policy = walker_step_wave_kernel<NMAX, SH, WAVE_POLICY>;
 #else
-    w->kernel = walker_step_wave_kernel<NMAX, SH>; w->rollout = walker_step_wave_kernel<NMAX, SH, WAVE_ROLLOUT>; w->policy = nullptr;
+    w->kernel = walker_step_wave_kernel<NMAX, SH>; w->rollout = walker_step_wave_kernel<NMAX, SH, WAVE_ROLLOUT>;
 #endif
     w->model_in_lds = WAVE_MODEL_IN_LDS<NMAX, SH>; w->plan.fd = SH::fd;
 }
 
 // Every decision of a wave-mapping step, made on the host before anything is launched. policy_hidden >= 0: a launch of the
-// policy form with that many hidden units (its LDS tail, wave_policy_tail_bytes, comes behind the model tail).
-int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const mg_walker_state *st, WaveLaunch *w, int policy_hidden = -1) {
+// policy form with that many hidden units (its LDS tail, wave_policy_tail_bytes, comes behind the model tail; recurrent: the
+// recurrent form's, wave_rpolicy_tail_bytes).
+int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const mg_walker_state *st, WaveLaunch *w, int policy_hidden = -1,
+              bool recurrent = false) {
     const int nb = tp->n_bodies, nj = tp->n_joints, ns = tp->n_spheres, ndof = 6 + nj;
     if (ns > 128 || ndof > 64)
         return mg::set_error(MG_ERR_BAD_SIZE, "wave mapping needs <= 128 collision proxies and <= 58 joints");
@@ -2425,7 +2528,9 @@ int wave_plan(const mg_walker_topology *tp, const mg_walker_params *prm, const m
                              "mapping has %zu: use mapping = lane", (size_t)scan, (size_t)room);
     p.tail = (int)((lay.dend * sizeof(double) + lay.iend * sizeof(int) + 15) & ~size_t(15));
     w->lds = p.tail + (w->model_in_lds ? wave_model_doubles(nb, nj) * sizeof(double) : 0);
-    if (policy_hidden >= 0) w->lds += wave_policy_tail_bytes(8 + 2 * nj + tp->n_feet, policy_hidden);
+    if (policy_hidden >= 0)
+        w->lds += recurrent ? wave_rpolicy_tail_bytes(8 + 2 * nj + tp->n_feet, nj, policy_hidden)
+                            : wave_policy_tail_bytes(8 + 2 * nj + tp->n_feet, policy_hidden);
 #ifdef MG_WALKER_LDS_FLOOR      /* timing experiment only (scripts/walker_occupancy_probe.py): fewer resident envs per CU */
     if (const char *fl = getenv("MG_WALKER_LDS_FLOOR")) { const size_t f = (size_t)atol(fl); if (f > w->lds && f <= 64 * 1024) w->lds = f; }
 #endif

@@ -4,6 +4,7 @@ see DESIGN.md §3.5."""
 from . import variants
 from .mjcf import Model, load_mjcf
 from .walker_env import MetaHumanoidEnv, MetaAntEnv, WalkerBatchEnv
-from .policy import WalkerPolicy, WalkerPolicyRollout
+from .policy import WalkerPolicy, WalkerPolicyRollout, WalkerPolicyState, WalkerRecurrentPolicy
 
-__all__ = ["MetaHumanoidEnv", "MetaAntEnv", "WalkerBatchEnv", "WalkerPolicy", "WalkerPolicyRollout", "Model", "load_mjcf", "variants"]
+__all__ = ["MetaHumanoidEnv", "MetaAntEnv", "WalkerBatchEnv", "WalkerPolicy", "WalkerPolicyRollout", "WalkerRecurrentPolicy",
+           "WalkerPolicyState", "Model", "load_mjcf", "variants"]

@@ -16,6 +16,25 @@ against the env when a policy is used, not when it is built.
 
     pol = WalkerPolicy.linear(w, b)                        # w [P, 8, 28], b [P, 8], float32: P linear policies for the ant
     res = env.rollout_policy(pol, steps=64)                # env e runs policy e % P
+`WalkerRecurrentPolicy` is the form that remembers (include/metagym_hip.h, mg_walker_rpolicy_rollout): besides x it reads pa[A],
+the previous UNCLAMPED action (the value the `actions` record holds), pr, the previous step's float32 reward record, pd, the
+previous done, and a memory h[H] (1 <= H <= 256) carried from step to step, across episode ends and from call to call in a
+`WalkerPolicyState`. x is the observation row the env's last step produced; at step 0 it is `obs0`. Every operation is float32,
+rounded once, never fused, in this order:
+
+    for j in 0..H-1:  z = b[j];  for i in 0..D-1: z = z + wx[j][i] * x[i];  for k in 0..A-1: z = z + wa[j][k] * pa[k]
+                      z = z + wr[j] * pr;  z = z + wd[j] * (pd ? 1 : 0);  for i in 0..H-1: z = z + wh[j][i] * h[i]
+                      hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+    h = hn
+    for k in 0..A-1:  a[k] = bo[k];  for j in 0..H-1: a[k] = a[k] + wo[k][j] * h[j]
+
+`a` goes into the step unclamped. The clamp of hn is compares and selects: -0 stays -0 and a NaN pre-activation stays NaN.
+With `auto_reset` the memory survives a done: the next step sees the new episode's first observation, pd = 1 and the ending
+step's reward and action (the RL^2 trial); `episodic=True` zeroes the env's carry at that done instead.
+
+    rp = WalkerRecurrentPolicy(wx, wa, wr, wd, wh, b, wo, bo)
+    res = env.rollout_policy(rp, steps=64)                 # a fresh zero carry
+    res = env.rollout_policy(rp, steps=64, state=res.state)    # ... continued: 128 steps through one carry
 """
 import numpy as np
 
@@ -147,14 +166,217 @@ class WalkerPolicy(object):
         return a
 
 
+def recurrent_param_count(hidden, obs_dim, n_act):
+    """Floats per packed recurrent policy (what mg_walker_rpolicy_param_count returns): H + (D + A + 2 + H) H + A + H A."""
+    H, D, A = int(hidden), int(obs_dim), int(n_act)
+    if not (1 <= H <= MAX_HIDDEN):
+        raise ValueError("hidden units must be in [1, %d], got %r" % (MAX_HIDDEN, hidden))
+    if D < 1 or A < 1:
+        raise ValueError("a policy needs at least one input and one output, got obs_dim=%r n_act=%r" % (obs_dim, n_act))
+    return H + (D + A + 2 + H) * H + A + H * A
+
+
+def _np(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+class WalkerPolicyState(object):
+    """The carry of a recurrent closed-loop rollout, the policy's memory of each env: h float32 [N, H], prev_action float32
+    [N, A] (unclamped), prev_reward float32 [N], prev_done uint8 [N]. `WalkerPolicyState(num_envs, hidden, n_act, device)` is
+    the fresh carry, all zero: torch tensors on `device`, updated in place by a launch; device None gives numpy arrays, which
+    is what `WalkerRecurrentPolicy.reference` returns."""
+    __slots__ = ("h", "prev_action", "prev_reward", "prev_done")
+
+    def __init__(self, num_envs, hidden, n_act, device=None):
+        N, H, A = int(num_envs), int(hidden), int(n_act)
+        if N < 1 or not (1 <= H <= MAX_HIDDEN) or A < 1:
+            raise ValueError("a carry needs num_envs >= 1, hidden in [1, %d] and n_act >= 1, got %d, %d and %d" % (MAX_HIDDEN, N, H, A))
+        if device is None:
+            self.h, self.prev_action = np.zeros((N, H), np.float32), np.zeros((N, A), np.float32)
+            self.prev_reward, self.prev_done = np.zeros(N, np.float32), np.zeros(N, np.uint8)
+        else:
+            import torch
+            self.h = torch.zeros(N, H, dtype=torch.float32, device=device)
+            self.prev_action = torch.zeros(N, A, dtype=torch.float32, device=device)
+            self.prev_reward = torch.zeros(N, dtype=torch.float32, device=device)
+            self.prev_done = torch.zeros(N, dtype=torch.uint8, device=device)
+
+    @classmethod
+    def of(cls, h, prev_action, prev_reward, prev_done):
+        """A carry that holds the given arrays (not copied)."""
+        self = cls.__new__(cls)
+        self.h, self.prev_action, self.prev_reward, self.prev_done = h, prev_action, prev_reward, prev_done
+        return self
+
+    @property
+    def num_envs(self):
+        return int(self.h.shape[0])
+
+    @property
+    def hidden(self):
+        return int(self.h.shape[1])
+
+    @property
+    def n_act(self):
+        return int(self.prev_action.shape[1])
+
+    @property
+    def device(self):
+        """The torch device of the arrays; None for a numpy carry."""
+        return self.h.device if hasattr(self.h, "detach") else None
+
+    def clone(self):
+        c = (lambda v: v.clone()) if hasattr(self.h, "clone") else (lambda v: v.copy())
+        return WalkerPolicyState.of(c(self.h), c(self.prev_action), c(self.prev_reward), c(self.prev_done))
+
+    def numpy(self):
+        """A host copy, as numpy arrays: what `WalkerRecurrentPolicy.reference` takes."""
+        return WalkerPolicyState.of(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.float32),
+                                    _np(self.prev_reward).astype(np.float32), _np(self.prev_done).astype(np.uint8))
+
+    def observed(self, reward, done, clear=None):
+        """The numpy carry after the env step that followed `reference`: prev_reward = float32(reward), prev_done = done, h
+        and prev_action kept. `clear` (bool [N] or None): the envs whose four fields are zeroed afterwards, which is what
+        `episodic=True` does at a done with `auto_reset`."""
+        out = WalkerPolicyState.of(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.float32),
+                                   _np(reward).astype(np.float32), (_np(done) != 0).astype(np.uint8))
+        if out.prev_reward.shape != (self.num_envs,) or out.prev_done.shape != (self.num_envs,):
+            raise ValueError("reward and done must have shape (%d,)" % self.num_envs)
+        if clear is not None:
+            c = _np(clear).astype(bool)
+            if c.shape != (self.num_envs,):
+                raise ValueError("clear must have shape (%d,)" % self.num_envs)
+            out.h[c] = 0.0
+            out.prev_action[c] = 0.0
+            out.prev_reward[c] = 0.0
+            out.prev_done[c] = 0
+        return out
+
+
+class WalkerRecurrentPolicy(object):
+    """P recurrent policies: wx [P, H, D], wa [P, H, A], wr [P, H], wd [P, H], wh [P, H, H], b [P, H], wo [P, A, H], bo [P, A],
+    all float32 and finite, 1 <= H <= 256. D and A are checked against the env when the policy is used."""
+
+    def __init__(self, wx, wa, wr, wd, wh, b, wo, bo):
+        wx, wa, wr, wd = _f32("wx", wx, 3), _f32("wa", wa, 3), _f32("wr", wr, 2), _f32("wd", wd, 2)
+        wh, b, wo, bo = _f32("wh", wh, 3), _f32("b", b, 2), _f32("wo", wo, 3), _f32("bo", bo, 2)
+        P, H, D = wx.shape
+        A = wo.shape[1]
+        if P < 1 or D < 1 or A < 1:
+            raise ValueError("a policy set needs at least one policy, one input and one output; got wx %s, wo %s" % (wx.shape, wo.shape))
+        if not (1 <= H <= MAX_HIDDEN):
+            raise ValueError("hidden units must be in [1, %d], got %d" % (MAX_HIDDEN, H))
+        if wa.shape != (P, H, A) or wr.shape != (P, H) or wd.shape != (P, H) or wh.shape != (P, H, H) or b.shape != (P, H) or \
+                wo.shape != (P, A, H) or bo.shape != (P, A):
+            raise ValueError("shapes must be wx [P,H,D], wa [P,H,A], wr [P,H], wd [P,H], wh [P,H,H], b [P,H], wo [P,A,H], bo [P,A]; "
+                             "got %s %s %s %s %s %s %s %s" % (wx.shape, wa.shape, wr.shape, wd.shape, wh.shape, b.shape, wo.shape,
+                                                              bo.shape))
+        self.wx, self.wa, self.wr, self.wd, self.wh, self.b, self.wo, self.bo = wx, wa, wr, wd, wh, b, wo, bo
+        self.num_policies, self.hidden, self.obs_dim, self.n_act = P, H, D, A
+        self._device = {}
+
+    def __len__(self):
+        return self.num_policies
+
+    @property
+    def param_count(self):
+        return recurrent_param_count(self.hidden, self.obs_dim, self.n_act)
+
+    def pack(self):
+        """float32 [P, param_count]: the layout the kernel reads (documented in include/metagym_hip.h), input-major so that
+        the lanes of a wave read consecutive floats, no padding: b[H], wx [D][H], wa [A][H], wr[H], wd[H], wh [H_in][H_out],
+        bo[A], wo [H][A]."""
+        P, H, D, A = self.num_policies, self.hidden, self.obs_dim, self.n_act
+        t = lambda w: w.transpose(0, 2, 1).reshape(P, -1)
+        out = np.ascontiguousarray(np.concatenate([self.b, t(self.wx), t(self.wa), self.wr, self.wd, t(self.wh), self.bo,
+                                                   t(self.wo)], axis=1), dtype=np.float32)
+        assert out.shape == (P, self.param_count)
+        return out
+
+    @classmethod
+    def unpack(cls, packed, hidden, obs_dim, n_act):
+        """The inverse of `pack`."""
+        packed = _f32("packed", packed, 2)
+        P, H, D, A = packed.shape[0], int(hidden), int(obs_dim), int(n_act)
+        if packed.shape[1] != recurrent_param_count(H, D, A):
+            raise ValueError("packed has shape %s, hidden=%d, obs_dim=%d and n_act=%d need [P, %d]"
+                             % (packed.shape, H, D, A, recurrent_param_count(H, D, A)))
+        at = [0]
+
+        def take(rows, cols):              # the next [rows][cols] block, transposed back to [P, cols, rows]
+            blk = packed[:, at[0]:at[0] + rows * cols].reshape(P, rows, cols)
+            at[0] += rows * cols
+            return blk.transpose(0, 2, 1).copy()
+        b = take(1, H)[:, :, 0]
+        wx, wa = take(D, H), take(A, H)
+        wr, wd = take(1, H)[:, :, 0], take(1, H)[:, :, 0]
+        wh = take(H, H)
+        bo = take(1, A)[:, :, 0]
+        wo = take(H, A)
+        return cls(wx, wa, wr, wd, wh, b, wo, bo)
+
+    def to(self, device):
+        """The packed parameters as a torch tensor on `device` (uploaded once per device)."""
+        import torch
+        from .. import _lib
+        key = str(_lib.canonical_device(device))
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.pack()).to(_lib.canonical_device(device)).contiguous()
+        return self._device[key]
+
+    def reference(self, obs, policy_ids, state):
+        """One step of the definition in numpy float32, with exactly that association: every unit's sum runs one term at a
+        time over [N, H] arrays and every output's over [N, A] arrays (D + A + 2 + H + H array operations per step). obs
+        float32 [N, D], policy_ids [N], state a `WalkerPolicyState` (read, never written). Returns (actions float32 [N, A],
+        new state): a numpy carry with h = hn and prev_action = the actions; its prev_reward and prev_done are still the old
+        ones, since they come from the env step that follows (`WalkerPolicyState.observed`). The oracle of the policy half
+        of a recurrent closed-loop rollout."""
+        x = _np(obs)
+        ids = _np(policy_ids)
+        P, H, D, A = self.num_policies, self.hidden, self.obs_dim, self.n_act
+        if x.dtype != np.float32 or x.ndim != 2 or x.shape[1] != D:
+            raise ValueError("obs must be float32 [N, %d], got %s %s" % (D, x.dtype, x.shape))
+        N = x.shape[0]
+        if ids.shape != (N,) or ids.dtype.kind not in "iu":
+            raise ValueError("policy_ids must be %d integers" % N)
+        if N and (int(ids.min()) < 0 or int(ids.max()) >= P):
+            raise ValueError("policy_ids must be in [0, %d)" % P)
+        h, pa, pr, pd = _np(state.h), _np(state.prev_action), _np(state.prev_reward), _np(state.prev_done)
+        if h.shape != (N, H) or h.dtype != np.float32:
+            raise ValueError("state.h must be float32 [%d, %d], got %s %s" % (N, H, h.dtype, h.shape))
+        if pa.shape != (N, A) or pa.dtype != np.float32 or pr.shape != (N,) or pr.dtype != np.float32 or pd.shape != (N,):
+            raise ValueError("state.prev_action (float32 [N, %d]) / prev_reward (float32 [N]) / prev_done ([N]) for N = %d" % (A, N))
+        pdf = (pd != 0).astype(np.float32)
+        wx, wa, wr, wd, wh, wo = self.wx[ids], self.wa[ids], self.wr[ids], self.wd[ids], self.wh[ids], self.wo[ids]
+        one = np.float32(1.0)
+        with np.errstate(all="ignore"):
+            z = self.b[ids].copy()                         # [N, H]: every unit's own sum, in the order of the definition
+            for i in range(D):
+                z = z + wx[:, :, i] * x[:, i:i + 1]
+            for k in range(A):
+                z = z + wa[:, :, k] * pa[:, k:k + 1]
+            z = z + wr * pr[:, None]
+            z = z + wd * pdf[:, None]
+            for i in range(H):
+                z = z + wh[:, :, i] * h[:, i:i + 1]
+            hn = np.where(z > one, one, np.where(z < -one, -one, z))
+            a = self.bo[ids].copy()                        # [N, A]
+            for j in range(H):
+                a = a + wo[:, :, j] * hn[:, j:j + 1]
+        assert a.dtype == np.float32 and a.shape == (N, A) and hn.dtype == np.float32 and hn.shape == (N, H)
+        return a, WalkerPolicyState.of(hn, a.copy(), pr.astype(np.float32), (pd != 0).astype(np.uint8))
+
+
 class WalkerPolicyRollout(object):
     """What `WalkerBatchEnv.rollout_policy` returns. Always: ret_total f64 [N] (the T float32 rewards widened and added in step
     order), ret_episode f64 [N] (the rewards up to and including the first done), episode_len int32 [N] (steps added into
     ret_episode; T if the env was never done), obs (the persistent [N, D] buffer for obs_every = 0, else [K, N, D]) and
     obs_steps (the K recorded step indices). With record=True also actions [T,N,nj] (unclamped), reward [T,N], done [T,N]
-    bool, rewards5 [T,N,5]; otherwise those are None."""
-    __slots__ = ("ret_total", "ret_episode", "episode_len", "obs", "obs_steps", "actions", "reward", "done", "rewards5")
+    bool, rewards5 [T,N,5]; otherwise those are None. state: the end carry (a `WalkerPolicyState`) of a rollout with a
+    `WalkerRecurrentPolicy`, else None."""
+    __slots__ = ("ret_total", "ret_episode", "episode_len", "obs", "obs_steps", "actions", "reward", "done", "rewards5", "state")
 
     def __init__(self, ret_total, ret_episode, episode_len, obs, obs_steps, actions=None, reward=None, done=None, rewards5=None):
         self.ret_total, self.ret_episode, self.episode_len, self.obs, self.obs_steps = ret_total, ret_episode, episode_len, obs, obs_steps
         self.actions, self.reward, self.done, self.rewards5 = actions, reward, done, rewards5
+        self.state = None

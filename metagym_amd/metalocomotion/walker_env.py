@@ -424,9 +424,9 @@ class WalkerBatchEnv(object):
             info["rewards"] = r5
         return obs, reward, done, info
 
-    def rollout_policy(self, policy, steps, policy_ids=None, record=False, obs_every=0, obs0=None):
-        """`steps` closed-loop env steps in ONE launch: env e evaluates policy `policy_ids[e]` of `policy` (a `WalkerPolicy`;
-        `policy_ids=None` = e % P, else `num_envs` integers in [0, P), checked on the host) on its own observation inside the
+    def rollout_policy(self, policy, steps, policy_ids=None, record=False, obs_every=0, obs0=None, state=None, episodic=False):
+        """`steps` closed-loop env steps in ONE launch: env e evaluates policy `policy_ids[e]` of `policy` (a `WalkerPolicy` or
+        a `WalkerRecurrentPolicy`; `policy_ids=None` = e % P, else `num_envs` integers in [0, P), checked on the host) on its own observation inside the
         kernel and steps with the result, the robot staying in LDS. Given the actions the policy produces, everything else is
         `rollout(actions)`: same physics, rewards, dones, fused auto-resets (an env that ends an episode goes on with the first
         observation of the next one) and end state, bit for bit; works after `set_task` with the Models of any robot the wave
@@ -440,10 +440,20 @@ class WalkerBatchEnv(object):
         observation that belongs to the checkpoint as `obs0`. `global_step` advances by `steps`; the persistent reward and
         done buffers of `step` are not written. Nothing synchronises when `policy_ids` is None, a host array, or the device
         tensor of the previous call; any other device tensor is read back once to validate it. A refused call (an id out of
-        range, a policy of another observation or action width) raises and leaves the env as it was."""
-        from .policy import WalkerPolicy, WalkerPolicyRollout
-        if not isinstance(policy, WalkerPolicy):
-            raise TypeError("policy must be a WalkerPolicy, got %s" % type(policy).__name__)
+        range, a policy of another observation or action width) raises and leaves the env as it was.
+
+        With a `WalkerRecurrentPolicy`, `state` is the carry (a `WalkerPolicyState` on the env's device, updated in place;
+        None = a fresh zero carry) and the result's `state` is the end carry: the caller's own object if one was passed.
+        T1 then T2 steps through one state object equal T1 + T2 steps in one call. The memory survives a done;
+        `episodic=True` (only with `auto_reset`) zeroes the carry of an env at its done instead. A refused call leaves the
+        carry as it was too. `state` and `episodic` belong to the recurrent form: with a `WalkerPolicy` they raise
+        TypeError."""
+        from .policy import WalkerPolicy, WalkerPolicyRollout, WalkerPolicyState, WalkerRecurrentPolicy
+        recurrent = isinstance(policy, WalkerRecurrentPolicy)
+        if not recurrent and not isinstance(policy, WalkerPolicy):
+            raise TypeError("policy must be a WalkerPolicy or a WalkerRecurrentPolicy, got %s" % type(policy).__name__)
+        if not recurrent and (state is not None or episodic):
+            raise TypeError("state and episodic belong to a WalkerRecurrentPolicy; a WalkerPolicy has no memory")
         if not self._robot_set:
             raise Exception("BaseBulletEnv::_reset: must call set_robot and set_scene first")   # env_bases.py:68-69
         T, N, dev, P = int(steps), self.num_envs, self.device, policy.num_policies
@@ -459,6 +469,23 @@ class WalkerBatchEnv(object):
             if tuple(x0.shape) != (N, self.obs_dim) or x0.dtype != torch.float32:
                 raise ValueError("obs0 must be float32 [%d, %d], got %s %s" % (N, self.obs_dim, x0.dtype, tuple(x0.shape)))
             x0 = x0.to(dev).contiguous()
+        if recurrent:
+            if episodic and not self.auto_reset:
+                raise ValueError("episodic=True clears the carry at a fused reset: it needs an env built with auto_reset=True")
+            if state is not None:
+                if not isinstance(state, WalkerPolicyState):
+                    raise TypeError("state must be a WalkerPolicyState, got %s" % type(state).__name__)
+                fields = (state.h, state.prev_action, state.prev_reward, state.prev_done)
+                if not all(isinstance(t, torch.Tensor) for t in fields):
+                    raise ValueError("state must hold torch tensors on %s (WalkerPolicyState(N, H, A, device))" % dev)
+                if any(t.device != dev for t in fields):
+                    raise ValueError("state lives on %s, the env on %s" % (state.h.device, dev))
+                want = (((N, policy.hidden), torch.float32), ((N, self.n_joints), torch.float32), ((N,), torch.float32),
+                        ((N,), torch.uint8))
+                for t, (shape, dtype), name in zip(fields, want, WalkerPolicyState.__slots__):
+                    if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                        raise ValueError("state.%s must be a contiguous %s tensor of shape %s (num_envs=%d, hidden=%d, n_act=%d), "
+                                         "got %s %s" % (name, dtype, shape, N, policy.hidden, self.n_joints, t.dtype, tuple(t.shape)))
         ids_d = self._policy_ids(policy_ids, P)
         params = policy.to(dev)
         desc = _lib.WalkerPolicyDesc(params.data_ptr(), ids_d.data_ptr(), P, policy.hidden, policy.obs_dim, policy.n_act)
@@ -472,6 +499,20 @@ class WalkerBatchEnv(object):
             res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
             res.rewards5 = torch.empty(T, N, 5, dtype=torch.float32, device=dev)
         self._params_c.step_index = self.global_step
+        if recurrent:
+            if state is None:
+                state = WalkerPolicyState(N, policy.hidden, self.n_joints, dev)
+            carry = _lib.WalkerRPolicyCarry(state.h.data_ptr(), state.prev_action.data_ptr(), state.prev_reward.data_ptr(),
+                                            state.prev_done.data_ptr())
+            rc = self._lib.mg_walker_rpolicy_rollout(self._topo, self._models_c, self._params_c, N, self._state_c, T,
+                                                     int(obs_every), desc, carry, int(bool(episodic)), _lib.ptr(x0), _lib.ptr(obs),
+                                                     _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len),
+                                                     _lib.ptr(res.actions), _lib.ptr(res.reward), _lib.ptr(res.rewards5),
+                                                     _lib.ptr(res.done), _lib.current_stream(dev))
+            _lib.check(rc, "mg_walker_rpolicy_rollout")
+            self.global_step += T
+            res.state = state
+            return res
         rc = self._lib.mg_walker_policy_rollout(self._topo, self._models_c, self._params_c, N, self._state_c, T, int(obs_every),
                                                 desc, _lib.ptr(x0), _lib.ptr(obs), _lib.ptr(res.ret_total),
                                                 _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len), _lib.ptr(res.actions),
