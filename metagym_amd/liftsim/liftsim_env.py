@@ -101,6 +101,8 @@ def custom_tables(flow, floors, dt):
             pix = prob[i, j].astype(np.float64)
             rem = 1.0
             for c in range(F - 1):                    # random_multinomial: p_c / remaining_p, then random_binomial's flip
+                if rem == 0.0:                        # a category with p == 1 took every person: numpy has left its loop
+                    break
                 p = float(pix[c]) / rem
                 rem -= float(pix[c])
                 if p > 0.5:
