@@ -1544,6 +1544,76 @@ int mg_liftsim_rollout(const mg_liftsim_config *cfg, int32_t n_envs, void *arena
                        int32_t n_steps, double *ret, double *rec_reward, double *rec_time_consume,
                        double *rec_energy_consume, int32_t *rec_given_up, int32_t *rec_actions, void *stream);
 
+/* ---- LiftSim closed-loop rollouts: learned dispatchers inside the launch (additive; MG_ABI_VERSION unchanged) ----
+ *
+ * mg_liftsim_rollout with the dispatcher a small network: building e is dispatched by policy policy_ids[e] of the
+ * n_policies packed networks. The network is shared by the building's elevators: at every step it is evaluated once per
+ * elevator, on that elevator's state plus the building's hall calls, and its argmax is that elevator's
+ * (DispatchTarget, DispatchTargetDirection). The step is mg_liftsim_step's, unchanged: replaying the recorded actions
+ * through mg_liftsim_rollout (ACTIONS) or mg_liftsim_step from the same arena reproduces every record and the end arena.
+ *
+ * The policy, defined exactly. F floors, E elevators, H hidden ReLU units (1 <= H <= 64), A = 2F + 2 choices. Every
+ * operation is float32, rounded once, never fused, in this order; a double input is first converted to float32 (round to
+ * nearest even). For elevator el of an env, from the state as it stands before the step (after the stream refill, which
+ * changes no state); the E elevators of a step are all evaluated on that same state:
+ *   x[0..7] = f32(raw[i]) * scale[i]
+ *             raw = Floor, Velocity, Direction, DoorState, LoadWeight, OverloadedAlarm, DoorIsOpening (0/1),
+ *                   DoorIsClosing (0/1)
+ *   for j in 0..H-1:
+ *       z = b[j]
+ *       for i in 0..7:  z = z + ws[j][i] * x[i]
+ *       z = z + we[j][el]
+ *       d = CurrentDispatchTarget;  if 0 <= d <= F:  z = z + wt[j][d]
+ *       for f in 1..F ascending, if f in ReservedTargetFloors[el]:   z = z + wr[j][f-1]
+ *       for f in 1..F ascending, if f in RequiringUpwardFloors:      z = z + wu[j][f-1]
+ *       for f in 1..F ascending, if f in RequiringDownwardFloors:    z = z + wd[j][f-1]
+ *       h[j] = (z > 0) ? z : 0
+ *   for c in 0..A-1:  l[c] = bo[c];  for j in 0..H-1:  l[c] = l[c] + wo[c][j] * h[j]
+ *   choice = 0;  for c in 1..A-1:  if l[c] > l[choice]:  choice = c
+ * One-hot and bit inputs are lookups: each costs one add, or none, never a multiply-add (a pre-activation of -0 stays -0
+ * whatever the weights hold; walking a bit set and multiplying a dense 0/1 vector would differ there). Ties and NaN
+ * logits resolve to the lowest index.
+ * Choice to action: c < F: (c + 1, +1); F <= c < 2F: (c - F + 1, -1); c = 2F: (0, 1), the rule dispatcher's "nothing";
+ * c = 2F + 1: (-1, 1), no new dispatch, the standing one stays. All pass mg_liftsim_step's range check: a policy never
+ * sets INVALID.
+ * An env frozen by OVERFLOW or UNSUPPORTED when a step begins evaluates nothing and records (0, 0) per elevator, as the
+ * RULE rollout does; it stays in the loop for the wave's refills.
+ *
+ * Packed parameters, DEVICE f32, 16-byte aligned, mg_liftsim_policy_param_count(H, F, E) floats per policy, policy p at
+ * params + p * count. With P4(n) = n rounded up to a multiple of 4, RU = 12 + P4(E) + P4(F+1) + 3 P4(F), RC = 4 + P4(H):
+ *   one record of RU floats per hidden unit j, at RU j, its groups in this order, each zero-padded to a multiple of 4:
+ *     [0] b[j], [1..3] 0 | [4..11] ws[j][0..7] | we[j][0..E-1] | wt[j][0..F] | wr[j][0..F-1] | wu[j][0..F-1] |
+ *     wd[j][0..F-1]
+ *   then one record of RC floats per choice c, at H RU + RC c:
+ *     [0] bo[c], [1..3] 0 | [4 .. 3+H] wo[c][0..H-1], zeros up to [3+P4(H)]
+ *   (count = H RU + A RC; F = 128, E = 32, H = 64: 53 384 floats)
+ * so every record, every group and every 16-byte read starts on a multiple of four floats. The padding is never added
+ * into a sum. Parameters must be finite and are read-only for the launch. scale is the same for all policies. */
+typedef struct mg_liftsim_policy {
+    const float *params;               /* DEVICE f32 [n_policies][count] */
+    int32_t n_policies, hidden, floors, elevators;
+    float scale[8];                    /* x[i] = f32(raw[i]) * scale[i] */
+} mg_liftsim_policy;
+
+/* Floats per packed policy (host only); MG_ERR_BAD_SIZE for hidden outside [1, 64], floors outside [2, 128] or elevators
+ * outside [1, 32]. */
+int32_t mg_liftsim_policy_param_count(int32_t hidden, int32_t floors, int32_t elevators);
+
+/* One launch of n_steps steps: one lane per building, one wave per workgroup. policy_ids i32 [N], each in
+ * [0, n_policies): validated by the caller (the kernel clamps an id, it never reads outside the parameters). A wave whose
+ * envs all hold one id stages that policy in LDS when the launch's LDS need fits the 160 KiB of a workgroup (decided on
+ * the host, for the whole launch); otherwise every lane reads its own policy from global memory. The result does not
+ * depend on it. ret and the optional records are mg_liftsim_rollout's; rec_actions (i32 [n_steps][N][2E]) holds the
+ * actions the policy chose, (0, 0) for an env that was frozen when the step began.
+ * Refused on the host, before anything is launched: NULL required pointers (MG_ERR_NULL_POINTER); n_envs <= 0,
+ * n_steps < 1, n_policies < 1, hidden outside [1, 64] (MG_ERR_BAD_SIZE); floors or elevators different from the
+ * config's, params not 16-byte aligned, whatever mg_liftsim_step refuses in cfg (MG_ERR_BAD_CONFIG). Nothing is allocated
+ * and nothing synchronises: the call is hipGraph-capturable as it stands. */
+int mg_liftsim_policy_rollout(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, int32_t n_steps,
+                              const mg_liftsim_policy *policy, const int32_t *policy_ids, double *ret, double *rec_reward,
+                              double *rec_time_consume, double *rec_energy_consume, int32_t *rec_given_up,
+                              int32_t *rec_actions, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

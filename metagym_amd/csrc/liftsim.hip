@@ -995,6 +995,7 @@ dim3 grid(int32_t n) { return dim3((unsigned)(((int64_t)n + 63) / 64)); }
 
 }  // namespace
 
+#ifndef MG_LIFTSIM_CORE_ONLY   // liftsim_policy.hip takes the device functions and the host checks above, and none of what follows
 extern "C" int mg_liftsim_layout(const mg_liftsim_config *cfg, int32_t n_envs, int64_t *offsets, int64_t *total_bytes) {
     MG_REQUIRE_PTR(cfg);
     MG_REQUIRE_PTR(offsets);
@@ -1093,3 +1094,4 @@ extern "C" int mg_liftsim_rollout(const mg_liftsim_config *cfg, int32_t n_envs, 
                            fold(cfg), lay(cfg, n_envs), n_envs, static_cast<uint8_t *>(arena), actions, n_steps, rec);
     return mg::check_launch("liftsim_rollout_kernel");
 }
+#endif   // MG_LIFTSIM_CORE_ONLY

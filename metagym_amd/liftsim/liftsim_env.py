@@ -1,5 +1,6 @@
 """LiftSim (reference metagym/liftsim/environment/env.py) for N buildings at once, stepped by `mg_liftsim_step` on the GPU;
-the reference's rule-based dispatcher (`rule_policy`) and whole rollouts in one launch (`rollout`) run there too."""
+the reference's rule-based dispatcher (`rule_policy`) and whole rollouts in one launch (`rollout`, and `rollout_policy` with
+learned dispatchers in the loop) run there too."""
 import collections
 import configparser
 import ctypes as C
@@ -365,6 +366,75 @@ class LiftSim(object):
             _lib.ptr(out.get("reward")), _lib.ptr(out.get("time_consume")), _lib.ptr(out.get("energy_consume")),
             _lib.ptr(out.get("given_up_persons")), _lib.ptr(out.get("actions")), self._stream()), "mg_liftsim_rollout")
         return out
+
+    def rollout_policy(self, policy, steps, policy_ids=None, record=()):
+        """`steps` closed-loop env steps of every building in ONE launch: building e is dispatched by policy
+        `policy_ids[e]` of `policy` (a `LiftPolicy`; `policy_ids=None` = policy 0 for all), evaluated inside the kernel
+        once per elevator on the state before each step (liftsim/policy.py defines the arithmetic exactly). The step is
+        `step()`'s: replaying the recorded actions through `rollout(actions)` or `step()` from the same arena gives the
+        same records and the same end arena, bit for bit. Returns the dict of `rollout()`: "return" [N] and the records
+        named in `record` (of RECORDS; "actions" [T, N, 2E] holds the policy's actions, (0, 0) for an env that was
+        frozen when the step began). The ids are validated once: nothing synchronises when `policy_ids` is None, a host
+        array, or the (unchanged) tensor of the previous call, so after `policy.to(device)` the call can be captured in a hipGraph. A refused call
+        (a policy for another F or E, an id out of range, steps < 1) raises and leaves the arena untouched."""
+        import torch
+        from .policy import LiftPolicy
+        if not isinstance(policy, LiftPolicy):
+            raise TypeError("policy must be a LiftPolicy, got %s" % type(policy).__name__)
+        T, N, E = int(steps), self.num_envs, self.E
+        if T < 1:
+            raise ValueError("steps must be at least 1, got %d" % T)
+        if policy.floors != self.F or policy.elevators != E:
+            raise ValueError("the policy was built for %d floors and %d elevators, the env has %d and %d"
+                             % (policy.floors, policy.elevators, self.F, E))
+        record = (record,) if isinstance(record, str) else tuple(record or ())
+        unknown = set(record) - set(self.RECORDS)
+        if unknown:
+            raise ValueError("unknown records: %s (known: %s)" % (sorted(unknown), list(self.RECORDS)))
+        ids = self._policy_ids(policy_ids, policy.num_policies)
+        params = policy.to(self.device)
+        desc = _lib.LiftsimPolicyDesc(params.data_ptr(), policy.num_policies, policy.hidden, policy.floors, policy.elevators,
+                                      (C.c_float * 8)(*[float(v) for v in policy.scale]))
+        out = {"return": torch.empty(N, dtype=torch.float64, device=self.device)}
+        for name in record:
+            if name == "actions":
+                out[name] = torch.empty(T, N, 2 * E, dtype=torch.int32, device=self.device)
+            else:
+                out[name] = torch.empty(T, N, dtype=torch.int32 if name == "given_up_persons" else torch.float64,
+                                        device=self.device)
+        _lib.check(self._lib.mg_liftsim_policy_rollout(
+            self._cfg, N, _lib.ptr(self.arena), T, desc, _lib.ptr(ids), _lib.ptr(out["return"]),
+            _lib.ptr(out.get("reward")), _lib.ptr(out.get("time_consume")), _lib.ptr(out.get("energy_consume")),
+            _lib.ptr(out.get("given_up_persons")), _lib.ptr(out.get("actions")), self._stream()),
+            "mg_liftsim_policy_rollout")
+        return out
+
+    def _policy_ids(self, policy_ids, P):
+        """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a
+        hipGraph capture after its warm-up) neither uploads nor reads back."""
+        import torch
+        N = self.num_envs
+        keep = getattr(self, "_policy_ids_keep", None)     # (P, device ids, source tensor, its version, the ids' bytes)
+        if isinstance(policy_ids, torch.Tensor) and keep is not None and keep[0] == P and policy_ids is keep[2] and \
+                policy_ids._version == keep[3]:
+            return keep[1]
+        if policy_ids is None:
+            ids_h = np.zeros(N, dtype=np.int64)
+        else:
+            ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
+            if ids_h.shape != (N,):
+                raise ValueError("policy_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
+            if ids_h.dtype.kind not in "iu":
+                raise ValueError("policy_ids must be integers, got %s" % ids_h.dtype)
+            if int(ids_h.min()) < 0 or int(ids_h.max()) >= P:
+                raise ValueError("policy_ids must be in [0, %d)" % P)
+        ids_h = ids_h.astype(np.int32)
+        if keep is not None and keep[0] == P and keep[4] == ids_h.tobytes():
+            return keep[1]
+        ids_d = torch.as_tensor(ids_h, device=self.device).contiguous()
+        src = policy_ids if isinstance(policy_ids, torch.Tensor) else None
+        self._policy_ids_keep = (P, ids_d, src, src._version if src is not None else None, ids_h.tobytes())
+        return ids_d
 
     def statistics_tensors(self):
         """env.statistics of every env as [N] tensors (one launch, no host synchronisation)."""

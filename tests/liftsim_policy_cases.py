@@ -1,0 +1,222 @@
+"""Fixtures shared by tests/test_liftsim_policy.py (CPU) and tests/test_liftsim_policy_gpu.py: the policy sets, a scalar
+restatement of the dispatcher network written straight from the definition in include/metagym_hip.h, and the closed loop
+on the oracle (tests/liftsim_oracle.Env stepped with LiftPolicy.reference). Runs are cached, so the tests of one session
+share them. Nothing here touches the kernel under test."""
+import collections
+import functools
+import os
+
+import numpy as np
+
+import liftsim_cases as LC
+import liftsim_oracle as O
+
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+CONF = {  # the reference's tests/conf/config<i>.ini (the ones test_liftsim_rule_gpu.py runs)
+    1: dict(dt=0.5, floors=2, elevators=1, particle_number=12, generation_interval=150.0),
+    3: dict(dt=1.0, floors=10, elevators=4, particle_number=12, generation_interval=15.0),
+}
+N_POLICIES = 6
+
+
+def edge_choices(F):
+    """The choice whose bo gets +3 in policy q: the last up and down floors, "nothing", "no new dispatch", the first up and
+    down floors."""
+    return [F - 1, 2 * F - 1, 2 * F, 2 * F + 1, 0, F]
+
+
+def random_weights(rs, P, H, F, E, sigma=0.5):
+    A = 2 * F + 2
+    shapes = [(P, H, 8), (P, H, E), (P, H, F + 1), (P, H, F), (P, H, F), (P, H, F), (P, H), (P, A, H), (P, A)]
+    return [(rs.randn(*s) * sigma).astype(np.float32) for s in shapes]     # ws we wt wr wu wd b wo bo
+
+
+@functools.lru_cache(maxsize=None)
+def policies(F, E, H, seed=5):
+    """Six policies with N(0, 0.5^2) float32 weights; policy q prefers one edge choice (+3 on its bo)."""
+    from metagym_amd.liftsim import LiftPolicy
+    w = random_weights(np.random.RandomState(seed), N_POLICIES, H, F, E)
+    for q, c in enumerate(edge_choices(F)):
+        w[8][q, c] += np.float32(3.0)
+    return LiftPolicy(*w)
+
+
+def obs_of(states, F, E):
+    """The arrays of LiftSim.observation() (numpy, [n, ...]) of a list of MansionState namedtuples."""
+    n = len(states)
+    obs = {k: np.zeros((n, E), np.float64) for k in ("Floor", "Velocity", "DoorState", "LoadWeight", "OverloadedAlarm")}
+    for k in ("Direction", "CurrentDispatchTarget", "DispatchTargetDirection", "ReservedTargetCount"):
+        obs[k] = np.zeros((n, E), np.int32)
+    obs["DoorIsOpening"], obs["DoorIsClosing"] = np.zeros((n, E), np.bool_), np.zeros((n, E), np.bool_)
+    obs["ReservedTargetFloors"] = np.zeros((n, E, F), np.int32)
+    obs["RequiringUpwardFloors"], obs["RequiringDownwardFloors"] = np.zeros((n, F), np.bool_), np.zeros((n, F), np.bool_)
+    for i, st in enumerate(states):
+        assert len(st.ElevatorStates) == E
+        for el, es in enumerate(st.ElevatorStates):
+            for k in ("Floor", "Velocity", "DoorState", "LoadWeight", "OverloadedAlarm", "Direction", "CurrentDispatchTarget",
+                      "DispatchTargetDirection", "DoorIsOpening", "DoorIsClosing"):
+                obs[k][i, el] = getattr(es, k)
+            t = list(es.ReservedTargetFloors)
+            obs["ReservedTargetCount"][i, el] = len(t)
+            obs["ReservedTargetFloors"][i, el, :len(t)] = t
+        for f in st.RequiringUpwardFloors:
+            obs["RequiringUpwardFloors"][i, f - 1] = True
+        for f in st.RequiringDownwardFloors:
+            obs["RequiringDownwardFloors"][i, f - 1] = True
+    return obs
+
+
+def scalar_policy(pol, q, state, el, want_z=False):
+    """Policy q of `pol` for elevator `el` of one MansionState, straight from the definition: Python loops, one np.float32
+    operation at a time. Returns the choice (and the list of pre-activations z with `want_z`)."""
+    f32 = np.float32
+    F, H, A = pol.floors, pol.hidden, pol.choices
+    es = state.ElevatorStates[el]
+    raw = [es.Floor, es.Velocity, es.Direction, es.DoorState, es.LoadWeight, es.OverloadedAlarm,
+           1 if es.DoorIsOpening else 0, 1 if es.DoorIsClosing else 0]
+    with np.errstate(all="ignore"):
+        x = [f32(np.float64(raw[i])) * pol.scale[i] for i in range(8)]
+        h, zs = [], []
+        for j in range(H):
+            z = pol.b[q, j]
+            for i in range(8):
+                z = f32(z + f32(pol.ws[q, j, i] * x[i]))
+            z = f32(z + pol.we[q, j, el])
+            d = int(es.CurrentDispatchTarget)
+            if 0 <= d <= F:
+                z = f32(z + pol.wt[q, j, d])
+            for f in range(1, F + 1):
+                if f in es.ReservedTargetFloors:
+                    z = f32(z + pol.wr[q, j, f - 1])
+            for f in range(1, F + 1):
+                if f in state.RequiringUpwardFloors:
+                    z = f32(z + pol.wu[q, j, f - 1])
+            for f in range(1, F + 1):
+                if f in state.RequiringDownwardFloors:
+                    z = f32(z + pol.wd[q, j, f - 1])
+            assert isinstance(z, np.float32)
+            zs.append(z)
+            h.append(z if z > 0 else f32(0.0))
+        logits = []
+        for c in range(A):
+            v = pol.bo[q, c]
+            for j in range(H):
+                v = f32(v + f32(pol.wo[q, c, j] * h[j]))
+            logits.append(v)
+        choice = 0
+        for c in range(1, A):
+            if logits[c] > logits[choice]:
+                choice = c
+    return (choice, zs) if want_z else choice
+
+
+def scalar_actions(pol, ids, states):
+    """[n][2E] actions of the scalar restatement, with the choice-to-action table spelt out."""
+    F, out = pol.floors, []
+    for q, st in zip(ids, states):
+        row = []
+        for el in range(pol.elevators):
+            c = scalar_policy(pol, int(q), st, el)
+            row += [c + 1, 1] if c < F else [c - F + 1, -1] if c < 2 * F else [0, 1] if c == 2 * F else [-1, 1]
+        out.append(row)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the closed loop on the oracle
+def rush_flow():
+    """tests/golden/liftsim_flow.npy turned so that the morning rush comes first (test_liftsim_rule_gpu.rush_flow)."""
+    flow = np.load(os.path.join(GOLD, "liftsim_flow.npy"))
+    t = flow[:, 1]
+    i0 = int(np.nonzero(t <= 28500.0)[0][-1])
+    out = np.concatenate([flow[i0:], flow[:i0]]).copy()
+    out[:, 1] = np.concatenate([t[i0:] - t[i0], t[:i0] + 86400.0 - t[i0]])
+    assert out[0, 1] == 0.0 and (np.diff(out[:, 1]) > 0).all() and out[-1, 1] < 86400
+    return out
+
+
+# name -> what LiftSim takes, the oracle's config, N, seed, the sampled envs, steps, H. Sampled env sample[i] plays policy i % 6.
+def _case(kw, N, seed, sample, steps, H, flow=None):
+    return dict(kw=kw, N=N, seed=seed, sample=tuple(sample), steps=steps, H=H, flow=flow)
+
+
+CASES = {
+    "uniform3": lambda: _case(dict(generator="UNIFORM", **CONF[3]), 130, 40, (0, 1, 63, 64, 127, 128, 129), 150, 8),
+    "big": lambda: _case(dict(generator="UNIFORM", floors=128, elevators=32, **LC.BIG_KW), LC.BIG_N, LC.BIG_SEED, LC.BIG_SAMPLE,
+                         320, 4),
+    "f2_n1": lambda: _case(dict(generator="UNIFORM", **CONF[1]), 1, 11, (0,), 200, 1),
+    "f2_n65": lambda: _case(dict(generator="UNIFORM", **CONF[1]), 65, 11, (0, 1, 31, 62, 63, 64), 200, 1),
+    "custom_rush": lambda: _case(dict(generator="CUSTOM"), 70, 21, (0, 1, 33, 63, 64, 69), 200, 64, flow=rush_flow()),
+}
+
+
+def oracle_config(case):
+    kw = dict(case["kw"])
+    if case["flow"] is not None:
+        kw["flow"] = case["flow"]
+    return O.Config(**kw)
+
+
+def case_ids(case, P=N_POLICIES):
+    """int32 [N] policy ids: sampled env sample[i] plays policy i % P (so ids 0..5 are given explicitly), the others
+    (7 e + 3) % P, which mixes the ids inside every wave."""
+    ids = (7 * np.arange(case["N"]) + 3) % P
+    for i, e in enumerate(case["sample"]):
+        ids[e] = i % P
+    return ids.astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def closed_loop(name):
+    """The sampled envs of a case in the oracle, dispatched by LiftPolicy.reference: per step the actions, the choices and
+    the outputs; at the end the states and both streams; and what the run covered."""
+    case = CASES[name]()
+    cfg = oracle_config(case)
+    F, E, T, S = cfg.F, cfg.E, case["steps"], len(case["sample"])
+    pol = policies(F, E, case["H"])
+    ids = case_ids(case)[list(case["sample"])]
+    envs = [O.Env(cfg, case["seed"] + e) for e in case["sample"]]
+    out = dict(case=case, policy=pol, ids=ids, actions=np.zeros((T, S, 2 * E), np.int32), rows=np.zeros((T, S, 4)),
+               choices=collections.Counter(), ev=collections.Counter(), states_mid={})
+    for k in range(T):
+        states = [env.mansion_state() for env in envs]
+        a, c = pol.reference(ids, obs_of(states, F, E), return_choices=True)
+        out["choices"].update(c.ravel().tolist())
+        for st in states:
+            out["ev"]["top_reserved"] += any(F in e.ReservedTargetFloors for e in st.ElevatorStates)
+            out["ev"]["down_call_at_top"] += F in st.RequiringDownwardFloors
+            out["ev"]["up_call_below_top"] += (F - 1) in st.RequiringUpwardFloors
+        out["actions"][k] = a
+        for j, env in enumerate(envs):
+            out["rows"][k, j] = LC.row(*env.step([int(v) for v in a[j]]))
+    out["states"] = [env.mansion_state() for env in envs]
+    out["streams"] = [LC.streams(env) for env in envs]
+    out["max_queue"] = max(env.max_queue for env in envs)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- a queue that overflows
+# The inputs of test_liftsim_rule_gpu.test_rollout_overflow_freezes_only_its_env (queue_capacity 33, seed 5, 64 envs of
+# CONF[3]) under the policies: env e plays policy e % 6. The oracle's queues are unbounded: an env overflows on the device
+# in the step in which the oracle's longest queue first reaches queue_capacity + 1.
+FROZEN = dict(kw=dict(generator="UNIFORM", **CONF[3]), N=64, seed=5, Q=33, steps=480, H=8, sample=(0, 14, 15, 16, 59, 60, 63))
+
+
+@functools.lru_cache(maxsize=None)
+def frozen_run():
+    """The sampled envs of FROZEN in the oracle: per step the actions and outputs, and the step of the first overflow
+    (-1: none within the run)."""
+    c = FROZEN
+    cfg = O.Config(**c["kw"])
+    F, E, T, S = cfg.F, cfg.E, c["steps"], len(c["sample"])
+    pol = policies(F, E, c["H"])
+    ids = np.array(c["sample"]) % N_POLICIES
+    envs = [O.Env(cfg, c["seed"] + e) for e in c["sample"]]
+    out = dict(policy=pol, actions=np.zeros((T, S, 2 * E), np.int32), rows=np.zeros((T, S, 4)), first=[-1] * S)
+    for k in range(T):
+        a = pol.reference(ids, obs_of([env.mansion_state() for env in envs], F, E))
+        out["actions"][k] = a
+        for j, env in enumerate(envs):
+            out["rows"][k, j] = LC.row(*env.step([int(v) for v in a[j]]))
+            if out["first"][j] < 0 and env.max_queue > c["Q"]:
+                out["first"][j] = k
+    return out

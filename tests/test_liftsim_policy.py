@@ -1,0 +1,296 @@
+"""LiftSim learned dispatchers on the CPU: the packed layout, LiftPolicy.reference against a scalar restatement written
+straight from the definition, the choice-to-action table, the closed loop on the oracle with its coverage, and the
+host-side refusals of mg_liftsim_policy_rollout. All comparisons are exact."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import liftsim_oracle as O
+import liftsim_policy_cases as PC
+
+
+def _lib():
+    from metagym_amd import _lib
+    return _lib, _lib.load()
+
+
+def _policy(F, E, H, P=2, seed=1):
+    from metagym_amd.liftsim import LiftPolicy
+    return LiftPolicy(*PC.random_weights(np.random.RandomState(seed), P, H, F, E))
+
+
+# ---------------------------------------------------------------------------------------------- 1. the packed layout
+@pytest.mark.parametrize("F,E,H", [(2, 1, 1), (10, 4, 8), (33, 5, 7), (128, 32, 64), (127, 31, 3)])
+def test_pack_round_trip_count_padding_and_offsets(F, E, H):
+    from metagym_amd.liftsim import LiftPolicy
+    from metagym_amd.liftsim import policy as LP
+    _, lib = _lib()
+    pol = _policy(F, E, H, P=3)
+    count = lib.mg_liftsim_policy_param_count(H, F, E)
+    assert count == pol.param_count == LP.param_count(H, F, E) and count % 4 == 0
+    packed = pol.pack()
+    assert packed.shape == (3, count) and packed.dtype == np.float32
+    back = LiftPolicy.unpack(packed, H, F, E)
+    for name in ("ws", "we", "wt", "wr", "wu", "wd", "b", "wo", "bo", "scale"):
+        assert getattr(back, name).tobytes() == getattr(pol, name).tobytes(), name
+    # every record and every group starts on a multiple of four floats, and everything that is not a parameter is zero
+    groups, ru = LP.unit_groups(F, E)
+    rc = 4 + ((H + 3) & ~3)
+    assert ru % 4 == 0 and rc % 4 == 0 and count == H * ru + (2 * F + 2) * rc
+    used = np.zeros(count, bool)
+    for j in range(H):
+        for name, o, n in groups:
+            assert o % 4 == 0
+            used[j * ru + o:j * ru + o + n] = True
+    for c in range(2 * F + 2):
+        base = H * ru + c * rc
+        used[base] = True
+        used[base + 4:base + 4 + H] = True
+    assert used.sum() == H * (9 + E + F + 1 + 3 * F) + (2 * F + 2) * (1 + H)
+    assert not packed[:, ~used].any()
+    ones = LiftPolicy(*[np.ones_like(getattr(pol, n)) for n in ("ws", "we", "wt", "wr", "wu", "wd", "b", "wo", "bo")]).pack()
+    assert (ones[:, used] == 1).all() and not ones[:, ~used].any()
+
+
+def test_param_count_refuses_sizes_outside_the_range():
+    _, lib = _lib()
+    for args in ((0, 10, 4), (65, 10, 4), (8, 1, 4), (8, 129, 4), (8, 10, 0), (8, 10, 33)):
+        assert lib.mg_liftsim_policy_param_count(*args) == -1002, args
+    assert lib.mg_liftsim_policy_param_count(64, 128, 32) == 53384
+
+
+def test_default_scale_is_float32_arithmetic():
+    pol = _policy(10, 4, 2)
+    one = np.float32(1)
+    want = np.array([one / np.float32(10), 0.5, 1, 1, one / np.float32(1600), 1, 1, 1], np.float32)
+    assert pol.scale.dtype == np.float32 and pol.scale.tobytes() == want.tobytes()
+
+
+# ---------------------------------------------------------------------------------------------- 2. reference against the scalar form
+def _oracle_states(cfg, seed, steps, every, rs):
+    """States of an oracle run under random held actions, one every `every` steps."""
+    env, out = O.Env(cfg, seed), []
+    a = [0, 1] * cfg.E
+    for k in range(steps):
+        if k % 6 == 0:
+            a = []
+            for _ in range(cfg.E):
+                a += [int(rs.randint(-1, cfg.F + 1)), int(rs.randint(-1, 2))]
+        env.step(a)
+        if k % every == every - 1:
+            out.append(env.mansion_state())
+    return out
+
+
+@pytest.mark.parametrize("F,E,H,steps,kw", [
+    (2, 1, 1, 1500, dict(dt=0.5, particle_number=12, generation_interval=150.0)),
+    (10, 4, 8, 240, dict(dt=1.0, particle_number=12, generation_interval=15.0)),
+    (33, 5, 3, 240, dict(dt=1.0, particle_number=40, generation_interval=4.0)),
+])
+def test_reference_matches_the_scalar_restatement_on_oracle_states(F, E, H, steps, kw):
+    pol = PC.policies(F, E, H)
+    rs = np.random.RandomState(F)
+    states = _oracle_states(O.Config(floors=F, elevators=E, generator="UNIFORM", **kw), 3, steps, steps // 40, rs)
+    assert any(st.RequiringUpwardFloors for st in states) and any(st.RequiringDownwardFloors for st in states)
+    assert any(es.ReservedTargetFloors for st in states for es in st.ElevatorStates) or F == 2
+    ids = np.arange(len(states)) % PC.N_POLICIES
+    got, choices = pol.reference(ids, PC.obs_of(states, F, E), return_choices=True)
+    assert got.dtype == np.int32 and got.shape == (len(states), 2 * E) and choices.shape == (len(states), E)
+    assert got.tolist() == PC.scalar_actions(pol, ids, states)
+    z = pol.preactivations(ids.astype(np.int64), *pol.inputs(PC.obs_of(states, F, E)))
+    for i, st in enumerate(states):
+        for el in range(E):
+            c, zs = PC.scalar_policy(pol, int(ids[i]), st, el, want_z=True)
+            assert c == choices[i, el]
+            assert np.array(zs, np.float32).tobytes() == z[i, el].tobytes()
+
+
+def _elevator(F, **kw):
+    base = dict(Floor=1.0, MaximumFloor=F, Velocity=0.0, MaximumSpeed=2.0, Direction=0, DoorState=0.0, CurrentDispatchTarget=0,
+                DispatchTargetDirection=1, LoadWeight=0.0, MaximumLoad=1600, ReservedTargetFloors=[], OverloadedAlarm=0.0,
+                DoorIsOpening=False, DoorIsClosing=False)
+    base.update(kw)
+    return O.ElevatorState(**base)
+
+
+def test_reference_with_every_call_and_every_reserved_bit_set_at_128_floors():
+    F, E, H = 128, 32, 4
+    pol = PC.policies(F, E, H)
+    every = list(range(1, F + 1))
+    els = [_elevator(F, Floor=1.0 + 3.97 * el, Velocity=(-1) ** el * 0.37, Direction=(el % 3) - 1, DoorState=0.25 * (el % 5),
+                     CurrentDispatchTarget=(el * 9) % (F + 1), LoadWeight=73.3 * el, OverloadedAlarm=0.5 * (el % 2),
+                     ReservedTargetFloors=every if el % 2 == 0 else every[::-1][:el], DoorIsOpening=el % 4 == 1,
+                     DoorIsClosing=el % 4 == 2) for el in range(E)]
+    states = [O.MansionState(els, every, every), O.MansionState(els, [F], [1, F]), O.MansionState(els, [], [])]
+    for q in range(PC.N_POLICIES):
+        ids = np.full(len(states), q)
+        assert pol.reference(ids, PC.obs_of(states, F, E)).tolist() == PC.scalar_actions(pol, ids, states)
+
+
+def test_exact_ties_and_nan_logits_resolve_to_the_lowest_index():
+    from metagym_amd.liftsim import LiftPolicy
+    F, E, H = 3, 2, 2
+    w = PC.random_weights(np.random.RandomState(2), 3, H, F, E)
+    w[7][0][:] = 0.0                     # policy 0: wo = 0 and one bo for all, every logit equal
+    w[8][0][:] = 0.25
+    w[7][1][:] = 0.0                     # policy 1: choices 3 and 6 tie above the rest
+    w[8][1][:] = -1.0
+    w[8][1][[3, 6]] = 2.0
+    w[6][2][:] = 3.0e38                  # policy 2: h overflows the products to +inf and -inf, logit 0 is NaN
+    w[0][2][:] = 0.0
+    w[7][2][0] = [3.0e38, -3.0e38]
+    pol = LiftPolicy(*w)
+    st = O.MansionState([_elevator(F), _elevator(F, Floor=2.0, CurrentDispatchTarget=2)], [1], [3])
+    ids = np.array([0, 1, 2])
+    got, choices = pol.reference(ids, PC.obs_of([st] * 3, F, E), return_choices=True)
+    assert choices.tolist() == [[0, 0], [3, 3], [0, 0]]
+    assert got.tolist() == PC.scalar_actions(pol, ids, [st] * 3)
+
+
+def test_a_negative_zero_preactivation_stays_negative_zero():
+    """b = -0 and nothing that adds: the lookups that do not apply add nothing, not 0 * w (which would give +0), and a
+    lookup outside [0, F] is no lookup."""
+    from metagym_amd.liftsim import LiftPolicy
+    F, E, H = 4, 2, 3
+    w = PC.random_weights(np.random.RandomState(3), 1, H, F, E)
+    w[6][:] = np.float32(-0.0)           # b
+    w[0][:] = np.float32(-0.0)           # ws: -0 * x = -0 for x >= 0, and -0 + -0 = -0
+    w[1][:] = np.float32(-0.0)           # we
+    pol = LiftPolicy(*w)
+    # nothing reserved, no calls, and a dispatch target outside [0, F]: wt, wr, wu, wd (all non-zero) must not be touched
+    for d in (-1, F + 1):
+        st = O.MansionState([_elevator(F, CurrentDispatchTarget=d), _elevator(F, CurrentDispatchTarget=d)], [], [])
+        obs = PC.obs_of([st], F, E)
+        z = pol.preactivations(np.array([0]), *pol.inputs(obs))
+        assert (z == 0).all() and np.signbit(z).all()
+        for el in range(E):
+            c, zs = PC.scalar_policy(pol, 0, st, el, want_z=True)
+            assert all(v == 0 and np.signbit(v) for v in zs)
+        assert pol.reference(np.array([0]), obs).tolist() == PC.scalar_actions(pol, [0], [st])
+    # with d inside the range the lookup is made: the pre-activation is wt[j][d] exactly
+    st = O.MansionState([_elevator(F, CurrentDispatchTarget=F), _elevator(F, CurrentDispatchTarget=0)], [], [])
+    z = pol.preactivations(np.array([0]), *pol.inputs(PC.obs_of([st], F, E)))
+    assert z[0, 0].tobytes() == pol.wt[0, :, F].tobytes() and z[0, 1].tobytes() == pol.wt[0, :, 0].tobytes()
+
+
+# ---------------------------------------------------------------------------------------------- 3. choices to actions
+@pytest.mark.parametrize("F", [2, 128])
+def test_actions_of_over_all_choices(F):
+    from metagym_amd.liftsim import LiftPolicy
+    got = LiftPolicy.actions_of(np.arange(2 * F + 2), F)
+    want = [[c + 1, 1] for c in range(F)] + [[c + 1, -1] for c in range(F)] + [[0, 1], [-1, 1]]
+    assert got.dtype == np.int32 and got.tolist() == want
+    assert ((got[:, 0] >= -1) & (got[:, 0] <= F) & (np.abs(got[:, 1]) == 1)).all()       # all pass step()'s range check
+    for bad in ([-1], [2 * F + 2]):
+        with pytest.raises(ValueError):
+            LiftPolicy.actions_of(np.array(bad), F)
+
+
+# ---------------------------------------------------------------------------------------------- 4. the closed loop and its coverage
+def test_closed_loop_on_the_big_building_covers_the_edges():
+    run = PC.closed_loop("big")
+    F, T, S = 128, run["case"]["steps"], len(run["case"]["sample"])
+    assert sorted(run["ids"].tolist()) == list(range(6))
+    for c in PC.edge_choices(F):
+        assert run["choices"][c] > 0, c
+    ev = run["ev"]
+    assert ev["top_reserved"] > 0 and ev["down_call_at_top"] > 0 and ev["up_call_below_top"] > 0, dict(ev)
+    assert run["max_queue"] < 128                       # under the default queue_capacity: no overflow on the device
+    assert run["actions"].shape == (T, S, 64) and (run["rows"][:, :, 0] < 0).all()
+    tf, dr = run["actions"][:, :, 0::2], run["actions"][:, :, 1::2]
+    assert tf.min() == -1 and tf.max() == F and set(np.unique(dr).tolist()) == {-1, 1}
+
+
+@pytest.mark.parametrize("name", ["uniform3", "f2_n1", "f2_n65", "custom_rush"])
+def test_closed_loop_cases_take_every_edge_choice_and_stay_under_the_queue_capacity(name):
+    run = PC.closed_loop(name)
+    F = run["policy"].floors
+    played = set(run["ids"].tolist())
+    for q, c in enumerate(PC.edge_choices(F)):
+        if q in played:
+            assert run["choices"][c] > 0, (q, c)
+    if name == "f2_n65":
+        assert sorted(c for c in run["choices"] if run["choices"][c] > 0) == list(range(6))      # 6 of 6 choices
+    assert 0 < run["max_queue"] < 128
+    assert (run["rows"][:, :, 0] < 0).all()
+
+
+# ---------------------------------------------------------------------------------------------- 5. refusals that need no device
+def test_policy_rollout_refuses_on_the_host():
+    L, lib = _lib()
+    cfg = L.LiftsimConfig()
+    cfg.floors, cfg.elevators, cfg.generator, cfg.queue_capacity, cfg.window = 10, 4, 1, 128, 1200
+    cfg.particle_number, cfg.floor_height, cfg.dt, cfg.generation_interval = 12, 4.0, 0.5, 150.0
+    fake = C.create_string_buffer(256)
+    base = (C.addressof(fake) + 15) & ~15
+    p = C.c_void_p(base)
+
+    def desc(**kw):
+        d = L.LiftsimPolicyDesc(base, 2, 8, 10, 4, (C.c_float * 8)(*([1.0] * 8)))
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def call(cfg=cfg, n=4, arena=p, steps=5, pol=None, ids=p, ret=p):
+        return lib.mg_liftsim_policy_rollout(cfg, n, arena, steps, desc() if pol is None else pol, ids, ret, None, None, None, None,
+                                             None, None)
+
+    NULL, SIZE, CONFIG = -1001, -1002, -1003
+    assert call(cfg=None) == NULL and call(arena=None) == NULL and call(ids=None) == NULL and call(ret=None) == NULL
+    assert lib.mg_liftsim_policy_rollout(cfg, 4, p, 5, None, p, p, None, None, None, None, None, None) == NULL
+    assert call(pol=desc(params=None)) == NULL and b"params" in lib.mg_last_error()
+    assert call(steps=0) == SIZE and b"n_steps" in lib.mg_last_error()
+    assert call(n=0) == SIZE
+    assert call(pol=desc(n_policies=0)) == SIZE
+    assert call(pol=desc(hidden=0)) == SIZE and call(pol=desc(hidden=65)) == SIZE and b"hidden" in lib.mg_last_error()
+    assert call(pol=desc(floors=11)) == CONFIG and b"floors" in lib.mg_last_error()
+    assert call(pol=desc(elevators=3)) == CONFIG
+    assert call(pol=desc(params=base + 4)) == CONFIG and b"16-byte" in lib.mg_last_error()
+    bad = L.LiftsimConfig.from_buffer_copy(cfg)
+    bad.queue_capacity = 0                             # what mg_liftsim_step refuses in cfg
+    assert call(cfg=bad) == CONFIG and b"queue_capacity" in lib.mg_last_error()
+    bad = L.LiftsimConfig.from_buffer_copy(cfg)
+    bad.generator, bad.table_len = 0, 3                # CUSTOM without its tables
+    assert call(cfg=bad) == CONFIG
+
+
+def test_lift_policy_refuses_bad_parameters():
+    from metagym_amd.liftsim import LiftPolicy
+    F, E, H = 5, 2, 3
+    names = ("ws", "we", "wt", "wr", "wu", "wd", "b", "wo", "bo")
+    good = dict(zip(names, PC.random_weights(np.random.RandomState(0), 2, H, F, E)))
+    LiftPolicy(**good)
+    for name in names:
+        w = dict(good)
+        w[name] = good[name].copy()
+        w[name].flat[1] = np.nan
+        with pytest.raises(ValueError):
+            LiftPolicy(**w)
+        w[name] = good[name].astype(np.float64)
+        with pytest.raises(TypeError):
+            LiftPolicy(**w)
+        w[name] = np.delete(good[name], 0, axis=-1 if name in ("b", "wo", "bo") else 1)   # one hidden unit (bo: one choice) short
+        with pytest.raises(ValueError):
+            LiftPolicy(**w)
+    with pytest.raises(ValueError):
+        LiftPolicy(scale=np.ones(7, np.float32), **good)
+    with pytest.raises(ValueError):
+        LiftPolicy(scale=np.array([1, 1, 1, np.inf, 1, 1, 1, 1], np.float32), **good)
+    with pytest.raises(ValueError):                                      # H = 65
+        LiftPolicy(*PC.random_weights(np.random.RandomState(0), 1, 65, F, E))
+    pol = LiftPolicy(**good)
+    st = O.MansionState([_elevator(F), _elevator(F)], [], [])
+    with pytest.raises(ValueError):
+        pol.reference(np.array([2]), PC.obs_of([st], F, E))              # an id out of range
+    with pytest.raises(ValueError):
+        pol.reference(np.array([0, 1]), PC.obs_of([st], F, E))           # two ids, one building
+    with pytest.raises(ValueError):
+        pol.reference(np.array([0]), PC.obs_of([O.MansionState([_elevator(F)], [], [])], F, 1))   # another E
+
+
+def test_the_frozen_case_overflows_its_queues_under_the_policies_own_actions():
+    run = PC.frozen_run()
+    first = dict(zip(PC.FROZEN["sample"], run["first"]))
+    assert 0 < first[15] < PC.FROZEN["steps"] - 1 and 0 < first[60] < PC.FROZEN["steps"] - 1, first
+    assert first[0] == first[14] == first[16] == first[59] == first[63] == -1, first
