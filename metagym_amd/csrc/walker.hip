@@ -126,6 +126,13 @@ __device__ __forceinline__ void tangent_basis(V3 n, V3 &t1, V3 &t2) {
     t2 = cross(n, t1);
 }
 
+// The velocity clamp of the "bullet" world. btClamp (and np.clip) compare, so a NaN passes through and the done rule sees it;
+// fmin(fmax(v, -m), m) alone returns the other operand for a NaN and hands a NaN velocity on as -m.
+__device__ __forceinline__ double clamp_keep_nan(double v, double m) {
+    const double c = fmin(fmax(v, -m), m);
+    return v != v ? v : c;
+}
+
 struct Env {   // per-lane simulation state
     V3 pos, vel, omega;
     double rot[9];
@@ -425,7 +432,7 @@ __device__ void substep(const mg_walker_topology &tp, const ModelRef &m, const m
         }
     // ---- integrate ------------------------------------------------------------------------------
     if (prm.max_coordinate_velocity > 0.0)        // btMultiBody::applyDeltaVeeMultiDof's clamp (mg_walker_params.max_coordinate_velocity)
-        for (int d = 0; d < n; ++d) u[d] = fmin(fmax(u[d], -prm.max_coordinate_velocity), prm.max_coordinate_velocity);
+        for (int d = 0; d < n; ++d) u[d] = clamp_keep_nan(u[d], prm.max_coordinate_velocity);
     s.vel = v3(u[0], u[1], u[2]);
     s.omega = v3(u[3], u[4], u[5]);
     for (int j = 0; j < nj; ++j) { s.qd[j] = u[6 + j]; s.q[j] += dt * s.qd[j]; }
@@ -1784,7 +1791,7 @@ __device__ __forceinline__ void wave_substep(const mg_walker_topology &tp, const
     }
     // ---- integrate -------------------------------------------------------------------------------------
     if (prm.max_coordinate_velocity > 0.0)        // btMultiBody::applyDeltaVeeMultiDof's clamp (mg_walker_params.max_coordinate_velocity)
-        u_d = fmin(fmax(u_d, -prm.max_coordinate_velocity), prm.max_coordinate_velocity);
+        u_d = clamp_keep_nan(u_d, prm.max_coordinate_velocity);
     if (lane < n) {
         if (lane >= 6) {
             const int j = lane - 6;
@@ -2215,9 +2222,12 @@ env_step:
             lim = fabsf(jp) > 0.99f;
         }
         at_limit = __popcll(__ballot(lim));
-        if (lane < nj) { ob[8 + 2 * lane] = clip5(jp); ob[9 + 2 * lane] = clip5(jv); }
-        if (wave_has_policy(ROLL) && lane < nj) { xl[8 + 2 * lane] = clip5(jp); xl[9 + 2 * lane] = clip5(jv); }     // the next step's x
-        bool finite = isfinite(jp) && isfinite(jv);
+        const float cp = clip5(jp), cv = clip5(jv);
+        if (lane < nj) { ob[8 + 2 * lane] = cp; ob[9 + 2 * lane] = cv; }
+        if (wave_has_policy(ROLL) && lane < nj) { xl[8 + 2 * lane] = cp; xl[9 + 2 * lane] = cv; }     // the next step's x
+        // the finite test reads the CLIPPED state (walker_base_env.py:46-48: np.clip, then np.isfinite): a float32 overflow is
+        // +-5 by then, only a NaN ends the episode. Same order as the head below and as the lane kernel.
+        bool finite = isfinite(cp) && isfinite(cv);
         // feet in contact now: one ballot per foot over the proxies (lane = proxy), not a loop over the proxies per foot
         float cnow = 0.0f;
         if (!after_reset)

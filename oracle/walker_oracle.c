@@ -425,7 +425,10 @@ int wo_substep(const wo_model *m, const wo_params *prm, wo_state *s, const doubl
     wo_flop_count[6] += 1; wo_flop_count[7] += (unsigned long long)nr; wo_flop_count[8] += (unsigned long long)ncont;
 #endif
     if (prm->max_coordinate_velocity > 0.0)      /* btMultiBody::applyDeltaVeeMultiDof's clamp of every generalized velocity */
-        for (int d = 0; d < n; ++d) u[d] = fmin(fmax(u[d], -prm->max_coordinate_velocity), prm->max_coordinate_velocity);
+        for (int d = 0; d < n; ++d) {             /* two comparisons like btClamp: a NaN stays a NaN (fmin / fmax would drop it) */
+            const double mv = prm->max_coordinate_velocity;
+            u[d] = u[d] < -mv ? -mv : (u[d] > mv ? mv : u[d]);
+        }
     for (int i = 0; i < 3; ++i) { s->vel[i] = u[i]; s->omega[i] = u[3 + i]; FL(F_FMA, 1); s->pos[i] += dt * u[i]; }
     for (int j = 0; j < NJ; ++j) { s->qd[j] = u[6 + j]; FL(F_FMA, 1); s->q[j] += dt * u[6 + j]; }
     const v3 om = ld3(s->omega);
@@ -454,7 +457,7 @@ static double calc_state(const wo_model *m, const wo_params *prm, wo_env *e, flo
         if (fabsf(jp) > 0.99f) ++lim;
         obs[8 + 2 * j] = jp < -5.0f ? -5.0f : (jp > 5.0f ? 5.0f : jp);
         obs[9 + 2 * j] = jv < -5.0f ? -5.0f : (jv > 5.0f ? 5.0f : jv);
-        fin = fin && isfinite(jp) && isfinite(jv);
+        fin = fin && isfinite(obs[8 + 2 * j]) && isfinite(obs[9 + 2 * j]);      /* the clipped values (walker_base_env.py:46-48) */
     }
     double sx = 0, sy = 0, cnt = e->floor_known ? 1.0 : 0.0;
     for (int b = 0; b < NB; ++b) {       /* mean over robot.parts: the base once, every other body once per hinge (min. 1) */
@@ -484,7 +487,7 @@ static double calc_state(const wo_model *m, const wo_params *prm, wo_env *e, flo
                            (float)roll, (float)pitch};
     for (int i = 0; i < 8; ++i) {
         obs[i] = head[i] < -5.0f ? -5.0f : (head[i] > 5.0f ? 5.0f : head[i]);
-        fin = fin && isfinite(head[i]);
+        fin = fin && isfinite(obs[i]);
     }
     for (int f = 0; f < nf; ++f) obs[8 + 2 * nj + f] = e->feet_contact[f] < -5.0f ? -5.0f : (e->feet_contact[f] > 5.0f ? 5.0f : e->feet_contact[f]);
     *at_limit = lim;
