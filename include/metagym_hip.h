@@ -687,6 +687,60 @@ int mg_maze2d_policy_rollout(const mg_maze_tasks *tasks, int32_t task_type, int3
                              int32_t *episodes, int32_t *actions, float *reward, double *reward64, uint8_t *done,
                              float *obs, void *stream);
 
+/* MetaMaze shortest-path fields and the expert that descends them (csrc/maze_expert.hip). The reference has no such
+ * function; the numbers are defined here and by metamaze/expert.py (distance_field_reference, expert_action_reference).
+ *
+ * dist[t][k][c] (i32, K orientations x n*n cells per task, c = x * n + y) is the smallest number of env steps that takes
+ * state (k, c) of task t onto a source cell: 0 on a source in every orientation, -1 where no source can be reached. A step
+ * is judged by the cell it ENTERS, as the env's step does, so a wall cell beside a free one has a distance too (the agent
+ * never stands there after a reset). Three kinds, each with the passability rule of the step it belongs to:
+ *   MG_MAZE_FIELD_MOVES_2D (K = 1)  MetaMaze2D: a move into c' is possible iff c' is inside the grid and walls[c'] < 1
+ *                                   (maze_2d.py:27). Off-grid is impassable: the reference's negative-index wrap (a move off
+ *                                   the low edge through a free border cell, maze_2d.py:24-29, which mg_maze2d_step follows)
+ *                                   is NOT followed. Sampled mazes have closed borders, where the two agree.
+ *   MG_MAZE_FIELD_CELLS_3D (K = 1)  the same with walls[c'] == 0 (maze_discrete_3d.py:63-65): the cell-level field of the
+ *                                   continuous maze, which has no expert.
+ *   MG_MAZE_FIELD_TURNS    (K = 4)  MetaMazeDiscrete3D: state (ori_idx, cell); the four DISCRETE_ACTIONS cost one step each:
+ *                                   turn -1, turn +1 (ori_idx mod 4), one cell backward, one cell forward along heading
+ *                                   0 = +x, 1 = +y, 2 = -x, 3 = -y (maze_discrete_3d.py:51-60), into walls == 0 inside the grid.
+ * Additive entry points; MG_ABI_VERSION is unchanged. */
+enum { MG_MAZE_FIELD_MOVES_2D = 0, MG_MAZE_FIELD_CELLS_3D = 1, MG_MAZE_FIELD_TURNS = 2 };
+
+/* One field per task of a table: one workgroup per task, an exact level-synchronous breadth-first search from the sources
+ * (at most K * n * n levels; no workgroup waits for another). sources u8 DEVICE [T][n*n], nonzero = source cell; NULL = each
+ * task's goal cell. An all-zero mask is valid and gives -1 everywhere. A level's frontier is kept in an LDS queue of
+ * mg_maze_distance_queue_capacity() states, so the work per task is proportional to its states; a wider level is found by
+ * a scan of all states instead, never truncated. n is whatever the maze calls accept (3 .. 255); a field too large for LDS
+ * (K * n * n * 4 bytes beside the queues: TURNS above n = 95, the others above n = 191) is built in `dist` itself.
+ * Refused: an unknown kind (MG_ERR_BAD_CONFIG), a NULL dist (MG_ERR_NULL_POINTER), and whatever the maze steps refuse in
+ * an ESCAPE table. Nothing is allocated and nothing synchronises: the call is hipGraph-capturable. */
+int mg_maze_distance_field(const mg_maze_tasks *tasks, int32_t kind, const uint8_t *sources, int32_t *dist, void *stream);
+
+/* States one level's LDS queue holds (host only, a constant of the kernel). */
+int32_t mg_maze_distance_queue_capacity(void);
+
+/* The expert: one launch, one lane per env. action[e] (i32 [N]) is the LOWEST index a in 0..3 whose successor state under
+ * the step's own rule (mg_maze2d_step for MOVES_2D, the discrete mg_maze3d_step for TURNS) has dist == dist(current) - 1,
+ * read in the slice of dist of the env's task; 0 if there is none (on a source, in an unreachable state, off the grid, or
+ * with a field built for another table). A successor off the grid (the 2-D wrap) is never chosen. Reads state->grid,
+ * state->ori_idx (TURNS) and state->task_id, writes `action` only and synchronises nothing. MG_MAZE_FIELD_CELLS_3D is
+ * MG_ERR_BAD_CONFIG: the continuous maze has no expert. */
+int mg_maze_expert_action(const mg_maze_tasks *tasks, int32_t kind, const int32_t *dist, int32_t n_envs,
+                          const mg_maze_state *state, int32_t *action, void *stream);
+
+/* The 2-D closed loop in one launch: mg_maze2d_policy_rollout with the policy, ids, carry, seed and step0 replaced by a
+ * MG_MAZE_FIELD_MOVES_2D field (dist i32 [T][n*n]). The step is mg_maze2d_rollout's; the action of every step is
+ * mg_maze_expert_action's, evaluated on the state before the step (after an auto-reset: the new episode's start), so replaying
+ * the recorded actions through mg_maze2d_rollout gives the same records and end state bit for bit. Outputs, optional records
+ * and the obs_every slices as for mg_maze2d_policy_rollout. Both task types and both auto_reset settings; in SURVIVAL the
+ * expert simply descends the field it is given. Refused: NULL required pointers, n_envs or n_steps < 1, obs_every < 0, and
+ * whatever mg_maze2d_step refuses. */
+int mg_maze2d_expert_rollout(const mg_maze_tasks *tasks, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                             int32_t auto_reset, int32_t n_envs, const mg_maze_state *state, int32_t n_steps,
+                             int32_t obs_every, const int32_t *dist, float *obs_last, double *ret_total, double *ret_episode,
+                             int32_t *episode_len, int32_t *episodes, int32_t *actions, float *reward, double *reward64,
+                             uint8_t *done, float *obs, void *stream);
+
 /* ========================================================================================
  * MetaLocomotion walkers (humanoid / ant) — replaces, for N envs, WalkerBaseEnv.step
  * (metalocomotion/envs/utils/walker_base_env.py:43-82) including the physics the reference

@@ -400,6 +400,12 @@ SIGNATURES = {
                                            C.POINTER(MazeState), C.c_int32, C.c_int32, C.POINTER(MazePolicyDesc), _P,
                                            C.POINTER(MazePolicyCarry), C.c_uint64, C.c_uint64, C.c_int32,
                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mg_maze_distance_field": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, _P, _P, _P]),
+    "mg_maze_distance_queue_capacity": (C.c_int32, []),
+    "mg_maze_expert_action": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, _P, C.c_int32, C.POINTER(MazeState), _P, _P]),
+    "mg_maze2d_expert_rollout": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(MazeState), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P]),
     "mg_walker_reset": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
                                   C.c_int32, C.POINTER(WalkerState), _P, _P, _P, _P]),
     "mg_walker_step": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),

@@ -104,6 +104,8 @@ class _MazeBatch(object):
         self.need_set_task = True
         self.need_reset = True
         self._tasks_c = None
+        self._goal_field = None
+        self._expert_action = None
         N, dev = self.num_envs, self.device
         self._reward = torch.zeros(N, dtype=torch.float32, device=dev)
         self._reward64 = torch.zeros(N, dtype=torch.float64, device=dev)
@@ -174,6 +176,7 @@ class _MazeBatch(object):
             c.cell_slot, c.slot_food, c.slot_interval = (self._cell_slot_t.data_ptr(), self._slot_food_t.data_ptr(),
                                                          self._slot_interval_t.data_ptr())
         self._tasks_c = c
+        self._goal_field = None                                      # the cached goal field was the previous table's
         if self._uniform_cell_size > 0.0:
             # the promise mg_maze_view.uniform_cell_size makes about THIS table, checked by the library against the uploaded
             # cell_size column (synchronous, once per set_task; a hipGraph capture of step() later finds the pair checked)
@@ -329,6 +332,79 @@ class _MazeBatch(object):
                              % (self.num_envs, tuple(a.shape)))
         return a.to(torch.int32).contiguous()
 
+    # ------------------------------------------------------------------ shortest-path fields and the expert
+    _FIELD_KIND = None    # the class's own kind of field (metamaze/expert.py): MOVES_2D, TURNS or CELLS_3D
+    _HAS_EXPERT = True
+
+    def distance_field(self, sources=None, kind=None):
+        """The shortest-path field of every task of the table, built on the GPU in one launch (mg_maze_distance_field, one
+        workgroup per task; metamaze/expert.py defines the numbers): a `MazeDistanceField` whose `dist` int32 [T, K, n, n]
+        holds the smallest number of env steps from each state onto a source cell, 0 on a source, -1 where none can be
+        reached. `kind` defaults to the class's own (2-D: MOVES_2D, discrete 3-D: TURNS with K = 4 headings, continuous 3-D:
+        CELLS_3D); `sources` is a bool / uint8 [T, n, n] mask, or None for each task's goal cell. The default goal field is
+        built once per `set_task` and kept; every other call returns a fresh tensor. Nothing synchronises and a
+        DeviceTaskTable never visits the host."""
+        from . import expert as ex
+        if self.need_set_task:
+            raise Exception("Must call \"set_task\" before distance_field")
+        kind = self._FIELD_KIND if kind is None else ex.check_kind(kind)
+        n, T, dev = self.n, self._tasks_c.n_tasks, self.device
+        default = sources is None and kind == self._FIELD_KIND
+        if default and self._goal_field is not None:
+            return self._goal_field
+        src = None
+        if sources is not None:
+            src = torch.as_tensor(sources)
+            if tuple(src.shape) != (T, n, n):
+                raise ValueError("sources must be a [T = %d, n = %d, n] mask, got %s" % (T, n, tuple(src.shape)))
+            if src.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("sources must be bool or uint8, got %s" % src.dtype)
+            src = src.to(dev).to(torch.uint8).contiguous()
+        dist = torch.empty(T, ex.orientations(kind), n, n, dtype=torch.int32, device=dev)
+        rc = self._lib.mg_maze_distance_field(self._tasks_c, kind, _lib.ptr(src), _lib.ptr(dist), _lib.current_stream(dev))
+        _lib.check(rc, "mg_maze_distance_field")
+        field = ex.MazeDistanceField(dist, kind, n)
+        if default:
+            self._goal_field = field
+        return field
+
+    def _expert_field(self, field, what):
+        """The field an expert call runs on, checked: None = the cached goal field; else one of this env's own kind, n, T and
+        device. Raises before anything is written."""
+        from . import expert as ex
+        if self.need_set_task:
+            raise Exception("Must call \"set_task\" before %s" % what)
+        self._check_step()
+        if field is None:
+            return self.distance_field()
+        if not isinstance(field, ex.MazeDistanceField):
+            raise TypeError("field must be a MazeDistanceField, got %s" % type(field).__name__)
+        if field.kind != self._FIELD_KIND:
+            raise ValueError("%s needs a %s field, got %s" % (what, ex.KIND_NAMES[self._FIELD_KIND], ex.KIND_NAMES[field.kind]))
+        if field.n != self.n or field.num_tasks != self._tasks_c.n_tasks:
+            raise ValueError("the field is for T = %d tasks of n = %d, the env holds T = %d of n = %d"
+                             % (field.num_tasks, field.n, self._tasks_c.n_tasks, self.n))
+        d = field.device
+        if not (d.type == self.device.type and (d.index or 0) == (self.device.index or 0)):
+            raise ValueError("the field lives on %s, the env on %s" % (d, self.device))
+        return field
+
+    def expert_action(self, field=None):
+        """The expert's action for every env, int32 [N], one launch (mg_maze_expert_action): the lowest action whose successor
+        under the step's own rule is one step nearer in `field` (a `MazeDistanceField` of the class's own kind; None = the
+        cached goal field), 0 where there is none (on a source, in an unreachable state). Reads the envs' cells, headings and
+        task ids and writes a persistent buffer, overwritten by the next call; nothing synchronises, so
+        `env.step(env.expert_action())` can be captured in a hipGraph. The continuous maze has no expert."""
+        if not self._HAS_EXPERT:
+            raise NotImplementedError("the continuous maze has no expert (distance_field gives its cell-level field)")
+        field = self._expert_field(field, "expert_action")
+        if self._expert_action is None:
+            self._expert_action = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        rc = self._lib.mg_maze_expert_action(self._tasks_c, field.kind, _lib.ptr(field.dist), self.num_envs, self._state_c,
+                                             _lib.ptr(self._expert_action), _lib.current_stream(self.device))
+        _lib.check(rc, "mg_maze_expert_action")
+        return self._expert_action
+
     def render(self, mode="human"):
         raise NotImplementedError("rendering is out of scope for the batched engine")
 
@@ -339,6 +415,7 @@ class _MazeBatch(object):
 class MetaMaze2D(_MazeBatch):
     """maze_env.py:155-212. obs float32 [N, 2v+1, 2v+1]; action int in {0..3} per env."""
     _BY_SLOT = True       # SURVIVAL arrays per food slot, [max_food, N] (mg_maze_state.food_by_slot)
+    _FIELD_KIND = 0       # expert.MOVES_2D
 
     def __init__(self, num_envs=1, device="cuda", enable_render=False, render_scale=480, max_steps=5000,
                  task_type="SURVIVAL", view_grid=2, auto_reset=False):
@@ -440,6 +517,43 @@ class MetaMaze2D(_MazeBatch):
                                                 _lib.ptr(res.done), _lib.ptr(obs) if int(obs_every) > 0 else None,
                                                 _lib.current_stream(dev))
         _lib.check(rc, "mg_maze2d_policy_rollout")
+        return res
+
+    def rollout_expert(self, steps, field=None, record=False, obs_every=0):
+        """`steps` closed-loop env steps in ONE launch (mg_maze2d_expert_rollout): before every step each env takes
+        `expert_action` on the state it holds (after an auto-reset: the new episode's start) and steps with it. `field` is a
+        MOVES_2D `MazeDistanceField` (None = the cached goal field, the shortest path in ESCAPE; in SURVIVAL the expert
+        simply descends the field it is given). Returns a `MazePolicyRollout` as `rollout_policy` does, with `state=None`:
+        ret_total, ret_episode, episode_len, episodes always; actions, reward, reward64, done [steps, N] when `record=True`,
+        else None (the launch then writes nothing per step); `obs_every` as for `rollout_policy`. Replaying the recorded
+        actions through `rollout` gives the same records and end state bit for bit. Nothing synchronises. A refused call (a
+        field of another n, T, kind or device, steps < 1, a call before set_task or reset) raises and leaves the env and the
+        field as they were."""
+        from .policy import MazePolicyRollout
+        T, N, dev = int(steps), self.num_envs, self.device
+        if self.need_set_task:
+            raise Exception("Must call \"set_task\" before rollout_expert")
+        self._check_step()
+        if T < 1:
+            raise ValueError("steps must be at least 1, got %d" % T)
+        idx = rollout_obs_steps(T, obs_every)
+        field = self._expert_field(field, "rollout_expert")
+        obs = self._obs if int(obs_every) == 0 else torch.empty((len(idx),) + tuple(self._obs.shape), dtype=torch.float32, device=dev)
+        res = MazePolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
+                                torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+                                None, obs, idx)
+        if record:
+            res.actions = torch.empty(T, N, dtype=torch.int32, device=dev)
+            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+            res.reward64 = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+        rc = self._lib.mg_maze2d_expert_rollout(self._tasks_c, self._tt, self.max_steps, self.view_grid, int(self.auto_reset), N,
+                                                self._state_c, T, int(obs_every), _lib.ptr(field.dist), _lib.ptr(self._obs),
+                                                _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len),
+                                                _lib.ptr(res.episodes), _lib.ptr(res.actions), _lib.ptr(res.reward),
+                                                _lib.ptr(res.reward64), _lib.ptr(res.done),
+                                                _lib.ptr(obs) if int(obs_every) > 0 else None, _lib.current_stream(dev))
+        _lib.check(rc, "mg_maze2d_expert_rollout")
         return res
 
     def _policy_ids(self, policy_ids, P):
@@ -554,6 +668,8 @@ class MetaMazeDiscrete3D(_Maze3D):
         super().__init__(num_envs, device, resolution, max_steps, task_type, auto_reset, obs_dtype=obs_dtype)
         self.action_space = Discrete(4)
 
+    _FIELD_KIND = 2       # expert.TURNS
+
     def _observe(self):
         self._launch(None, False)
         return self._obs
@@ -575,6 +691,8 @@ class MetaMazeContinuous3D(_Maze3D):
         self.action_space = Box(low=np.array([-1.0, -1.0]), high=np.array([1.0, 1.0]), dtype=np.float32)
 
     _CONTINUOUS = True
+    _FIELD_KIND = 1       # expert.CELLS_3D
+    _HAS_EXPERT = False
 
     def _rollout_actions(self, actions):
         a = torch.as_tensor(actions, dtype=torch.float32, device=self.device)
