@@ -171,9 +171,13 @@ def closed_loop(name):
     the outputs; at the end the states and both streams; and what the run covered."""
     case = CASES[name]()
     cfg = oracle_config(case)
+    return run_closed_loop(case, policies(cfg.F, cfg.E, case["H"]), case_ids(case)[list(case["sample"])])
+
+
+def run_closed_loop(case, pol, ids):
+    """`closed_loop` for any case and policy set: ids[i] is the policy of the sampled env case["sample"][i]."""
+    cfg = oracle_config(case)
     F, E, T, S = cfg.F, cfg.E, case["steps"], len(case["sample"])
-    pol = policies(F, E, case["H"])
-    ids = case_ids(case)[list(case["sample"])]
     envs = [O.Env(cfg, case["seed"] + e) for e in case["sample"]]
     out = dict(case=case, policy=pol, ids=ids, actions=np.zeros((T, S, 2 * E), np.int32), rows=np.zeros((T, S, 4)),
                choices=collections.Counter(), ev=collections.Counter(), states_mid={})

@@ -64,8 +64,8 @@ def _loops(pol, pid, h, pa, pr, pd):
     return g, np.array(hn, F)
 
 
-@pytest.mark.parametrize("arms", [2, 3, 10, 64])
-@pytest.mark.parametrize("hidden", [1, 3, 4, 5, 64])
+@pytest.mark.parametrize("arms", [2, 3, 10, 64, 4, 5, 6, 7, 63])          # the sizes of policy_size_cases.BANDITS_ADDED too
+@pytest.mark.parametrize("hidden", [1, 3, 4, 5, 64, 2, 6, 7, 63])
 def test_pack_round_trips_and_matches_the_library_count(hidden, arms):
     from metagym_amd import _lib
     lib = _lib.load()
@@ -165,7 +165,7 @@ def test_the_carry_is_the_maze_policies_carry():
     assert st.step == 0 and PHILOX_TAG == 0x4241
 
 
-@pytest.mark.parametrize("hidden,arms", [(1, 2), (5, 3), (7, 10), (64, 64)])
+@pytest.mark.parametrize("hidden,arms", [(1, 2), (5, 3), (7, 10), (64, 64), (2, 5), (4, 4), (6, 7), (7, 63), (63, 6)])
 def test_reference_equals_the_scalar_restatement(hidden, arms):
     P, n = 3, 11 if hidden < 64 else 4
     pol = _random_policy(P, hidden, arms, 5)

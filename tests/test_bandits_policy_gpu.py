@@ -440,11 +440,13 @@ def test_envs_that_are_over_do_nothing():
 
 
 # ---------------------------------------------------------------------------------------------------------- 8
-def test_negative_zero_and_nan_in_the_carry():
-    """Policy 0 keeps a pre-activation of exactly -0 at a first step: b, wr and wd are -0, wh is +0 on a carry handed in as
+@pytest.mark.parametrize("H", [5, 3])
+def test_negative_zero_and_nan_in_the_carry(H):
+    """H = 5 (a whole quad, then v.x alone) and H = 3 (a partial quad alone, one padding float behind it).
+    Policy 0 keeps a pre-activation of exactly -0 at a first step: b, wr and wd are -0, wh is +0 on a carry handed in as
     -0, and wa, all ones, is not looked up (no previous action). Policy 1 is ordinary; the envs 3 mod 4 hand it a NaN in
     h[0], which reaches every unit through wh and every logit through wo: arm 0. The NaN payload is not compared."""
-    N, K, H, M = 130, 10, 5, 7
+    N, K, M = 130, 10, 7
     rnd = make_policy(2, H, K, 16)
     wa, wr, wd, wh, b, wo, bo = (v.copy() for v in (rnd.wa, rnd.wr, rnd.wd, rnd.wh, rnd.b, rnd.wo, rnd.bo))
     wa[0], wr[0], wd[0], wh[0], b[0] = 1.0, -0.0, -0.0, 0.0, -0.0

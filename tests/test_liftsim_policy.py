@@ -21,7 +21,8 @@ def _policy(F, E, H, P=2, seed=1):
 
 
 # ---------------------------------------------------------------------------------------------- 1. the packed layout
-@pytest.mark.parametrize("F,E,H", [(2, 1, 1), (10, 4, 8), (33, 5, 7), (128, 32, 64), (127, 31, 3)])
+@pytest.mark.parametrize("F,E,H", [(2, 1, 1), (10, 4, 8), (33, 5, 7), (128, 32, 64), (127, 31, 3),
+                                   (5, 2, 2), (7, 3, 3), (33, 2, 5), (5, 3, 6), (7, 2, 7), (9, 3, 63)])     # policy_size_cases.LIFTSIM_ADDED
 def test_pack_round_trip_count_padding_and_offsets(F, E, H):
     from metagym_amd.liftsim import LiftPolicy
     from metagym_amd.liftsim import policy as LP
@@ -87,7 +88,8 @@ def _oracle_states(cfg, seed, steps, every, rs):
     (2, 1, 1, 1500, dict(dt=0.5, particle_number=12, generation_interval=150.0)),
     (10, 4, 8, 240, dict(dt=1.0, particle_number=12, generation_interval=15.0)),
     (33, 5, 3, 240, dict(dt=1.0, particle_number=40, generation_interval=4.0)),
-])
+] + [(F, E, H, 240, dict(dt=1.0, particle_number=16, generation_interval=8.0))         # policy_size_cases.LIFTSIM_ADDED and _KW
+     for F, E, H in ((5, 2, 2), (7, 3, 3), (33, 2, 5), (5, 3, 6), (7, 2, 7), (9, 3, 63))])
 def test_reference_matches_the_scalar_restatement_on_oracle_states(F, E, H, steps, kw):
     pol = PC.policies(F, E, H)
     rs = np.random.RandomState(F)

@@ -55,7 +55,7 @@ def _loops(pol, pid, win, h, pa, pr, pd):
     return g, np.array(hn, F)
 
 
-@pytest.mark.parametrize("hidden", [1, 5, 64])
+@pytest.mark.parametrize("hidden", [1, 5, 64, 2, 3, 4, 6, 7, 63])       # the last six: policy_size_cases.MAZE_ADDED
 @pytest.mark.parametrize("view_grid", [1, 2, 3])
 def test_pack_round_trips_and_matches_the_library_count(hidden, view_grid):
     from metagym_amd import _lib
@@ -163,7 +163,7 @@ def test_fresh_state():
     assert st.h[0, 0] == 0
 
 
-@pytest.mark.parametrize("hidden,view_grid", [(1, 1), (5, 2), (7, 3)])
+@pytest.mark.parametrize("hidden,view_grid", [(1, 1), (5, 2), (7, 3), (2, 1), (3, 2), (6, 3), (7, 1), (4, 2), (63, 3)])
 def test_reference_equals_the_scalar_restatement(hidden, view_grid):
     P, n = 3, 11
     pol = _random_policy(P, hidden, view_grid, 5)

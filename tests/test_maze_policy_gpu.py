@@ -271,8 +271,11 @@ def test_staged_and_per_lane_weight_reads_agree(H, view_grid):
     assert len(set(s.actions.cpu().numpy().ravel().tolist())) == 4
 
 
-def test_negative_zero_and_nan_pre_activations_on_the_device():
-    """Two policies on one open SURVIVAL maze (walls on the border only, start in the middle, life 2.5), H = 2, three steps.
+@pytest.mark.parametrize("H", [2, 3])
+def test_negative_zero_and_nan_pre_activations_on_the_device(H):
+    """Two policies on one open SURVIVAL maze (walls on the border only, start in the middle, life 2.5), H = 2, and H = 3,
+    where the partial quad adds v.x, v.y and v.z and skips one padding float (0 * -0 is -0, so a read too far would not
+    show in a zero; the poisoned padding of test_policy_sizes_gpu.py is what shows it), three steps.
     Policy 0 keeps a pre-activation of exactly -0: a sum is -0 only if every addend is, so b = -0, every input weight is -0
     (all its inputs are >= 0: no wall is in view for three steps, and the previous reward of SURVIVAL is the food eaten), and
     the recurrent weights are +0 on a carry handed in as -0 (+0 * -0 = -0). bo prefers move 0, which keeps the window clear of
@@ -280,7 +283,7 @@ def test_negative_zero_and_nan_pre_activations_on_the_device():
     times a handed-in previous reward of 2 = -inf. From then on every unit of it is NaN (0 * NaN) and every logit too: move
     0. Actions and h equal the reference's; the NaN payload is not compared."""
     from metagym_amd.metamaze import MazeTaskSampler
-    N, T, H, vg = 65, 3, 2, 1
+    N, T, vg = 65, 3, 1
     D, ww = input_dim(vg), 9
     base = MazeTaskSampler(n=9, allow_loops=True, step_reward=-0.01, food_density=0.1, food_interval=4, initial_life=2.5,
                            max_life=4.0, seed=20)

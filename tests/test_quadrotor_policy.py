@@ -34,7 +34,7 @@ def _loops(policy, x, pid):
     return np.array(a, F)
 
 
-@pytest.mark.parametrize("hidden", [0, 1, 5])
+@pytest.mark.parametrize("hidden", [0, 1, 5, 33, 256])
 @pytest.mark.parametrize("obs_dim", [16, 19])
 def test_reference_equals_the_scalar_restatement(hidden, obs_dim):
     pol = pc.make_policy(hidden, obs_dim)
@@ -93,7 +93,7 @@ def test_relu_of_negative_zero_and_nan_is_plus_zero():
     assert np.array_equal(out.view(np.uint32), np.zeros((3, 4), np.uint32))
 
 
-@pytest.mark.parametrize("hidden", [0, 1, 256])
+@pytest.mark.parametrize("hidden", [0, 1, 256, 33])
 @pytest.mark.parametrize("obs_dim", [16, 19])
 def test_packing_round_trips_and_matches_the_library_count(hidden, obs_dim):
     from metagym_amd import _lib

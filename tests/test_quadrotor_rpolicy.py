@@ -23,7 +23,7 @@ def _pad4(v):
     return (v + 3) // 4 * 4
 
 
-@pytest.mark.parametrize("hidden", rc.HIDDEN)
+@pytest.mark.parametrize("hidden", rc.HIDDEN + (2, 3, 4, 32, 33, 35, 36, 39, 63))      # policy_size_cases.QUADROTOR_RECURRENT_ADDED
 @pytest.mark.parametrize("obs_dim", [16, 19])
 def test_packing_round_trips_and_matches_the_layout_formula(hidden, obs_dim):
     from metagym_amd import _lib
@@ -186,7 +186,7 @@ def test_a_nan_observation_entry_reaches_every_unit():
     assert np.isnan(new.h).all() and np.isnan(a).all()                     # neither the clamp nor the sums drop it
 
 
-@pytest.mark.parametrize("hidden", rc.HIDDEN)
+@pytest.mark.parametrize("hidden", rc.HIDDEN + (2, 3, 4, 32, 33, 35, 36, 39, 63))      # policy_size_cases.QUADROTOR_RECURRENT_ADDED
 @pytest.mark.parametrize("obs_dim", [16, 19])
 def test_two_calls_through_the_state_equal_one_scalar_pass(hidden, obs_dim):
     from metagym_amd.quadrotor import QuadrotorPolicyState

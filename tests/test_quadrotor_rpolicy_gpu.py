@@ -303,25 +303,27 @@ def test_episodic_clears_the_carry_at_a_done():
         _env(nt=4).rollout_policy(pol, 2, ids, episodic=True)              # nothing resets: nothing to clear at
 
 
-def test_negative_zero_pre_activation_on_the_device():
-    """test_quadrotor_rpolicy.py's signed-zero case through the launch, on all five units of an H = 5 policy (three padding
-    entries behind wh). From a fresh carry every input but x is +0; with b = -0 and every weight a zero signed against its
-    input each product is -0, so every z, every hn and, with bo = -0 and wo = 1, every action is -0. One padding term
-    0 * h multiplied in would turn a z into +0."""
+@pytest.mark.parametrize("H", [5, 35])
+def test_negative_zero_pre_activation_on_the_device(H):
+    """test_quadrotor_rpolicy.py's signed-zero case through the launch, on all units of an H = 5 policy (three padding
+    entries behind wh) and of an H = 35 one (a group of 32, then a partial quad of three with one padding entry). From a
+    fresh carry every input but x is +0; with b = -0 and every weight a zero signed against its input each product is -0,
+    so every z, every hn and, with bo = -0 and wo = 1, every action is -0. One padding term 0 * h multiplied in would turn
+    a z into +0."""
     from metagym_amd.quadrotor import QuadrotorRecurrentPolicy
     f = np.float32
     env = _env(70)
     x0 = env.reset(init_velocity=np.zeros((70, 3)), init_angular_velocity=np.zeros((70, 3))).cpu().numpy()
     assert np.array_equal(_bits(x0), np.tile(_bits(x0[:1]), (70, 1)))        # one state, one sign pattern
-    wx = np.tile(np.where(np.signbit(x0[0]), f(0.0), f(-0.0)).astype(f), (1, 5, 1))
+    wx = np.tile(np.where(np.signbit(x0[0]), f(0.0), f(-0.0)).astype(f), (1, H, 1))
     neg = lambda *s: np.full(s, -0.0, f)
-    pol = QuadrotorRecurrentPolicy(wx, neg(1, 5, 4), neg(1, 5), neg(1, 5), neg(1, 5, 5), neg(1, 5), np.ones((1, 4, 5), f),
+    pol = QuadrotorRecurrentPolicy(wx, neg(1, H, 4), neg(1, H), neg(1, H), neg(1, H, H), neg(1, H), np.ones((1, 4, H), f),
                                    neg(1, 4))
     res = env.rollout_policy(pol, 1, record=True)
     assert np.array_equal(_bits(res.actions.cpu().numpy()), np.full((1, 70, 4), NEG0, np.uint32))
-    assert np.array_equal(_bits(res.state.h.cpu().numpy()), np.full((70, 5), NEG0, np.uint32))
-    a, new = pol.reference(x0, np.zeros(70, int), _fresh(70, 5).numpy())
-    assert np.array_equal(_bits(a), np.full((70, 4), NEG0, np.uint32)) and np.array_equal(_bits(new.h), np.full((70, 5), NEG0, np.uint32))
+    assert np.array_equal(_bits(res.state.h.cpu().numpy()), np.full((70, H), NEG0, np.uint32))
+    a, new = pol.reference(x0, np.zeros(70, int), _fresh(70, H).numpy())
+    assert np.array_equal(_bits(a), np.full((70, 4), NEG0, np.uint32)) and np.array_equal(_bits(new.h), np.full((70, H), NEG0, np.uint32))
 
 
 def test_after_load_state_dict_the_launch_uses_the_state_not_the_stale_buffer():

@@ -21,7 +21,7 @@ def _policy(P, H, d=D, a=A, seed=0):
     return WalkerPolicy(u(P, H, d), u(P, H), u(P, a, H), u(P, a))
 
 
-@pytest.mark.parametrize("H", [0, 1, 70, 256])
+@pytest.mark.parametrize("H", [0, 1, 70, 256, 64, 129])
 def test_pack_unpack_round_trip_and_layout(H):
     pol = _policy(3, H)
     packed = pol.pack()

@@ -28,7 +28,7 @@ def _state(N, H, a=A, seed=1):
                                 g.uniform(-3, 3, size=N).astype(f32), (g.uniform(size=N) < 0.5).astype(np.uint8))
 
 
-@pytest.mark.parametrize("H", [1, 64, 65, 256])
+@pytest.mark.parametrize("H", [1, 64, 65, 256, 31, 32, 33, 129, 193])
 def test_pack_unpack_round_trip_and_layout(H):
     pol = _policy(3, H)
     packed = pol.pack()
