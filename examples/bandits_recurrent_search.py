@@ -6,7 +6,8 @@ P candidate policies x V sampled Classical tasks run a whole trial inside ONE ke
 p * V + v plays candidate p on task v for `--pulls` pulls with the policy's memory kept (the RL^2 setting: the good arm is
 hidden, and what the agent saw of its rewards decides the next pull). The fitness of a candidate is its mean regret over the
 tasks, the expected reward it gave away against always pulling the best arm; it is printed next to the mean regret of
-uniform-random play (epsilon = 1) on the same tasks."""
+uniform-random play (epsilon = 1) on the same tasks. examples/bandits_classical_baselines.py prints the mean regret of Thompson
+sampling, UCB1, epsilon-greedy and the Gittins index on these tasks and seeds."""
 import argparse
 import os
 import sys

@@ -1478,6 +1478,95 @@ int mg_bandits_policy_rollout(const mg_bandits_config *cfg, int32_t n_envs, cons
                               double *regret, int32_t *actions, float *reward, uint8_t *done, int32_t *info_steps,
                               double *expected_gain, double *best_gain, uint8_t *invalid, void *stream);
 
+/* Closed-loop rollouts with a classical learner inside the launch (csrc/bandits_learner.hip): greedy on a Beta prior, UCB, an
+ * index table (Gittins) and Thompson sampling, the baselines a learned bandit policy is reported against.
+ *
+ * n_steps Bandits.step calls of every env in one launch, the action of env e at every step chosen inside the kernel by
+ * learner learner_ids[e] of P parameter rows of ONE kind from the env's own counts. The step is mg_bandits_step's, draw for
+ * draw, so replaying the recorded actions through mg_bandits_step from the same state gives the same records and end state
+ * bit for bit. The records, the five results and the over-env rule are mg_bandits_policy_rollout's.
+ *
+ * Memory (the carry): pulls i32 [N][K] and wins i32 [N][K]. After a step in which env e pulled arm a and got reward r,
+ * pulls[e][a] += 1 and wins[e][a] += (r == 1); an exploratory pull counts too. An env that is over does nothing and keeps its
+ * counts. episodic != 0: a done with auto_reset zeroes the env's counts (no counts are carried into a redrawn task);
+ * episodic == 0: the counts survive. Counts must satisfy 0 <= wins <= pulls (validated by the caller; the kernel never
+ * reads outside the table for other values).
+ *
+ * The arithmetic is defined exactly: float32 operations, rounded once, never fused, and integers. K = arms, 2 <= K <= 64.
+ * Every kind computes K scores and plays the lowest index among the maxima (best = score[0]; for k >= 1: if score[k] >
+ * best). Parameters are finite, so no score is NaN. n = pulls[k], w = wins[k], (float) is int32 -> float32, `/` and sqrt
+ * are the IEEE correctly rounded float32 operations; params row p = a0, b0, c, 0.
+ *   MG_BANDITS_LEARNER_GREEDY    a0, b0 > 0:   score = ((float)w + a0) / (((float)n + a0) + b0)
+ *   MG_BANDITS_LEARNER_UCB       c >= 0 (UCB1: c = 2). If an arm has n = 0: the lowest such arm (as scores: +inf for the
+ *                                unpulled arms, 0 for the others). Otherwise t = the int64 sum of the pulls, converted to
+ *                                float32, and score = (float)w / (float)n + sqrt((c * log32(t)) / (float)n)
+ *   MG_BANDITS_LEARNER_TABLE     an index policy read from table f32 [P][(C + 1)(C + 2) / 2], C = table_cap in [1, 1023];
+ *                                the cell of (n, s), 0 <= s <= n <= C, is n (n + 1) / 2 + s. n <= C: score = cell (n, w);
+ *                                otherwise cell (C, floor(w C / n)), in 64-bit integers
+ *   MG_BANDITS_LEARNER_THOMPSON  a0, b0 >= 1:  alpha = (float)w + a0, beta = (float)(n - w) + b0,
+ *                                X = gamma(alpha; which = 0), Y = gamma(beta; which = 1), score = X / (X + Y)
+ * Exploration (all kinds but Thompson, which takes none) is mg_bandits_policy_rollout's rule, unchanged: thr =
+ * eps_threshold[p]; out = philox4x32_10(c0 = e, c1 = n lo, c2 = n hi, c3 = 0x4241, key = seed) at carry step n = step0 + t;
+ * action = (out[0] < thr) ? (out[1] % K) : the maximum's index.
+ *
+ * log32(x), for positive normal x: fdlibm's single-precision log, one operation at a time. With i the bits of x:
+ *   i += 0x3f800000 - 0x3f3504f3;  k = (i >> 23) - 127;  m = the float with bits (i & 0x007fffff) + 0x3f3504f3
+ *   f = m - 1;  s = f / (2 + f);  z = s*s;  w = z*z;  t1 = w * (Lg2 + w*Lg4);  t2 = z * (Lg1 + w*Lg3);  R = t2 + t1
+ *   hfsq = (0.5*f)*f;  dk = (float)k;  result = (((s*(hfsq + R) + dk*ln2_lo) - hfsq) + f) + dk*ln2_hi
+ * with, by their float32 bits, Lg1 = 0x3f2aaaaa, Lg2 = 0x3eccce13, Lg3 = 0x3e91e9ee, Lg4 = 0x3e789e26, ln2_hi = 0x3f317180,
+ * ln2_lo = 0x3717f7d1. Every argument the sampler can produce is a positive normal number.
+ *
+ * gamma(a; which) for env e, arm k, carry step n (Marsaglia-Tsang with a polar normal):
+ *   d = a - 0.33333334f;  c = 1 / sqrt(9*d);  u01(word) = (float)(((word >> 9) << 1) | 1) * 2^-24 (exact, never 0 or 1)
+ *   attempt i = 0 .. max_attempts - 1:
+ *     o = philox4x32_10(c0 = e, c1 = n lo, c2 = n hi, c3 = 0x4C000000 | k << 17 | which << 16 | i, key = seed)
+ *     v1 = 2*u01(o[0]) - 1;  v2 = 2*u01(o[1]) - 1;  s = v1*v1 + v2*v2;  if s >= 1: next attempt
+ *     x = v1 * sqrt((-2*log32(s)) / s);  v = 1 + c*x;  if v <= 0: next attempt
+ *     v3 = (v*v)*v;  accept if log32(u01(o[2])) < (((0.5*x)*x + d) - d*v3) + d*log32(v3): the result is d*v3
+ *   all attempts exhausted: the result is d. */
+#define MG_BANDITS_LEARNER_GREEDY 0
+#define MG_BANDITS_LEARNER_UCB 1
+#define MG_BANDITS_LEARNER_TABLE 2
+#define MG_BANDITS_LEARNER_THOMPSON 3
+
+typedef struct mg_bandits_learner {
+    int32_t kind;                      /* MG_BANDITS_LEARNER_* */
+    int32_t n_learners;                /* P */
+    int32_t arms;                      /* K */
+    const float *params;               /* DEVICE f32 [n_learners][4]: a0, b0, c, 0 */
+    const uint32_t *eps_threshold;     /* DEVICE u32 [n_learners], or NULL: no exploration (Thompson: must be NULL) */
+    const float *table;                /* DEVICE f32 [n_learners][(table_cap + 1)(table_cap + 2) / 2] (TABLE only) */
+    int32_t table_cap;                 /* C in [1, 1023] (TABLE only) */
+    int32_t max_attempts;              /* in [1, 64] (THOMPSON only) */
+} mg_bandits_learner;
+
+/* The carry between launches, updated in place. */
+typedef struct mg_bandits_learner_carry {
+    int32_t *pulls;                    /* DEVICE i32 [N][K] */
+    int32_t *wins;                     /* DEVICE i32 [N][K] */
+} mg_bandits_learner_carry;
+
+/* One launch: one lane per env, one wave per workgroup, the counts in LDS (35 264 B at K = 64). learner_ids i32 [N], each
+ * in [0, n_learners): validated by the caller (the kernel clamps an id). step0 is the carry step of the launch's first step.
+ * Results and optional records: as mg_bandits_policy_rollout. Refused on the host, before anything is launched: NULL
+ * required pointers, a table learner without table (MG_ERR_NULL_POINTER); what mg_bandits_step refuses in cfg, a kind
+ * outside 0..3, learner->arms != cfg->arms, Thompson with eps_threshold (MG_ERR_BAD_CONFIG); n_envs <= 0, n_steps < 1,
+ * n_learners < 1, arms outside [2, 64], table_cap outside [1, 1023], max_attempts outside [1, 64] (MG_ERR_BAD_SIZE).
+ * Nothing is allocated and nothing synchronises: the call is hipGraph-capturable as it stands. */
+int mg_bandits_learner_rollout(const mg_bandits_config *cfg, int32_t n_envs, const mg_bandits_state *state, int32_t n_steps,
+                               const mg_bandits_learner *learner, const int32_t *learner_ids,
+                               const mg_bandits_learner_carry *carry, uint64_t seed, uint64_t step0, int32_t episodic,
+                               double *ret_total, double *ret_episode, int32_t *episode_len, int32_t *episodes,
+                               double *regret, int32_t *actions, float *reward, uint8_t *done, int32_t *info_steps,
+                               double *expected_gain, double *best_gain, uint8_t *invalid, void *stream);
+
+/* The K scores the step at carry step step0 would compute for every env, f32 [N][K], from one launch that steps nothing and
+ * changes nothing (the carry is only read). attempts i32 [N][K][2] or NULL (Thompson only; ignored otherwise): the number
+ * of attempts gamma(.; which) made, max_attempts + 1 where the fallback d was taken. Refusals as above. */
+int mg_bandits_learner_scores(int32_t n_envs, const mg_bandits_learner *learner, const int32_t *learner_ids,
+                              const mg_bandits_learner_carry *carry, uint64_t seed, uint64_t step0, float *scores,
+                              int32_t *attempts, void *stream);
+
 /* ========================================================================================
  * LiftSim — replaces metagym/liftsim/environment/env.py LiftSim (ABI 10)
  * ======================================================================================== */

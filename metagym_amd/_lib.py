@@ -315,6 +315,17 @@ class BanditsPolicyDesc(C.Structure):
 BanditsPolicyCarry = MazePolicyCarry   # mg_bandits_policy_carry is mg_maze_policy_carry
 
 
+class BanditsLearnerDesc(C.Structure):
+    """mg_bandits_learner (device pointers)"""
+    _fields_ = [("kind", C.c_int32), ("n_learners", C.c_int32), ("arms", C.c_int32), ("params", C.c_void_p),
+                ("eps_threshold", C.c_void_p), ("table", C.c_void_p), ("table_cap", C.c_int32), ("max_attempts", C.c_int32)]
+
+
+class BanditsLearnerCarry(C.Structure):
+    """mg_bandits_learner_carry (device pointers)"""
+    _fields_ = [("pulls", C.c_void_p), ("wins", C.c_void_p)]
+
+
 class LiftsimConfig(C.Structure):
     """mg_liftsim_config"""
     _fields_ = [("floors", C.c_int32), ("elevators", C.c_int32), ("generator", C.c_int32), ("queue_capacity", C.c_int32),
@@ -459,6 +470,11 @@ SIGNATURES = {
     "mg_bandits_policy_rollout": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), C.c_int32,
                                             C.POINTER(BanditsPolicyDesc), _P, C.POINTER(BanditsPolicyCarry), C.c_uint64,
                                             C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mg_bandits_learner_rollout": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), C.c_int32,
+                                             C.POINTER(BanditsLearnerDesc), _P, C.POINTER(BanditsLearnerCarry), C.c_uint64,
+                                             C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mg_bandits_learner_scores": (C.c_int, [C.c_int32, C.POINTER(BanditsLearnerDesc), _P, C.POINTER(BanditsLearnerCarry),
+                                            C.c_uint64, C.c_uint64, _P, _P, _P]),
 }
 
 _lib = None

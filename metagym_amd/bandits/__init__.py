@@ -1,5 +1,7 @@
 """Batched K-armed Bernoulli bandits on the GPU (mirrors metagym/bandits/__init__.py: id bandits-v0)."""
 from .bandits_env import DISTRIBUTIONS, Bandits, classical_lo_hi
+from .learner import BanditLearner, BanditLearnerState, BanditsLearnerRollout, gittins_index_table, log32
 from .policy import BanditPolicy, BanditPolicyState, BanditsPolicyRollout
 
-__all__ = ["Bandits", "DISTRIBUTIONS", "classical_lo_hi", "BanditPolicy", "BanditPolicyState", "BanditsPolicyRollout"]
+__all__ = ["Bandits", "DISTRIBUTIONS", "classical_lo_hi", "BanditPolicy", "BanditPolicyState", "BanditsPolicyRollout",
+           "BanditLearner", "BanditLearnerState", "BanditsLearnerRollout", "gittins_index_table", "log32"]

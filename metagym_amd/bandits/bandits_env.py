@@ -317,7 +317,94 @@ class Bandits(object):
         _lib.check(rc, "mg_bandits_policy_rollout")
         return res
 
-    def _policy_ids(self, policy_ids, P):
+    def _learner_call(self, learner, state, learner_ids, seed, T):
+        """The checks `rollout_learner` and `learner_scores` share: (state, ids, params, thr, table, desc) or an exception."""
+        import torch
+        from .learner import KINDS, BanditLearner, BanditLearnerState
+        if not isinstance(learner, BanditLearner):
+            raise TypeError("learner must be a BanditLearner, got %s" % type(learner).__name__)
+        N, K, dev, P = self.num_envs, self.K, self.device, learner.num_learners
+        if learner.arms != K:
+            raise ValueError("the learner was built for %d arms, the env has %d" % (learner.arms, K))
+        if not (0 <= int(seed) < 2 ** 64):
+            raise ValueError("seed must be in [0, 2^64), got %d" % int(seed))
+        if state is None:
+            state = BanditLearnerState.zeros(N, K, dev)
+        elif not isinstance(state, BanditLearnerState):
+            raise TypeError("state must be a BanditLearnerState, got %s" % type(state).__name__)
+        for name in ("pulls", "wins"):
+            v = getattr(state, name)
+            if not isinstance(v, torch.Tensor) or tuple(v.shape) != (N, K) or v.dtype != torch.int32 or v.device != dev:
+                raise ValueError("state.%s must be an int32 tensor of shape (%d, %d) on %s" % (name, N, K, dev))
+        if not (0 <= state.step < 2 ** 64 - T):
+            raise ValueError("state.step = %d is outside [0, 2^64 - steps)" % state.step)
+        ids_d = self._policy_ids(learner_ids, P, "learner_ids")
+        params, thr, table = learner.to(dev)
+        desc = _lib.BanditsLearnerDesc(KINDS[learner.kind], P, K, params.data_ptr(), thr.data_ptr() if thr is not None else None,
+                                       table.data_ptr() if table is not None else None, learner.table_cap, learner.max_attempts)
+        return state, ids_d, (params, thr, table), desc
+
+    def rollout_learner(self, learner, steps, learner_ids=None, state=None, seed=0, record=False, episodic=True):
+        """`steps` pulls of every env in ONE launch with a classical learner inside the kernel: env e plays parameter row
+        `learner_ids[e]` of `learner` (a `BanditLearner`: greedy, UCB, an index table or Thompson sampling; None = e % P)
+        from its own counts (bandits/learner.py defines the arithmetic exactly, so `BanditLearner.reference` reproduces every
+        action). `state` is the carry of the previous call (a `BanditLearnerState`; None = a fresh one); it is not written,
+        the end carry comes back as `.state` of the result with `step` advanced by `steps`. `seed` keys the sampler's and the
+        exploration draws. The step is `rollout`'s, draw for draw, with `auto_reset` and `resample_task` as the env was
+        built. `episodic=True` (the default here: a classical learner must not carry counts into a redrawn task) zeroes an
+        env's counts at a done with auto_reset; `episodic=False` keeps them. An env that is over when a step begins does
+        nothing in that step, as in `rollout_policy`. Returns a `BanditsLearnerRollout` (the fields of
+        `BanditsPolicyRollout`; records [steps, N] only with `record=True`). Nothing synchronises when `learner_ids` is None
+        or the array of the previous call, so after `learner.to(device)` the call can be captured in a hipGraph. The counts
+        of `state` must satisfy 0 <= wins <= pulls (`state.validate()` checks; the kernel reads nothing out of bounds
+        whatever they hold). A refused call raises and launches nothing."""
+        import torch
+        from .learner import BanditLearnerState, BanditsLearnerRollout
+        T, N, dev = int(steps), self.num_envs, self.device
+        if T < 1:
+            raise ValueError("steps must be at least 1, got %d" % T)
+        state, ids_d, keep, desc = self._learner_call(learner, state, learner_ids, seed, T)
+        # everything is checked: from here on the env and the new carry are written
+        carry = BanditLearnerState(state.pulls.clone().contiguous(), state.wins.clone().contiguous(), step=state.step + T)
+        carry_c = _lib.BanditsLearnerCarry(carry.pulls.data_ptr(), carry.wins.data_ptr())
+        f64 = lambda: torch.empty(N, dtype=torch.float64, device=dev)
+        i32 = lambda: torch.empty(N, dtype=torch.int32, device=dev)
+        res = BanditsLearnerRollout(f64(), f64(), i32(), i32(), f64(), carry)
+        if record:
+            res.actions = torch.empty(T, N, dtype=torch.int32, device=dev)
+            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+            res.info_steps = torch.empty(T, N, dtype=torch.int32, device=dev)
+            res.expected_gain = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.best_gain = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.invalid = torch.empty(T, N, dtype=torch.uint8, device=dev)
+        cfg = self._cfg(*(self.resample_task or (None,)))
+        rc = self._lib.mg_bandits_learner_rollout(cfg, N, self._state, T, desc, _lib.ptr(ids_d), carry_c, int(seed), state.step,
+                                                  int(bool(episodic)), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
+                                                  _lib.ptr(res.episode_len), _lib.ptr(res.episodes), _lib.ptr(res.regret),
+                                                  _lib.ptr(res.actions), _lib.ptr(res.reward), _lib.ptr(res.done),
+                                                  _lib.ptr(res.info_steps), _lib.ptr(res.expected_gain), _lib.ptr(res.best_gain),
+                                                  _lib.ptr(res.invalid), self._stream())
+        _lib.check(rc, "mg_bandits_learner_rollout")
+        return res
+
+    def learner_scores(self, learner, state, learner_ids=None, seed=0, return_attempts=False):
+        """The K scores the next `rollout_learner` step would compute for every env from `state`, float32 [N, K], from one
+        launch that steps nothing and changes nothing: posterior draws (Thompson), indices, means. UCB with an unpulled arm:
+        +inf for the unpulled arms and 0 for the others. `return_attempts=True` returns (scores, attempts int32 [N, K, 2]):
+        the attempts the sampler made for X and Y, max_attempts + 1 where its fallback was taken (zeros unless Thompson)."""
+        import torch
+        N, K, dev = self.num_envs, self.K, self.device
+        state, ids_d, keep, desc = self._learner_call(learner, state, learner_ids, seed, 1)
+        scores = torch.empty(N, K, dtype=torch.float32, device=dev)
+        attempts = torch.zeros(N, K, 2, dtype=torch.int32, device=dev) if return_attempts else None
+        carry_c = _lib.BanditsLearnerCarry(state.pulls.contiguous().data_ptr(), state.wins.contiguous().data_ptr())
+        rc = self._lib.mg_bandits_learner_scores(N, desc, _lib.ptr(ids_d), carry_c, int(seed), state.step, _lib.ptr(scores),
+                                                 _lib.ptr(attempts), self._stream())
+        _lib.check(rc, "mg_bandits_learner_scores")
+        return (scores, attempts) if return_attempts else scores
+
+    def _policy_ids(self, policy_ids, P, name="policy_ids"):
         """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a hipGraph
         capture after its warm-up) neither uploads nor reads back."""
         import torch
@@ -327,11 +414,11 @@ class Bandits(object):
         else:
             ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
             if ids_h.shape != (N,):
-                raise ValueError("policy_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
+                raise ValueError("%s must have shape (%d,), got %s" % (name, N, tuple(ids_h.shape)))
             if ids_h.dtype.kind not in "iu":
-                raise ValueError("policy_ids must be integers, got %s" % ids_h.dtype)
+                raise ValueError("%s must be integers, got %s" % (name, ids_h.dtype))
             if int(ids_h.min()) < 0 or int(ids_h.max()) >= P:
-                raise ValueError("policy_ids must be in [0, %d)" % P)
+                raise ValueError("%s must be in [0, %d)" % (name, P))
         key = (P, ids_h.astype(np.int32).tobytes())
         keep = getattr(self, "_policy_ids_keep", None)
         if keep is None or keep[0] != key:

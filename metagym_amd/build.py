@@ -34,7 +34,7 @@ FILE_FLAGS = {"quadrotor.hip": ["-fno-slp-vectorize"], "quadrotor_tasks.hip": ["
 FILE_DEPS = {"quadrotor_tasks.hip": ["quadrotor.hip"], "quadrotor_policy.hip": ["quadrotor.hip"],
              "walker_policy.hip": ["walker.hip"], "walker_rpolicy.hip": ["walker.hip"], "maze_policy.hip": ["maze.hip"],
              "maze_expert.hip": ["maze.hip"],
-             "bandits_policy.hip": ["bandits.hip"], "liftsim_policy.hip": ["liftsim.hip"]}
+             "bandits_policy.hip": ["bandits.hip"], "bandits_learner.hip": ["bandits.hip"], "liftsim_policy.hip": ["liftsim.hip"]}
 
 
 def sources():
