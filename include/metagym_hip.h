@@ -699,7 +699,7 @@ int mg_maze2d_policy_rollout(const mg_maze_tasks *tasks, int32_t task_type, int3
  *                                   the low edge through a free border cell, maze_2d.py:24-29, which mg_maze2d_step follows)
  *                                   is NOT followed. Sampled mazes have closed borders, where the two agree.
  *   MG_MAZE_FIELD_CELLS_3D (K = 1)  the same with walls[c'] == 0 (maze_discrete_3d.py:63-65): the cell-level field of the
- *                                   continuous maze, which has no expert.
+ *                                   continuous maze, whose expert steers down it (mg_maze_steer_action).
  *   MG_MAZE_FIELD_TURNS    (K = 4)  MetaMazeDiscrete3D: state (ori_idx, cell); the four DISCRETE_ACTIONS cost one step each:
  *                                   turn -1, turn +1 (ori_idx mod 4), one cell backward, one cell forward along heading
  *                                   0 = +x, 1 = +y, 2 = -x, 3 = -y (maze_discrete_3d.py:51-60), into walls == 0 inside the grid.
@@ -724,7 +724,7 @@ int32_t mg_maze_distance_queue_capacity(void);
  * read in the slice of dist of the env's task; 0 if there is none (on a source, in an unreachable state, off the grid, or
  * with a field built for another table). A successor off the grid (the 2-D wrap) is never chosen. Reads state->grid,
  * state->ori_idx (TURNS) and state->task_id, writes `action` only and synchronises nothing. MG_MAZE_FIELD_CELLS_3D is
- * MG_ERR_BAD_CONFIG: the continuous maze has no expert. */
+ * MG_ERR_BAD_CONFIG: the continuous maze has no expert of this kind (mg_maze_steer_action is its own). */
 int mg_maze_expert_action(const mg_maze_tasks *tasks, int32_t kind, const int32_t *dist, int32_t n_envs,
                           const mg_maze_state *state, int32_t *action, void *stream);
 
@@ -740,6 +740,45 @@ int mg_maze2d_expert_rollout(const mg_maze_tasks *tasks, int32_t task_type, int3
                              int32_t obs_every, const int32_t *dist, float *obs_last, double *ret_total, double *ret_episode,
                              int32_t *episode_len, int32_t *episodes, int32_t *actions, float *reward, double *reward64,
                              uint8_t *done, float *obs, void *stream);
+
+/* The steering expert of the continuous maze: one launch, one lane per env. action[e] (f32 [N][2] = turn, walk) takes the
+ * env one cell down a MG_MAZE_FIELD_CELLS_3D field (dist i32 [T][n*n]), every decision by comparison, so it is one of
+ * (0,0), (0,1), (1,0), (-1,0). metamaze/expert.py steer_action_reference is the definition; the kernel reproduces it bit for bit:
+ *   off the grid, or d0 = dist[cell] <= 0 (a source, unreachable)                  -> (0, 0)
+ *   target cell: the first of (-1,0), (1,0), (0,-1), (0,1) inside the grid with walls == 0 and dist == d0 - 1; none -> (0, 0)
+ *   p = ((float)target + 0.5f) * (float)cell_size per axis;  v = p - loc in float32, widened to float64
+ *   hx = (double)(float)cos(ori), hy = (double)(float)sin(ori)   (cos / sin of the float64 heading, as the renderer takes them)
+ *   c = hx * vy - hy * vx,  d = hx * vx + hy * vy   (float64; the products are exact, one rounding each)
+ *   d > 0 and |c| <= TAN9 * d, TAN9 = (double)0.15838444f  -> (0, 1);   else (c >= 0 ? 1 : -1, 0)
+ * One env step at turn +-1 rotates 18 degrees, so the +-9 degree dead band is always reached. Reads state->grid, loc, ori and
+ * task_id (clamped into the table), writes `action` only, synchronises nothing. Refused: NULL pointers (state->loc and
+ * state->ori included), n_envs < 1, and whatever the maze steps refuse in an ESCAPE table. */
+int mg_maze_steer_action(const mg_maze_tasks *tasks, const int32_t *dist, int32_t n_envs, const mg_maze_state *state,
+                         float *action, void *stream);
+
+/* The host half of mg_maze3d_step alone: every argument check it makes for an observe-only call (action == NULL) and its LDS
+ * opt-in, no launch. MG_OK means mg_maze3d_step(..., NULL, obs, NULL, NULL, NULL, stream) will launch. */
+int mg_maze3d_step_check(const mg_maze_tasks *tasks, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                         int32_t continuous, int32_t auto_reset, int32_t n_envs, const mg_maze_state *state, void *obs,
+                         void *stream);
+
+/* The 3-D closed loop: mg_maze3d_rollout with the actions computed inside the launches. Before every step each env takes
+ * its expert's action on the state it holds (after an auto-reset: the new episode's start) and steps with it: discrete
+ * (continuous == 0) mg_maze_expert_action's rule on a MG_MAZE_FIELD_TURNS field (dist i32 [T][4][n*n]), continuous
+ * mg_maze_steer_action's rule on a MG_MAZE_FIELD_CELLS_3D field (dist i32 [T][n*n]). The launch pattern is
+ * mg_maze3d_rollout's: per recorded step one lane-per-env launch for the steps up to it, then the renderer of mg_maze3d_step
+ * in its observe-only form, so replaying the recorded actions through mg_maze3d_rollout gives the same records, frames and
+ * end state bit for bit. obs: K slices as for mg_maze3d_rollout. Per env, all required: ret_total, ret_episode (f64 [N]),
+ * episode_len, episodes (i32 [N]) as for mg_maze2d_policy_rollout; they are carried from launch to launch through these
+ * arrays (the first launch initialises them), the float64 sums in step order. Optional records, NULL = not written:
+ * actions (discrete i32 [n_steps][N], continuous f32 [n_steps][N][2]), reward f32, reward64 f64, done u8, each [n_steps][N].
+ * Refused before the first launch: NULL required pointers, n_steps < 1, obs_every < 0 and whatever mg_maze3d_step refuses.
+ * Nothing is allocated and nothing synchronises. */
+int mg_maze3d_expert_rollout(const mg_maze_tasks *tasks, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                             int32_t continuous, int32_t auto_reset, int32_t n_envs, const mg_maze_state *state,
+                             int32_t n_steps, int32_t obs_every, const int32_t *dist, void *obs, double *ret_total,
+                             double *ret_episode, int32_t *episode_len, int32_t *episodes, void *actions, float *reward,
+                             double *reward64, uint8_t *done, void *stream);
 
 /* ========================================================================================
  * MetaLocomotion walkers (humanoid / ant) — replaces, for N envs, WalkerBaseEnv.step

@@ -417,6 +417,12 @@ SIGNATURES = {
     "mg_maze2d_expert_rollout": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.POINTER(MazeState), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                            _P, _P, _P]),
+    "mg_maze_steer_action": (C.c_int, [C.POINTER(MazeTasks), _P, C.c_int32, C.POINTER(MazeState), _P, _P]),
+    "mg_maze3d_step_check": (C.c_int, [C.POINTER(MazeTasks), C.POINTER(MazeView), C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.POINTER(MazeState), _P, _P]),
+    "mg_maze3d_expert_rollout": (C.c_int, [C.POINTER(MazeTasks), C.POINTER(MazeView), C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.POINTER(MazeState), C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, _P, _P]),
     "mg_walker_reset": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
                                   C.c_int32, C.POINTER(WalkerState), _P, _P, _P, _P]),
     "mg_walker_step": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),

@@ -1570,6 +1570,15 @@ extern "C" int mg_maze3d_step(const mg_maze_tasks *T, const mg_maze_view *view, 
                             stream, false);
 }
 
+// the observe-only call's host half, for a caller in another translation unit (maze_expert.hip) that must refuse before its
+// first launch what mg_maze3d_step would refuse
+extern "C" int mg_maze3d_step_check(const mg_maze_tasks *T, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                                    int32_t continuous, int32_t auto_reset, int32_t n, const mg_maze_state *st, void *obs,
+                                    void *stream) {
+    return maze3d_step_impl(T, view, task_type, max_steps, continuous, auto_reset, n, st, nullptr, obs, nullptr, nullptr,
+                            nullptr, stream, true);
+}
+
 extern "C" int mg_maze2d_rollout(const mg_maze_tasks *T, int32_t task_type, int32_t max_steps, int32_t view_grid,
                                  int32_t auto_reset, int32_t n, const mg_maze_state *st, int32_t n_steps, int32_t obs_every,
                                  const int32_t *actions, float *obs, float *reward, double *reward64, uint8_t *done,

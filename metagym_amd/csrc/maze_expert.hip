@@ -1,5 +1,5 @@
 // maze_expert.hip — MetaMaze shortest-path fields and the expert that descends them (mg_maze_distance_field,
-// mg_maze_expert_action, mg_maze2d_expert_rollout).
+// mg_maze_expert_action, mg_maze2d_expert_rollout, mg_maze_steer_action, mg_maze3d_expert_rollout).
 //
 // A translation unit of its own, like maze_policy.hip and for the same reason: it takes maze.hip's device functions
 // (load_task, load_agent, transition_discrete, eval_scalar, eval_cells, reset_cells, reset_agent, observe_2d, rollout_records)
@@ -21,6 +21,12 @@
 // The expert. One lane per env looks at the (at most four) successors of the env's state under the step's own rule and takes
 // the lowest action whose successor is one step nearer; mg_maze2d_expert_rollout is maze2d_rollout_kernel's step body in its
 // order with the action load replaced by that choice.
+//
+// The 3-D demonstrations (mg_maze_steer_action, mg_maze3d_expert_rollout). The continuous maze's expert steers: towards the
+// centre of the first neighbour cell one step nearer in a CELLS_3D field, walking inside a +-9 degree dead band and turning
+// otherwise, every decision a comparison (me_steer_pick). mg_maze3d_expert_rollout follows mg_maze3d_rollout's launch pattern:
+// per recorded frame one lane-per-env launch of maze3d_advance_kernel's body with the action load replaced by the pick
+// (maze3d_expert_advance_kernel), then the untouched renderer through mg_maze3d_step's observe-only form.
 #define MG_MAZE_CORE_ONLY
 #include "maze.hip"
 
@@ -271,6 +277,134 @@ __global__ __launch_bounds__(ME_ROLL_BLOCK) void maze2d_expert_rollout_kernel(mg
     po.episodes[e] = episodes;
 }
 
+// The steering expert's action in the state `a` holds (include/metagym_hip.h states the rule; metamaze/expert.py
+// steer_action_reference is the definition): (0, 0), (0, 1) or (+-1, 0), every decision a comparison. `field` is the task's
+// [n*n] slice of a CELLS_3D field. d0 and the four neighbours' walls and distances are read at once, from addresses that
+// depend on the cell alone, as in me_expert_pick; the lowest descending neighbour is the last one kept.
+__device__ __forceinline__ void me_steer_pick(const Task &t, const int32_t *field, const Agent &a, float &turn, float &walk) {
+    turn = 0.0f;
+    walk = 0.0f;
+    if (a.gx < 0 || a.gx >= t.n || a.gy < 0 || a.gy >= t.n) return;
+    const int c = a.gx * t.n + a.gy, d0 = field[c];
+    int best = -1;
+#pragma unroll
+    for (int act = 3; act >= 0; --act) {
+        const int ti = a.gx + (act == 0 ? -1 : (act == 1 ? 1 : 0));
+        const int tj = a.gy + (act == 2 ? -1 : (act == 3 ? 1 : 0));
+        const bool in = ti >= 0 && ti < t.n && tj >= 0 && tj < t.n;
+        const int tc = in ? ti * t.n + tj : c;
+        const int8_t w = t.walls[tc];
+        const int ds = field[tc];
+        if (in && w == 0 && ds == d0 - 1) best = act;
+    }
+    if (d0 <= 0 || best < 0) return;
+    const int tx = a.gx + (best == 0 ? -1 : (best == 1 ? 1 : 0));
+    const int ty = a.gy + (best == 2 ? -1 : (best == 3 ? 1 : 0));
+    const float cs = (float)t.cell_size;
+    const float px = ((float)tx + 0.5f) * cs, py = ((float)ty + 0.5f) * cs;   // the target cell's centre
+    const double vx = (double)(px - a.lx), vy = (double)(py - a.ly);
+    // the heading as the renderer takes it (es->s_ori = sin(a.ori)), rounded to float32: a last-bit difference between two
+    // libms cannot move a comparison, and the four products below are exact in float64
+    const double hx = (double)(float)cos(a.ori), hy = (double)(float)sin(a.ori);
+    const double cr = hx * vy - hy * vx, dt = hx * vx + hy * vy;
+    const double TAN9 = (double)0.15838444f;                                  // tan(9 deg): half of one step's 18 deg turn
+    if (dt > 0.0 && fabs(cr) <= TAN9 * dt) walk = 1.0f;
+    else turn = cr >= 0.0 ? 1.0f : -1.0f;
+}
+
+__global__ __launch_bounds__(ME_BLOCK) void maze_steer_action_kernel(mg_maze_tasks T, const int32_t *dist, int n_envs,
+                                                                     mg_maze_state st, float *action) {
+    const int e = blockIdx.x * ME_BLOCK + threadIdx.x;
+    if (e >= n_envs) return;
+    const int tid = me_clamp_task(st.task_id[e], T.n_tasks);
+    const Task t = load_task(T, tid);
+    Agent a;
+    a.gx = st.grid[e];
+    a.gy = st.grid[n_envs + e];
+    a.lx = st.loc[e];
+    a.ly = st.loc[n_envs + e];
+    a.ori = st.ori[e];
+    float turn, walk;
+    me_steer_pick(t, dist + (size_t)tid * t.nn, a, turn, walk);
+    action[2 * (size_t)e] = turn;
+    action[2 * (size_t)e + 1] = walk;
+}
+
+struct Me3Out {
+    double *ret_total, *ret_episode;        // [n]
+    int32_t *episode_len, *episodes;        // [n]
+};
+struct Me3Rec {                             // [T][n] each (continuous actions [T][n][2]); each may be null
+    void *actions;
+    float *reward;
+    double *reward64;
+    uint8_t *done;
+};
+
+// maze3d_advance_kernel's body in its order for the steps s0 .. s1-1 of a demonstration, one lane per env, one wave per
+// workgroup, the agent in registers, the action chosen from the field on the state the lane holds. The returns travel from
+// stretch to stretch through `po`: the stretch that starts at step 0 begins them, a later one picks them up; "the episode has
+// ended" is episodes > 0. Inside the step loop the kernel stores only what `rec` asks for.
+template <bool CONT>
+__global__ __launch_bounds__(ME_ROLL_BLOCK) void maze3d_expert_advance_kernel(mg_maze_tasks T, mg_maze_state st, double col_dist,
+                                                                              int task_type, int max_steps, int auto_reset,
+                                                                              int n_envs, int s0, int s1, const int32_t *dist,
+                                                                              Me3Out po, Me3Rec rec) {
+    const int e = blockIdx.x * ME_ROLL_BLOCK + threadIdx.x;
+    if (e >= n_envs) return;
+    const int tid = me_clamp_task(st.task_id[e], T.n_tasks);
+    const Task t = load_task(T, tid);
+    const int32_t *field = dist + (size_t)tid * (CONT ? 1 : 4) * t.nn;
+    Agent a = load_agent(st, n_envs, e);
+    double ret_total = 0.0, ret_episode = 0.0;
+    int episode_len = 0, episodes = 0;
+    if (s0 > 0) {
+        ret_total = po.ret_total[e];
+        ret_episode = po.ret_episode[e];
+        episode_len = po.episode_len[e];
+        episodes = po.episodes[e];
+    }
+    for (int s = s0; s < s1; ++s) {
+        const size_t r_at = (size_t)s * n_envs + e;
+        if (CONT) {
+            float turn, walk;
+            me_steer_pick(t, field, a, turn, walk);
+            if (rec.actions) {
+                float *ac = static_cast<float *>(rec.actions) + 2 * r_at;
+                ac[0] = turn;
+                ac[1] = walk;
+            }
+            transition_continuous(t, col_dist, turn, walk, a);
+        } else {
+            const int act = me_expert_pick(t, MG_MAZE_FIELD_TURNS, field, a.gx, a.gy, a.ori_idx);
+            if (rec.actions) static_cast<int32_t *>(rec.actions)[r_at] = act;
+            transition_discrete(t, act, a);
+        }
+        double r;
+        const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
+        if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);
+        if (rec.reward) rec.reward[r_at] = (float)r;
+        if (rec.reward64) rec.reward64[r_at] = r;
+        if (rec.done) rec.done[r_at] = (uint8_t)d;
+        if (d && auto_reset) {
+            if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
+            reset_agent(t, task_type, a);
+        }
+        // the returns: float64 sums in step order; the episode's stops with the first done
+        ret_total = ret_total + r;
+        if (episodes == 0) {
+            ret_episode = ret_episode + r;
+            episode_len += 1;
+        }
+        episodes += d;
+    }
+    store_agent(st, n_envs, e, a);
+    po.ret_total[e] = ret_total;
+    po.ret_episode[e] = ret_episode;
+    po.episode_len[e] = episode_len;
+    po.episodes[e] = episodes;
+}
+
 int check_kind(int32_t kind, const char *who) {
     if (kind != MG_MAZE_FIELD_MOVES_2D && kind != MG_MAZE_FIELD_CELLS_3D && kind != MG_MAZE_FIELD_TURNS)
         return mg::set_error(MG_ERR_BAD_CONFIG, "%s: kind=%d is none of MG_MAZE_FIELD_MOVES_2D / CELLS_3D / TURNS", who, kind);
@@ -345,4 +479,63 @@ extern "C" int mg_maze2d_expert_rollout(const mg_maze_tasks *T, int32_t task_typ
                        0, (hipStream_t)stream, *T, *st, task_type, max_steps, view_grid, auto_reset, n, n_steps, obs_every, dist, po,
                        rec);
     return mg::check_launch("maze2d_expert_rollout_kernel");
+}
+
+extern "C" int mg_maze_steer_action(const mg_maze_tasks *T, const int32_t *dist, int32_t n, const mg_maze_state *st, float *action,
+                                    void *stream) {
+    MG_REQUIRE_PTR(T);
+    MG_REQUIRE_PTR(dist);
+    MG_REQUIRE_PTR(st);
+    MG_REQUIRE_PTR(action);
+    if (n <= 0) return mg::set_error(MG_ERR_BAD_SIZE, "n_envs=%d", n);
+    if (int rc = check_tasks(T, MG_MAZE_ESCAPE)) return rc;
+    if (int rc = check_mstate(st, MG_MAZE_ESCAPE)) return rc;
+    if (st->loc == nullptr || st->ori == nullptr)
+        return mg::set_error(MG_ERR_NULL_POINTER, "mg_maze_steer_action needs mg_maze_state.loc and ori");
+    mg::DeviceGuard guard(mg::device_of(st->grid));
+    hipLaunchKernelGGL(maze_steer_action_kernel, dim3((unsigned)((n + ME_BLOCK - 1) / ME_BLOCK)), dim3(ME_BLOCK), 0,
+                       (hipStream_t)stream, *T, dist, n, *st, action);
+    return mg::check_launch("maze_steer_action_kernel");
+}
+
+extern "C" int mg_maze3d_expert_rollout(const mg_maze_tasks *T, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                                        int32_t continuous, int32_t auto_reset, int32_t n, const mg_maze_state *st,
+                                        int32_t n_steps, int32_t obs_every, const int32_t *dist, void *obs, double *ret_total,
+                                        double *ret_episode, int32_t *episode_len, int32_t *episodes, void *actions,
+                                        float *reward, double *reward64, uint8_t *done, void *stream) {
+    MG_REQUIRE_PTR(dist);
+    MG_REQUIRE_PTR(ret_total);
+    MG_REQUIRE_PTR(ret_episode);
+    MG_REQUIRE_PTR(episode_len);
+    MG_REQUIRE_PTR(episodes);
+    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze3d_expert_rollout: n_steps=%d (at least 1)", n_steps);
+    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze3d_expert_rollout: obs_every=%d (0 = the last step only, k >= 1 = every k-th)", obs_every);
+    // everything mg_maze3d_step refuses (NULL tasks / view / state / obs, n_envs < 1, ...), before the first launch
+    if (int rc = mg_maze3d_step_check(T, view, task_type, max_steps, continuous, auto_reset, n, st, obs, stream)) return rc;
+    const size_t frame = (size_t)n * view->res_h * view->res_v * 3 * (view->obs_format == 1 ? 1 : sizeof(int32_t));
+    unsigned char *slice = static_cast<unsigned char *>(obs);
+    const Me3Out po{ret_total, ret_episode, episode_len, episodes};
+    const Me3Rec rec{actions, reward, reward64, done};
+    const dim3 grid((unsigned)((n + ME_ROLL_BLOCK - 1) / ME_ROLL_BLOCK)), block(ME_ROLL_BLOCK);
+    for (int s0 = 0; s0 < n_steps;) {
+        int s1 = s0;
+        while (!rollout_records(s1, n_steps, obs_every)) ++s1;      // the stretch ends with the next recorded step
+        ++s1;
+        {
+            mg::DeviceGuard guard(mg::device_of(st->grid));
+            if (continuous)
+                hipLaunchKernelGGL(maze3d_expert_advance_kernel<true>, grid, block, 0, (hipStream_t)stream, *T, *st,
+                                   view->collision_dist, task_type, max_steps, auto_reset, n, s0, s1, dist, po, rec);
+            else
+                hipLaunchKernelGGL(maze3d_expert_advance_kernel<false>, grid, block, 0, (hipStream_t)stream, *T, *st,
+                                   view->collision_dist, task_type, max_steps, auto_reset, n, s0, s1, dist, po, rec);
+            if (int rc = mg::check_launch("maze3d_expert_advance_kernel")) return rc;
+        }
+        // the frame of the state the stretch left: mg_maze3d_step's observe-only form, renderer untouched
+        if (int rc = mg_maze3d_step(T, view, task_type, max_steps, continuous, auto_reset, n, st, nullptr, slice, nullptr, nullptr,
+                                    nullptr, stream)) return rc;
+        slice += frame;
+        s0 = s1;
+    }
+    return MG_OK;
 }

@@ -158,3 +158,58 @@ def expert_action_reference(field, task, grid, ori_idx=0):
         if nxt is not None and int(field[nxt]) == d0 - 1:
             return a
     return 0
+
+
+STEER_TAN9 = float(np.float32(0.15838444))                # tan(9 deg) as a float32: half of the 18 deg one step at turn +-1 rotates
+
+
+def steer_action_reference(field, task, grid, loc, ori):
+    """The steering expert of the continuous maze in one state, on the host: the (turn, walk) that takes the agent one cell
+    down a CELLS_3D field, one of (0, 0), (0, 1), (1, 0), (-1, 0). The device code (csrc/maze_expert.hip me_steer_pick)
+    reproduces it bit for bit; every decision is a comparison. `field` is the task's slice [1, n, n], `task` the TaskConfig
+    (or a pair (cell_walls [n, n], cell_size)), `grid` the agent's cell, `loc` its float32 location, `ori` its float64
+    heading.
+      1. off the grid, or d0 = field[cell] <= 0 (a source, unreachable): (0, 0);
+      2. the target cell is the first of DISCRETE_ACTIONS' four neighbours inside the grid with walls == 0 and field == d0 - 1;
+         none: (0, 0);
+      3. the target point is that cell's centre in float32, v = p - loc in float32, widened to float64;
+      4. the heading is (float32(cos(ori)), float32(sin(ori))), cos / sin of the float64 `ori` as the renderer takes them,
+         widened to float64: a last-bit difference between two libms cannot move a comparison;
+      5. c = hx * vy - hy * vx, d = hx * vx + hy * vy in float64 (the products are exact, one rounding each);
+      6. d > 0 and |c| <= STEER_TAN9 * d: walk, (0, 1); else turn towards the target, (c >= 0 ? 1 : -1, 0). The target exactly
+         behind (c == 0, d <= 0) turns +1."""
+    field = np.asarray(field)
+    if field.ndim != 3 or field.shape[0] != 1 or field.shape[1] != field.shape[2]:
+        raise ValueError("field must be one task's [1, n, n] slice of a CELLS_3D field, got %s" % (field.shape,))
+    if hasattr(task, "cell_walls"):
+        walls, cell_size = np.asarray(task.cell_walls), task.cell_size
+    else:
+        walls, cell_size = np.asarray(task[0]), task[1]
+    n = field.shape[-1]
+    if walls.shape != (n, n):
+        raise ValueError("the task's walls are %s, the field is for n = %d" % (walls.shape, n))
+    x, y = int(grid[0]), int(grid[1])
+    if not (0 <= x < n and 0 <= y < n):
+        return (0.0, 0.0)
+    d0 = int(field[0, x, y])
+    if d0 <= 0:
+        return (0.0, 0.0)
+    target = None
+    for dx, dy in DISCRETE_ACTIONS:
+        tx, ty = x + dx, y + dy
+        if 0 <= tx < n and 0 <= ty < n and walls[tx, ty] == 0 and int(field[0, tx, ty]) == d0 - 1:
+            target = (tx, ty)
+            break
+    if target is None:
+        return (0.0, 0.0)
+    f32 = np.float32
+    cs = f32(cell_size)
+    px, py = (f32(target[0]) + f32(0.5)) * cs, (f32(target[1]) + f32(0.5)) * cs
+    vx, vy = np.float64(px - f32(loc[0])), np.float64(py - f32(loc[1]))
+    ori = np.float64(ori)
+    hx, hy = np.float64(f32(np.cos(ori))), np.float64(f32(np.sin(ori)))
+    c = hx * vy - hy * vx
+    d = hx * vx + hy * vy
+    if d > 0 and abs(c) <= np.float64(STEER_TAN9) * d:
+        return (0.0, 1.0)
+    return (1.0 if c >= 0 else -1.0, 0.0)

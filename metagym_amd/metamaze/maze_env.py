@@ -394,7 +394,8 @@ class _MazeBatch(object):
         under the step's own rule is one step nearer in `field` (a `MazeDistanceField` of the class's own kind; None = the
         cached goal field), 0 where there is none (on a source, in an unreachable state). Reads the envs' cells, headings and
         task ids and writes a persistent buffer, overwritten by the next call; nothing synchronises, so
-        `env.step(env.expert_action())` can be captured in a hipGraph. The continuous maze has no expert."""
+        `env.step(env.expert_action())` can be captured in a hipGraph. The continuous maze has no expert of this kind and
+        raises NotImplementedError; its expert steers, see `MetaMazeContinuous3D.steer_action`."""
         if not self._HAS_EXPERT:
             raise NotImplementedError("the continuous maze has no expert (distance_field gives its cell-level field)")
         field = self._expert_field(field, "expert_action")
@@ -659,6 +660,51 @@ class _Maze3D(_MazeBatch):
                                          _lib.current_stream(self.device))
         _lib.check(rc, "mg_maze3d_rollout")
 
+    def demonstrate(self, steps, field=None, record=False, obs_every=0):
+        """`steps` closed-loop env steps with the expert inside the launches (mg_maze3d_expert_rollout): before every step each
+        env takes its expert's action on the state it holds (after an auto-reset: the new episode's start) and steps with
+        it. The discrete env uses `expert_action`'s rule on a TURNS field, the continuous env `steer_action`'s rule on a
+        CELLS_3D field; `field` is a `MazeDistanceField` of that kind (None = the cached goal field, the way out in ESCAPE; in
+        SURVIVAL the expert simply descends the field it is given). Returns a `MazePolicyRollout` as
+        `MetaMaze2D.rollout_expert` does, with `state=None`: ret_total, ret_episode, episode_len, episodes always; actions
+        (int32 [steps, N], continuous: float32 [steps, N, 2]), reward, reward64, done [steps, N] when `record=True`, else None
+        (the launches then write nothing per step). obs and obs_steps as in `rollout`: obs_every == 0 keeps the last frame
+        only, in the persistent buffer `step` returns; k >= 1 returns a fresh [K, N, H, V, 3] tensor in the env's obs_dtype
+        with the frames `rollout_obs_steps` selects. Two launches per recorded frame, as `rollout`: the steps up to it
+        without a picture, then the renderer. Replaying the recorded actions through `rollout` gives the same records,
+        frames and end state bit for bit. Nothing synchronises. A refused call (a field of another n, T, kind or device,
+        steps < 1, obs_every < 0, a call before set_task or reset) raises before anything is written."""
+        from .policy import MazePolicyRollout
+        T, N, dev = int(steps), self.num_envs, self.device
+        if self.need_set_task:
+            raise Exception("Must call \"set_task\" before demonstrate")
+        self._check_step()
+        if T < 1:
+            raise ValueError("steps must be at least 1, got %d" % T)
+        idx = rollout_obs_steps(T, obs_every)
+        field = self._expert_field(field, "demonstrate")
+        if self._tex_version != MAZE_TASK_MANAGER.version:
+            self._build_view()
+        obs = self._obs if int(obs_every) == 0 else torch.empty((len(idx),) + tuple(self._obs.shape), dtype=self._obs.dtype,
+                                                                 device=dev)
+        res = MazePolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
+                                torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+                                None, obs, idx)
+        if record:
+            res.actions = (torch.empty(T, N, 2, dtype=torch.float32, device=dev) if self._CONTINUOUS
+                           else torch.empty(T, N, dtype=torch.int32, device=dev))
+            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+            res.reward64 = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+        rc = self._lib.mg_maze3d_expert_rollout(self._tasks_c, self._view_c, self._tt, self.max_steps, int(self._CONTINUOUS),
+                                                int(self.auto_reset), N, self._state_c, T, int(obs_every), _lib.ptr(field.dist),
+                                                _lib.ptr(obs), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
+                                                _lib.ptr(res.episode_len), _lib.ptr(res.episodes), _lib.ptr(res.actions),
+                                                _lib.ptr(res.reward), _lib.ptr(res.reward64), _lib.ptr(res.done),
+                                                _lib.current_stream(dev))
+        _lib.check(rc, "mg_maze3d_expert_rollout")
+        return res
+
 
 class MetaMazeDiscrete3D(_Maze3D):
     """maze_env.py:16-83. action int in {0..3}: turn left / right, step back / forward."""
@@ -693,6 +739,7 @@ class MetaMazeContinuous3D(_Maze3D):
     _CONTINUOUS = True
     _FIELD_KIND = 1       # expert.CELLS_3D
     _HAS_EXPERT = False
+    _steer_action = None
 
     def _rollout_actions(self, actions):
         a = torch.as_tensor(actions, dtype=torch.float32, device=self.device)
@@ -704,6 +751,21 @@ class MetaMazeContinuous3D(_Maze3D):
     def _observe(self):
         self._launch(None, True)
         return self._obs
+
+    def steer_action(self, field=None):
+        """The steering expert's action for every env, float32 [N, 2] = (turn, walk), one launch (mg_maze_steer_action): towards
+        the centre of the first neighbour cell one step nearer in `field` (a CELLS_3D `MazeDistanceField`; None = the cached
+        goal field) — walk when the heading is within 9 degrees of it, else turn towards it; (0, 0) on a source, in an
+        unreachable cell or off the grid. metamaze/expert.py `steer_action_reference` is the definition, reproduced bit for
+        bit. Reads the envs' cells, locations, headings and task ids and writes a persistent buffer, overwritten by the next
+        call; nothing synchronises, so `env.step(env.steer_action())` can be captured in a hipGraph."""
+        field = self._expert_field(field, "steer_action")
+        if self._steer_action is None:
+            self._steer_action = torch.zeros(self.num_envs, 2, dtype=torch.float32, device=self.device)
+        rc = self._lib.mg_maze_steer_action(self._tasks_c, _lib.ptr(field.dist), self.num_envs, self._state_c,
+                                            _lib.ptr(self._steer_action), _lib.current_stream(self.device))
+        _lib.check(rc, "mg_maze_steer_action")
+        return self._steer_action
 
     def step(self, action):
         self._check_step()
