@@ -1,7 +1,7 @@
 """Bandits (reference metagym/bandits/bandits_env.py) for N envs at once, stepped by `mg_bandits_step` on the GPU."""
 import numpy as np
 
-from .. import _lib
+from .. import _lib, _policy
 from ..spaces import Discrete
 
 # name -> MG_BANDITS_* code
@@ -261,11 +261,11 @@ class Bandits(object):
         step: its memory, stream and returns stay, its records are action -1, reward 0, done 0, invalid 2. Returns a
         `BanditsPolicyRollout`: ret_total, ret_episode, episode_len, episodes, regret and state always; actions, reward,
         done, info_steps, expected_gain, best_gain, invalid [steps, N] when `record=True`, else None (the launch then writes
-        nothing per step). Nothing synchronises when `policy_ids` is None or the array of the previous call, so after
+        nothing per step). Nothing synchronises when `policy_ids` is None, a host array, or the device tensor of the previous
+        call (the same object, unchanged; any other device tensor is read back once to validate it), so after
         `policy.to(device)` the call can be captured in a hipGraph. A refused call (a policy of another K, an id out of range,
         a carry of another N or H, steps < 1) raises and launches nothing."""
-        import torch
-        from .policy import BanditPolicy, BanditPolicyState, BanditsPolicyRollout
+        from .policy import BanditPolicy, BanditPolicyState
         if not isinstance(policy, BanditPolicy):
             raise TypeError("policy must be a BanditPolicy, got %s" % type(policy).__name__)
         T, N, dev, P, H = int(steps), self.num_envs, self.device, policy.num_policies, policy.hidden
@@ -273,29 +273,32 @@ class Bandits(object):
             raise ValueError("steps must be at least 1, got %d" % T)
         if policy.arms != self.K:
             raise ValueError("the policy was built for %d arms, the env has %d" % (policy.arms, self.K))
-        seed = int(seed)
-        if not (0 <= seed < 2 ** 64):
-            raise ValueError("seed must be in [0, 2^64), got %d" % seed)
-        if state is None:
-            state = BanditPolicyState.zeros(N, H, dev)
-        elif not isinstance(state, BanditPolicyState):
-            raise TypeError("state must be a BanditPolicyState, got %s" % type(state).__name__)
-        want = (("h", (N, H), torch.float32), ("prev_action", (N,), torch.int32), ("prev_reward", (N,), torch.float32),
-                ("prev_done", (N,), torch.uint8))
-        for name, shape, dtype in want:
-            v = getattr(state, name)
-            if not isinstance(v, torch.Tensor) or tuple(v.shape) != shape or v.dtype != dtype:
-                raise ValueError("state.%s must be a %s tensor of shape %s (this env has %d envs, the policy %d hidden units)"
-                                 % (name, dtype, shape, N, H))
-        if not (0 <= state.step < 2 ** 64 - T):
-            raise ValueError("state.step = %d is outside [0, 2^64 - steps)" % state.step)
-        ids_d = self._policy_ids(policy_ids, P)
+        state, seed = _policy.check_discrete_carry(state, BanditPolicyState, N, H, T, seed, dev)
+        ids_d = _policy.policy_ids(self, policy_ids, P)
         params, thr = policy.to(dev)
         # everything is checked: from here on the env and the new carry are written
-        carry = BanditPolicyState(*[getattr(state, name).to(dev).clone().contiguous() for name, _, _ in want], step=state.step + T)
+        carry = BanditPolicyState(*[v.to(dev).clone().contiguous() for v in (state.h, state.prev_action, state.prev_reward,
+                                                                             state.prev_done)], step=state.step + T)
         desc = _lib.BanditsPolicyDesc(params.data_ptr(), thr.data_ptr() if thr is not None else None, P, H, policy.arms)
         carry_c = _lib.BanditsPolicyCarry(carry.h.data_ptr(), carry.prev_action.data_ptr(), carry.prev_reward.data_ptr(),
                                           carry.prev_done.data_ptr())
+        res = self._rollout_results(T, record, carry)
+        cfg = self._cfg(*(self.resample_task or (None,)))
+        rc = self._lib.mg_bandits_policy_rollout(cfg, N, self._state, T, desc, _lib.ptr(ids_d), carry_c, seed, state.step,
+                                                 int(bool(episodic)), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
+                                                 _lib.ptr(res.episode_len), _lib.ptr(res.episodes), _lib.ptr(res.regret),
+                                                 _lib.ptr(res.actions), _lib.ptr(res.reward), _lib.ptr(res.done),
+                                                 _lib.ptr(res.info_steps), _lib.ptr(res.expected_gain), _lib.ptr(res.best_gain),
+                                                 _lib.ptr(res.invalid), self._stream())
+        _lib.check(rc, "mg_bandits_policy_rollout")
+        return res
+
+    def _rollout_results(self, T, record, carry):
+        """The `BanditsPolicyRollout` of a T-step launch, its tensors allocated: the five results always, the seven [T, N]
+        records with `record`, else None. `rollout_policy` and `rollout_learner` share it."""
+        import torch
+        from .policy import BanditsPolicyRollout
+        N, dev = self.num_envs, self.device
         f64 = lambda: torch.empty(N, dtype=torch.float64, device=dev)
         i32 = lambda: torch.empty(N, dtype=torch.int32, device=dev)
         res = BanditsPolicyRollout(f64(), f64(), i32(), i32(), f64(), carry)
@@ -307,14 +310,6 @@ class Bandits(object):
             res.expected_gain = torch.empty(T, N, dtype=torch.float64, device=dev)
             res.best_gain = torch.empty(T, N, dtype=torch.float64, device=dev)
             res.invalid = torch.empty(T, N, dtype=torch.uint8, device=dev)
-        cfg = self._cfg(*(self.resample_task or (None,)))
-        rc = self._lib.mg_bandits_policy_rollout(cfg, N, self._state, T, desc, _lib.ptr(ids_d), carry_c, seed, state.step,
-                                                 int(bool(episodic)), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
-                                                 _lib.ptr(res.episode_len), _lib.ptr(res.episodes), _lib.ptr(res.regret),
-                                                 _lib.ptr(res.actions), _lib.ptr(res.reward), _lib.ptr(res.done),
-                                                 _lib.ptr(res.info_steps), _lib.ptr(res.expected_gain), _lib.ptr(res.best_gain),
-                                                 _lib.ptr(res.invalid), self._stream())
-        _lib.check(rc, "mg_bandits_policy_rollout")
         return res
 
     def _learner_call(self, learner, state, learner_ids, seed, T):
@@ -338,7 +333,7 @@ class Bandits(object):
                 raise ValueError("state.%s must be an int32 tensor of shape (%d, %d) on %s" % (name, N, K, dev))
         if not (0 <= state.step < 2 ** 64 - T):
             raise ValueError("state.step = %d is outside [0, 2^64 - steps)" % state.step)
-        ids_d = self._policy_ids(learner_ids, P, "learner_ids")
+        ids_d = _policy.policy_ids(self, learner_ids, P, name="learner_ids")
         params, thr, table = learner.to(dev)
         desc = _lib.BanditsLearnerDesc(KINDS[learner.kind], P, K, params.data_ptr(), thr.data_ptr() if thr is not None else None,
                                        table.data_ptr() if table is not None else None, learner.table_cap, learner.max_attempts)
@@ -354,30 +349,20 @@ class Bandits(object):
         built. `episodic=True` (the default here: a classical learner must not carry counts into a redrawn task) zeroes an
         env's counts at a done with auto_reset; `episodic=False` keeps them. An env that is over when a step begins does
         nothing in that step, as in `rollout_policy`. Returns a `BanditsLearnerRollout` (the fields of
-        `BanditsPolicyRollout`; records [steps, N] only with `record=True`). Nothing synchronises when `learner_ids` is None
-        or the array of the previous call, so after `learner.to(device)` the call can be captured in a hipGraph. The counts
+        `BanditsPolicyRollout`; records [steps, N] only with `record=True`). Nothing synchronises when `learner_ids` is None,
+        a host array, or the device tensor of the previous call (the same object, unchanged; any other device tensor is read
+        back once to validate it), so after `learner.to(device)` the call can be captured in a hipGraph. The counts
         of `state` must satisfy 0 <= wins <= pulls (`state.validate()` checks; the kernel reads nothing out of bounds
         whatever they hold). A refused call raises and launches nothing."""
-        import torch
-        from .learner import BanditLearnerState, BanditsLearnerRollout
-        T, N, dev = int(steps), self.num_envs, self.device
+        from .learner import BanditLearnerState
+        T, N = int(steps), self.num_envs
         if T < 1:
             raise ValueError("steps must be at least 1, got %d" % T)
         state, ids_d, keep, desc = self._learner_call(learner, state, learner_ids, seed, T)
         # everything is checked: from here on the env and the new carry are written
         carry = BanditLearnerState(state.pulls.clone().contiguous(), state.wins.clone().contiguous(), step=state.step + T)
         carry_c = _lib.BanditsLearnerCarry(carry.pulls.data_ptr(), carry.wins.data_ptr())
-        f64 = lambda: torch.empty(N, dtype=torch.float64, device=dev)
-        i32 = lambda: torch.empty(N, dtype=torch.int32, device=dev)
-        res = BanditsLearnerRollout(f64(), f64(), i32(), i32(), f64(), carry)
-        if record:
-            res.actions = torch.empty(T, N, dtype=torch.int32, device=dev)
-            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
-            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
-            res.info_steps = torch.empty(T, N, dtype=torch.int32, device=dev)
-            res.expected_gain = torch.empty(T, N, dtype=torch.float64, device=dev)
-            res.best_gain = torch.empty(T, N, dtype=torch.float64, device=dev)
-            res.invalid = torch.empty(T, N, dtype=torch.uint8, device=dev)
+        res = self._rollout_results(T, record, carry)
         cfg = self._cfg(*(self.resample_task or (None,)))
         rc = self._lib.mg_bandits_learner_rollout(cfg, N, self._state, T, desc, _lib.ptr(ids_d), carry_c, int(seed), state.step,
                                                   int(bool(episodic)), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
@@ -403,27 +388,6 @@ class Bandits(object):
                                                  _lib.ptr(attempts), self._stream())
         _lib.check(rc, "mg_bandits_learner_scores")
         return (scores, attempts) if return_attempts else scores
-
-    def _policy_ids(self, policy_ids, P, name="policy_ids"):
-        """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a hipGraph
-        capture after its warm-up) neither uploads nor reads back."""
-        import torch
-        N = self.num_envs
-        if policy_ids is None:
-            ids_h = np.arange(N, dtype=np.int64) % P
-        else:
-            ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
-            if ids_h.shape != (N,):
-                raise ValueError("%s must have shape (%d,), got %s" % (name, N, tuple(ids_h.shape)))
-            if ids_h.dtype.kind not in "iu":
-                raise ValueError("%s must be integers, got %s" % (name, ids_h.dtype))
-            if int(ids_h.min()) < 0 or int(ids_h.max()) >= P:
-                raise ValueError("%s must be in [0, %d)" % (name, P))
-        key = (P, ids_h.astype(np.int32).tobytes())
-        keep = getattr(self, "_policy_ids_keep", None)
-        if keep is None or keep[0] != key:
-            keep = self._policy_ids_keep = (key, torch.as_tensor(ids_h.astype(np.int32), device=self.device).contiguous())
-        return keep[1]
 
     def expected_upperbound(self):
         """max_steps * max(gains), float64 [N]."""

@@ -19,7 +19,7 @@ kind computes K scores and plays the lowest index among the maxima (best = score
                Y = gamma(beta; which = 1), score = X / (X + Y)
 
 Exploration (`epsilon`, all kinds but Thompson) is `BanditPolicy`'s rule as it stands: the threshold, the tag 0x4241 and
-out[1] % K are imported from bandits/policy.py, not restated.
+out[1] % K are those of bandits/policy.py (the threshold rule itself lives in _policy.py), not restated.
 
 log32(x), for positive normal x, is fdlibm's single-precision log, one operation at a time. With i the bits of x:
 
@@ -45,7 +45,7 @@ Nothing here needs a GPU to import.
 """
 import numpy as np
 
-from ..metamaze.policy import _f32, _np, eps_threshold, philox4x32_10
+from .._policy import PackedPolicySet, check_epsilon, f32_array, philox4x32_10, to_numpy
 from .policy import MAX_ARMS, PHILOX_TAG, BanditsPolicyRollout
 
 F = np.float32
@@ -173,17 +173,17 @@ class BanditLearnerState(object):
 
     def numpy(self):
         """The same carry on the host, as numpy arrays."""
-        return BanditLearnerState(_np(self.pulls).astype(np.int32), _np(self.wins).astype(np.int32), self.step)
+        return BanditLearnerState(to_numpy(self.pulls).astype(np.int32), to_numpy(self.wins).astype(np.int32), self.step)
 
     def validate(self):
         """Raises unless 0 <= wins <= pulls everywhere (reads the arrays back: not for a captured region)."""
-        p, w = _np(self.pulls), _np(self.wins)
+        p, w = to_numpy(self.pulls), to_numpy(self.wins)
         if p.shape != w.shape or p.ndim != 2 or not ((w >= 0) & (w <= p)).all():
             raise ValueError("a BanditLearnerState needs pulls and wins of one shape [N, K] with 0 <= wins <= pulls")
         return self
 
 
-class BanditLearner(object):
+class BanditLearner(PackedPolicySet):
     """P parameter rows of one kind of classical learner for K arms; build one with `greedy`, `ucb`, `table` or `thompson`."""
 
     def __init__(self, kind, arms, params, epsilon=None, table=None, table_cap=0, max_attempts=MAX_ATTEMPTS):
@@ -198,18 +198,10 @@ class BanditLearner(object):
         if epsilon is not None:
             if kind == "thompson":
                 raise ValueError("Thompson sampling takes no epsilon")
-            eps = _np(epsilon)
-            if eps.dtype != np.float64:
-                raise TypeError("epsilon must be float64, got %s" % eps.dtype)
-            if eps.shape != (P,):
-                raise ValueError("epsilon must have shape (%d,), got %s" % (P, eps.shape))
-            if not ((eps >= 0.0) & (eps <= 1.0)).all():
-                raise ValueError("epsilon must be in [0, 1]")
-            epsilon = np.ascontiguousarray(eps)
+            epsilon = check_epsilon(epsilon, P)
         self.kind, self.arms, self.num_learners = kind, K, P
         self.params, self.epsilon, self.index, self.table_cap = params, epsilon, table, int(table_cap)
         self.max_attempts = int(max_attempts)
-        self._device = {}
 
     # ------------------------------------------------------------------ the four kinds
     @staticmethod
@@ -222,7 +214,7 @@ class BanditLearner(object):
     @classmethod
     def greedy(cls, arms, prior, epsilon=None):
         """score = posterior mean under the prior Beta(a0, b0): prior float32 [P, 2], both > 0."""
-        prior = _f32("prior", prior, 2)
+        prior = f32_array("prior", prior, 2)
         if prior.shape[1] != 2 or not (prior > 0).all():
             raise ValueError("prior must be [P, 2] with a0, b0 > 0")
         return cls("greedy", arms, cls._rows([prior[:, 0], prior[:, 1]], [0, 1]), epsilon)
@@ -230,7 +222,7 @@ class BanditLearner(object):
     @classmethod
     def ucb(cls, arms, c, epsilon=None):
         """score = mean + sqrt(c log(t) / n), every arm once first: c float32 [P], >= 0 (UCB1 is c = 2)."""
-        c = _f32("c", c, 1)
+        c = f32_array("c", c, 1)
         if not (c >= 0).all():
             raise ValueError("c must be >= 0")
         return cls("ucb", arms, cls._rows([c], [2]), epsilon)
@@ -239,7 +231,7 @@ class BanditLearner(object):
     def table(cls, arms, index, epsilon=None):
         """score = index[cell of (n, w)]: index float32 [P, (C + 1)(C + 2) / 2] with 1 <= C <= 1023 (C is found from the
         row length)."""
-        index = _f32("index", index, 2)
+        index = f32_array("index", index, 2)
         cells = index.shape[1]
         cap = int((np.sqrt(8.0 * cells + 1.0) - 3.0) / 2.0 + 0.5)
         if cap < 1 or cap > MAX_CAP or table_cells(cap) != cells:
@@ -249,7 +241,7 @@ class BanditLearner(object):
     @classmethod
     def thompson(cls, arms, prior, max_attempts=MAX_ATTEMPTS):
         """score = a draw from the posterior Beta(a0 + w, b0 + n - w): prior float32 [P, 2], both >= 1."""
-        prior = _f32("prior", prior, 2)
+        prior = f32_array("prior", prior, 2)
         if prior.shape[1] != 2 or not (prior >= 1).all():
             raise ValueError("prior must be [P, 2] with a0, b0 >= 1")
         if int(max_attempts) != max_attempts or not (1 <= int(max_attempts) <= MAX_ATTEMPTS):
@@ -259,26 +251,10 @@ class BanditLearner(object):
     def __len__(self):
         return self.num_learners
 
-    @property
-    def thresholds(self):
-        """uint32 [P]: thr[p] = min(floor(epsilon[p] * 2^32), 2^32 - 1); zeros without epsilon."""
-        if self.epsilon is None:
-            return np.zeros(self.num_learners, np.uint32)
-        return eps_threshold(self.epsilon)
-
-    def to(self, device):
-        """(params [P, 4], thresholds or None, table or None) as torch tensors on `device` (uploaded once per device). The
-        thresholds travel as the int32 tensor with the uint32's bits."""
-        import torch
-        from .. import _lib
-        dev = _lib.canonical_device(device)
-        key = str(dev)
-        if key not in self._device:
-            params = torch.from_numpy(self.params).to(dev).contiguous()
-            thr = None if self.epsilon is None else torch.from_numpy(self.thresholds.view(np.int32).copy()).to(dev).contiguous()
-            table = None if self.index is None else torch.from_numpy(self.index).to(dev).contiguous()
-            self._device[key] = (params, thr, table)
-        return self._device[key]
+    def _host(self):
+        """`to(device)` gives (params [P, 4], thresholds or None, table or None); the thresholds travel as the int32 tensor
+        with the uint32's bits."""
+        return self.params, self._threshold_bits(), self.index
 
     # ------------------------------------------------------------------ the definition in numpy
     def reference(self, learner_ids, state, seed=0, env_ids=None, return_scores=False, return_attempts=False):
@@ -287,18 +263,18 @@ class BanditLearner(object):
         the actions int32 [N]; with `return_scores` also the scores float32 [N, K]; with `return_attempts` also int32
         [N, K, 2], the attempts of gamma(.; which) (zeros unless Thompson). The caller applies the count update."""
         P, K = self.num_learners, self.arms
-        ids = _np(learner_ids)
+        ids = to_numpy(learner_ids)
         if ids.ndim != 1 or ids.dtype.kind not in "iu":
             raise ValueError("learner_ids must be a vector of integers")
         N = ids.shape[0]
         if N and (int(ids.min()) < 0 or int(ids.max()) >= P):
             raise ValueError("learner_ids must be in [0, %d)" % P)
-        pulls, wins = _np(state.pulls), _np(state.wins)
+        pulls, wins = to_numpy(state.pulls), to_numpy(state.wins)
         if pulls.shape != (N, K) or wins.shape != (N, K) or pulls.dtype != np.int32 or wins.dtype != np.int32:
             raise ValueError("state.pulls and state.wins must be int32 [%d, %d]" % (N, K))
         if not ((wins >= 0) & (wins <= pulls)).all():
             raise ValueError("the counts must satisfy 0 <= wins <= pulls")
-        e = np.arange(N, dtype=np.uint64) if env_ids is None else _np(env_ids).astype(np.uint64)
+        e = np.arange(N, dtype=np.uint64) if env_ids is None else to_numpy(env_ids).astype(np.uint64)
         n, s = int(state.step), int(seed)
         a0, b0, c = (self.params[ids, j][:, None] for j in range(3))
         nf, wf = pulls.astype(F), wins.astype(F)

@@ -23,7 +23,7 @@ out = philox4x32_10(c0 = e, c1 = n & 0xFFFFFFFF, c2 = n >> 32, c3 = 0x4241, k0 =
 action = (out[0] < thr) ? (out[1] % K) : greedy, with an unsigned modulo.
 
 `BanditPolicy.reference` evaluates exactly this in numpy float32 and numpy integers. Nothing here needs a GPU to import. The
-carry, the Philox function and the threshold rule are the maze policies' (metamaze/policy.py), imported, not restated.
+carry is the maze policies' (metamaze/policy.py); the Philox function and the threshold rule are shared (_policy.py).
 
     pol = BanditPolicy(wa, wr, wd, wh, b, wo, bo)           # wa [P, H, K], wr wd b [P, H], wh [P, H, H], wo [P, K, H], bo [P, K]
     res = env.rollout_policy(pol, steps=256)                # env e plays policy e % P; res.regret is the per-env regret
@@ -31,17 +31,14 @@ carry, the Philox function and the threshold rule are the maze policies' (metama
 """
 import numpy as np
 
-from ..metamaze.policy import MazePolicyState, _f32, _np, eps_threshold, philox4x32_10
+from .._policy import PackedPolicySet, check_epsilon, f32_array, pad4, philox4x32_10, to_numpy
+from ..metamaze.policy import MazePolicyState
 
 MAX_HIDDEN = 64
 MAX_ARMS = 64
 PHILOX_TAG = 0x4241          # c3 of the exploration draw
 
 BanditPolicyState = MazePolicyState   # h [N, H], prev_action [N] (-1 = none), prev_reward [N], prev_done [N], step
-
-
-def _pad4(n):
-    return (n + 3) & ~3
 
 
 def param_count(hidden, arms):
@@ -51,16 +48,16 @@ def param_count(hidden, arms):
     if not (2 <= int(arms) <= MAX_ARMS):
         raise ValueError("arms must be in [2, %d], got %r" % (MAX_ARMS, arms))
     H, K = int(hidden), int(arms)
-    return H * (4 + _pad4(K) + _pad4(H)) + K * (4 + _pad4(H))
+    return H * (4 + pad4(K) + pad4(H)) + K * (4 + pad4(H))
 
 
-class BanditPolicy(object):
+class BanditPolicy(PackedPolicySet):
     """P recurrent policies: wa [P, H, K], wr [P, H], wd [P, H], wh [P, H, H], b [P, H], wo [P, K, H], bo [P, K], all float32
     and finite; epsilon float64 [P] in [0, 1] or None (no exploration). 1 <= H <= 64, 2 <= K <= 64."""
 
     def __init__(self, wa, wr, wd, wh, b, wo, bo, epsilon=None):
-        wa, wr, wd, wh = _f32("wa", wa, 3), _f32("wr", wr, 2), _f32("wd", wd, 2), _f32("wh", wh, 3)
-        b, wo, bo = _f32("b", b, 2), _f32("wo", wo, 3), _f32("bo", bo, 2)
+        wa, wr, wd, wh = f32_array("wa", wa, 3), f32_array("wr", wr, 2), f32_array("wd", wd, 2), f32_array("wh", wh, 3)
+        b, wo, bo = f32_array("b", b, 2), f32_array("wo", wo, 3), f32_array("bo", bo, 2)
         P, H, K = wa.shape
         if P < 1:
             raise ValueError("a policy set needs at least one policy")
@@ -72,32 +69,13 @@ class BanditPolicy(object):
                 or bo.shape != (P, K):
             raise ValueError("shapes must be wa [P,H,K], wr [P,H], wd [P,H], wh [P,H,H], b [P,H], wo [P,K,H], bo [P,K]; "
                              "got %s %s %s %s %s %s %s" % (wa.shape, wr.shape, wd.shape, wh.shape, b.shape, wo.shape, bo.shape))
-        if epsilon is not None:
-            eps = _np(epsilon)
-            if eps.dtype != np.float64:
-                raise TypeError("epsilon must be float64, got %s" % eps.dtype)
-            if eps.shape != (P,):
-                raise ValueError("epsilon must have shape (%d,), got %s" % (P, eps.shape))
-            if not ((eps >= 0.0) & (eps <= 1.0)).all():
-                raise ValueError("epsilon must be in [0, 1]")
-            epsilon = np.ascontiguousarray(eps)
-        self.wa, self.wr, self.wd, self.wh, self.b, self.wo, self.bo, self.epsilon = wa, wr, wd, wh, b, wo, bo, epsilon
+        self.wa, self.wr, self.wd, self.wh, self.b, self.wo, self.bo = wa, wr, wd, wh, b, wo, bo
+        self.epsilon = None if epsilon is None else check_epsilon(epsilon, P)
         self.num_policies, self.hidden, self.arms = P, H, K
-        self._device = {}
-
-    def __len__(self):
-        return self.num_policies
 
     @property
     def param_count(self):
         return param_count(self.hidden, self.arms)
-
-    @property
-    def thresholds(self):
-        """uint32 [P]: thr[p] = min(floor(epsilon[p] * 2^32), 2^32 - 1); zeros without epsilon."""
-        if self.epsilon is None:
-            return np.zeros(self.num_policies, np.uint32)
-        return eps_threshold(self.epsilon)
 
     def pack(self):
         """float32 [P, param_count]: the layout the kernel reads (documented in include/metagym_hip.h). With HP and KP = H
@@ -106,7 +84,7 @@ class BanditPolicy(object):
         0, 0, 0, wo[k][0..H-1], zeros up to HP). Every record is a multiple of four floats, so every 16-byte read is
         aligned."""
         P, H, K = self.num_policies, self.hidden, self.arms
-        kp, hp = _pad4(K), _pad4(H)
+        kp, hp = pad4(K), pad4(H)
         ru, ra = 4 + kp + hp, 4 + hp
         out = np.zeros((P, self.param_count), np.float32)
         unit = out[:, :H * ru].reshape(P, H, ru)
@@ -121,29 +99,21 @@ class BanditPolicy(object):
     @classmethod
     def unpack(cls, packed, hidden, arms, epsilon=None):
         """The inverse of `pack`."""
-        packed = _f32("packed", packed, 2)
+        packed = f32_array("packed", packed, 2)
         P, H, K = packed.shape[0], int(hidden), int(arms)
         if packed.shape[1] != param_count(H, K):
             raise ValueError("packed has shape %s, hidden=%d and arms=%d need [P, %d]" % (packed.shape, H, K, param_count(H, K)))
-        kp, hp = _pad4(K), _pad4(H)
+        kp, hp = pad4(K), pad4(H)
         ru, ra = 4 + kp + hp, 4 + hp
         unit = packed[:, :H * ru].reshape(P, H, ru)
         arm = packed[:, H * ru:].reshape(P, K, ra)
         return cls(unit[:, :, 4:4 + K].copy(), unit[:, :, 1].copy(), unit[:, :, 2].copy(), unit[:, :, 4 + kp:4 + kp + H].copy(),
                    unit[:, :, 0].copy(), arm[:, :, 4:4 + H].copy(), arm[:, :, 0].copy(), epsilon)
 
-    def to(self, device):
-        """(packed parameters, thresholds or None) as torch tensors on `device` (uploaded once per device). The thresholds
-        travel as the int32 tensor with the uint32's bits."""
-        import torch
-        from .. import _lib
-        dev = _lib.canonical_device(device)
-        key = str(dev)
-        if key not in self._device:
-            params = torch.from_numpy(self.pack()).to(dev).contiguous()
-            thr = None if self.epsilon is None else torch.from_numpy(self.thresholds.view(np.int32).copy()).to(dev).contiguous()
-            self._device[key] = (params, thr)
-        return self._device[key]
+    def _host(self):
+        """`to(device)` gives (packed parameters, thresholds or None); the thresholds travel as the int32 tensor with the
+        uint32's bits."""
+        return self.pack(), self._threshold_bits()
 
     def reference(self, policy_ids, state, seed=0, env_ids=None, return_explored=False):
         """One step of the definition above in numpy float32 (and numpy integers for the exploration), with exactly that
@@ -153,14 +123,14 @@ class BanditPolicy(object):
         (actions int32 [N], next h float32 [N, H]), and with `return_explored` also the bool [N] mask of the envs whose
         action was the exploratory draw. The oracle of the policy half of a closed-loop rollout."""
         P, H, K = self.num_policies, self.hidden, self.arms
-        ids = _np(policy_ids)
+        ids = to_numpy(policy_ids)
         if ids.ndim != 1 or ids.dtype.kind not in "iu":
             raise ValueError("policy_ids must be a vector of integers")
         N = ids.shape[0]
         if N and (int(ids.min()) < 0 or int(ids.max()) >= P):
             raise ValueError("policy_ids must be in [0, %d)" % P)
-        h = _np(state.h)
-        pa, pr, pd = _np(state.prev_action), _np(state.prev_reward), _np(state.prev_done)
+        h = to_numpy(state.h)
+        pa, pr, pd = to_numpy(state.prev_action), to_numpy(state.prev_reward), to_numpy(state.prev_done)
         if h.shape != (N, H) or h.dtype != np.float32:
             raise ValueError("state.h must be float32 [%d, %d], got %s %s" % (N, H, h.dtype, h.shape))
         if pa.shape != (N,) or pr.shape != (N,) or pd.shape != (N,) or pr.dtype != np.float32:
@@ -191,7 +161,7 @@ class BanditPolicy(object):
                 best = np.where(better, logits[:, k], best)
         assert hn.dtype == np.float32 and logits.dtype == np.float32
         thr = self.thresholds[ids]
-        e = np.arange(N, dtype=np.uint64) if env_ids is None else _np(env_ids).astype(np.uint64)
+        e = np.arange(N, dtype=np.uint64) if env_ids is None else to_numpy(env_ids).astype(np.uint64)
         n, s = int(state.step), int(seed)
         out = philox4x32_10(e, n & 0xFFFFFFFF, (n >> 32) & 0xFFFFFFFF, PHILOX_TAG, s & 0xFFFFFFFF, (s >> 32) & 0xFFFFFFFF)
         explored = out[0] < thr

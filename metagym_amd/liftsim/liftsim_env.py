@@ -9,7 +9,7 @@ import random
 
 import numpy as np
 
-from .. import _lib
+from .. import _lib, _policy
 
 CUSTOM, UNIFORM = 0, 1
 QN = 16           # MG_LIFTSIM_QN
@@ -391,7 +391,7 @@ class LiftSim(object):
         unknown = set(record) - set(self.RECORDS)
         if unknown:
             raise ValueError("unknown records: %s (known: %s)" % (sorted(unknown), list(self.RECORDS)))
-        ids = self._policy_ids(policy_ids, policy.num_policies)
+        ids = _policy.policy_ids(self, policy_ids, policy.num_policies, default="zero")
         params = policy.to(self.device)
         desc = _lib.LiftsimPolicyDesc(params.data_ptr(), policy.num_policies, policy.hidden, policy.floors, policy.elevators,
                                       (C.c_float * 8)(*[float(v) for v in policy.scale]))
@@ -408,33 +408,6 @@ class LiftSim(object):
             _lib.ptr(out.get("given_up_persons")), _lib.ptr(out.get("actions")), self._stream()),
             "mg_liftsim_policy_rollout")
         return out
-
-    def _policy_ids(self, policy_ids, P):
-        """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a
-        hipGraph capture after its warm-up) neither uploads nor reads back."""
-        import torch
-        N = self.num_envs
-        keep = getattr(self, "_policy_ids_keep", None)     # (P, device ids, source tensor, its version, the ids' bytes)
-        if isinstance(policy_ids, torch.Tensor) and keep is not None and keep[0] == P and policy_ids is keep[2] and \
-                policy_ids._version == keep[3]:
-            return keep[1]
-        if policy_ids is None:
-            ids_h = np.zeros(N, dtype=np.int64)
-        else:
-            ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
-            if ids_h.shape != (N,):
-                raise ValueError("policy_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
-            if ids_h.dtype.kind not in "iu":
-                raise ValueError("policy_ids must be integers, got %s" % ids_h.dtype)
-            if int(ids_h.min()) < 0 or int(ids_h.max()) >= P:
-                raise ValueError("policy_ids must be in [0, %d)" % P)
-        ids_h = ids_h.astype(np.int32)
-        if keep is not None and keep[0] == P and keep[4] == ids_h.tobytes():
-            return keep[1]
-        ids_d = torch.as_tensor(ids_h, device=self.device).contiguous()
-        src = policy_ids if isinstance(policy_ids, torch.Tensor) else None
-        self._policy_ids_keep = (P, ids_d, src, src._version if src is not None else None, ids_h.tobytes())
-        return ids_d
 
     def statistics_tensors(self):
         """env.statistics of every env as [N] tensors (one launch, no host synchronisation)."""

@@ -31,30 +31,13 @@ whatever the weights hold). Ties and NaN logits resolve to the lowest index. Cho
 """
 import numpy as np
 
+from .._policy import PackedPolicySet, f32_array, pad4, to_numpy
+
 MAX_HIDDEN = 64
 MAX_FLOORS, MAX_ELEVATORS = 128, 32
 N_SCALARS = 8
 MAXIMUM_LOAD = 1600
 RAW = ("Floor", "Velocity", "Direction", "DoorState", "LoadWeight", "OverloadedAlarm", "DoorIsOpening", "DoorIsClosing")
-
-
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-def _f32(name, x, ndim):
-    a = _np(x)
-    if a.dtype != np.float32:
-        raise TypeError("%s must be float32, got %s" % (name, a.dtype))
-    if a.ndim != ndim:
-        raise ValueError("%s must have %d dimensions, got shape %s" % (name, ndim, a.shape))
-    if not np.isfinite(a).all():
-        raise ValueError("%s holds a value that is not finite" % name)
-    return np.ascontiguousarray(a)
-
-
-def _pad4(n):
-    return (n + 3) & ~3
 
 
 def _check_sizes(hidden, floors, elevators):
@@ -73,14 +56,14 @@ def unit_groups(floors, elevators):
     groups, o = [], 0
     for name, n in (("b", 1), ("ws", N_SCALARS), ("we", E), ("wt", F + 1), ("wr", F), ("wu", F), ("wd", F)):
         groups.append((name, o, n))
-        o += _pad4(n)
+        o += pad4(n)
     return groups, o
 
 
 def param_count(hidden, floors, elevators):
     """Floats per packed policy (what mg_liftsim_policy_param_count returns)."""
     H, F, E = _check_sizes(hidden, floors, elevators)
-    return H * unit_groups(F, E)[1] + (2 * F + 2) * (4 + _pad4(H))
+    return H * unit_groups(F, E)[1] + (2 * F + 2) * (4 + pad4(H))
 
 
 def default_scale(floors):
@@ -89,14 +72,14 @@ def default_scale(floors):
     return np.array([one / np.float32(int(floors)), 0.5, 1.0, 1.0, one / np.float32(MAXIMUM_LOAD), 1.0, 1.0, 1.0], np.float32)
 
 
-class LiftPolicy(object):
+class LiftPolicy(PackedPolicySet):
     """P dispatcher networks: ws [P, H, 8], we [P, H, E], wt [P, H, F+1], wr wu wd [P, H, F], b [P, H], wo [P, A, H], bo [P, A]
     with A = 2F + 2, all float32 and finite; scale float32 [8], the same for all policies (None: `default_scale(F)`)."""
 
     def __init__(self, ws, we, wt, wr, wu, wd, b, wo, bo, scale=None):
-        ws, we, wt = _f32("ws", ws, 3), _f32("we", we, 3), _f32("wt", wt, 3)
-        wr, wu, wd = _f32("wr", wr, 3), _f32("wu", wu, 3), _f32("wd", wd, 3)
-        b, wo, bo = _f32("b", b, 2), _f32("wo", wo, 3), _f32("bo", bo, 2)
+        ws, we, wt = f32_array("ws", ws, 3), f32_array("we", we, 3), f32_array("wt", wt, 3)
+        wr, wu, wd = f32_array("wr", wr, 3), f32_array("wu", wu, 3), f32_array("wd", wd, 3)
+        b, wo, bo = f32_array("b", b, 2), f32_array("wo", wo, 3), f32_array("bo", bo, 2)
         P, H, E = we.shape
         F = wr.shape[2]
         if P < 1:
@@ -110,17 +93,13 @@ class LiftPolicy(object):
             if got[name].shape != shape:
                 raise ValueError("shapes must be ws [P,H,8], we [P,H,E], wt [P,H,F+1], wr wu wd [P,H,F], b [P,H], wo [P,A,H], "
                                  "bo [P,A] with A = 2F + 2; %s is %s, not %s" % (name, got[name].shape, shape))
-        scale = default_scale(F) if scale is None else _f32("scale", scale, 1)
+        scale = default_scale(F) if scale is None else f32_array("scale", scale, 1)
         if scale.shape != (N_SCALARS,):
             raise ValueError("scale must have shape (8,), got %s" % (scale.shape,))
         self.ws, self.we, self.wt, self.wr, self.wu, self.wd, self.b, self.wo, self.bo = ws, we, wt, wr, wu, wd, b, wo, bo
         self.scale = scale
         self.num_policies, self.hidden, self.floors, self.elevators, self.choices = P, H, F, E, A
-        self._device = {}
         self._gathered = None
-
-    def __len__(self):
-        return self.num_policies
 
     @property
     def param_count(self):
@@ -133,7 +112,7 @@ class LiftPolicy(object):
         HP). Every record and every group starts on a multiple of four floats."""
         P, H, F, E, A = self.num_policies, self.hidden, self.floors, self.elevators, self.choices
         groups, ru = unit_groups(F, E)
-        rc = 4 + _pad4(H)
+        rc = 4 + pad4(H)
         out = np.zeros((P, self.param_count), np.float32)
         unit = out[:, :H * ru].reshape(P, H, ru)
         for name, o, n in groups:
@@ -146,29 +125,19 @@ class LiftPolicy(object):
     @classmethod
     def unpack(cls, packed, hidden, floors, elevators, scale=None):
         """The inverse of `pack`."""
-        packed = _f32("packed", packed, 2)
+        packed = f32_array("packed", packed, 2)
         H, F, E = _check_sizes(hidden, floors, elevators)
         P, A = packed.shape[0], 2 * F + 2
         if packed.shape[1] != param_count(H, F, E):
             raise ValueError("packed has shape %s, hidden=%d floors=%d elevators=%d need [P, %d]"
                              % (packed.shape, H, F, E, param_count(H, F, E)))
         groups, ru = unit_groups(F, E)
-        rc = 4 + _pad4(H)
+        rc = 4 + pad4(H)
         unit = packed[:, :H * ru].reshape(P, H, ru)
         choice = packed[:, H * ru:].reshape(P, A, rc)
         g = {name: unit[:, :, o:o + n].copy() for name, o, n in groups}
         return cls(g["ws"], g["we"], g["wt"], g["wr"], g["wu"], g["wd"], g["b"][:, :, 0].copy(), choice[:, :, 4:4 + H].copy(),
                    choice[:, :, 0].copy(), scale)
-
-    def to(self, device):
-        """The packed parameters as a torch tensor on `device` (uploaded once per device)."""
-        import torch
-        from .. import _lib
-        dev = _lib.canonical_device(device)
-        key = str(dev)
-        if key not in self._device:
-            self._device[key] = torch.from_numpy(self.pack()).to(dev).contiguous()
-        return self._device[key]
 
     @staticmethod
     def actions_of(choices, floors):
@@ -195,16 +164,17 @@ class LiftPolicy(object):
         """(x float32 [n, E, 8], d int [n, E], reserved bool [n, E, F], up bool [n, F], down bool [n, F]) of the arrays of
         `env.observation()` (torch or numpy)."""
         F, E = self.floors, self.elevators
-        raw = [_np(obs[name]) for name in RAW]
+        raw = [to_numpy(obs[name]) for name in RAW]
         n = raw[0].shape[0]
         for name, a in zip(RAW, raw):
             if a.shape != (n, E):
                 raise ValueError("obs[%r] must have shape (%d, %d), got %s" % (name, n, E, a.shape))
         x = np.stack([(a != 0).astype(np.float32) if a.dtype == np.bool_ else a.astype(np.float32) for a in raw], axis=-1)
         x = x * self.scale
-        d = _np(obs["CurrentDispatchTarget"]).astype(np.int64)
-        targets, count = _np(obs["ReservedTargetFloors"]).astype(np.int64), _np(obs["ReservedTargetCount"]).astype(np.int64)
-        up, down = _np(obs["RequiringUpwardFloors"]) != 0, _np(obs["RequiringDownwardFloors"]) != 0
+        d = to_numpy(obs["CurrentDispatchTarget"]).astype(np.int64)
+        targets = to_numpy(obs["ReservedTargetFloors"]).astype(np.int64)
+        count = to_numpy(obs["ReservedTargetCount"]).astype(np.int64)
+        up, down = to_numpy(obs["RequiringUpwardFloors"]) != 0, to_numpy(obs["RequiringDownwardFloors"]) != 0
         if d.shape != (n, E) or targets.shape != (n, E, F) or count.shape != (n, E) or up.shape != (n, F) or down.shape != (n, F):
             raise ValueError("the observation does not belong to %d buildings of %d floors and %d elevators" % (n, F, E))
         listed = np.arange(F)[None, None, :] < count[:, :, None]
@@ -245,7 +215,7 @@ class LiftPolicy(object):
         obs: the arrays of `env.observation()` for n buildings (torch or numpy; [n, E], [n, E, F] with
         ReservedTargetCount, [n, F]). Returns the int32 [n, 2E] actions, ready for `env.step`, and with `return_choices`
         also the int32 [n, E] choices. The oracle of the policy half of a closed-loop rollout."""
-        ids = _np(policy_ids)
+        ids = to_numpy(policy_ids)
         if ids.ndim != 1 or ids.dtype.kind not in "iu":
             raise ValueError("policy_ids must be a vector of integers")
         n = ids.shape[0]

@@ -38,6 +38,8 @@ step's reward and action (the RL^2 trial); `episodic=True` zeroes the env's carr
 """
 import numpy as np
 
+from .._policy import ContinuousPolicyState, PackedPolicySet, f32_array, to_numpy
+
 MAX_HIDDEN = 256
 
 
@@ -46,25 +48,12 @@ def param_count(hidden, obs_dim, n_act):
     return hidden + obs_dim * hidden + n_act + hidden * n_act if hidden > 0 else n_act + obs_dim * n_act
 
 
-def _f32(name, x, ndim):
-    if hasattr(x, "detach"):                               # a torch tensor
-        x = x.detach().cpu().numpy()
-    a = np.asarray(x)
-    if a.dtype != np.float32:
-        raise TypeError("%s must be float32, got %s" % (name, a.dtype))
-    if a.ndim != ndim:
-        raise ValueError("%s must have %d dimensions, got shape %s" % (name, ndim, a.shape))
-    if not np.isfinite(a).all():
-        raise ValueError("%s holds a value that is not finite" % name)
-    return np.ascontiguousarray(a)
-
-
-class WalkerPolicy(object):
+class WalkerPolicy(PackedPolicySet):
     """P policies with one hidden ReLU layer: w1 [P, H, D], b1 [P, H], w2 [P, A, H], b2 [P, A], all float32 and finite,
     1 <= H <= 256. `WalkerPolicy.linear(w, b)` builds the H = 0 form."""
 
     def __init__(self, w1, b1, w2, b2):
-        w1, b1, w2, b2 = _f32("w1", w1, 3), _f32("b1", b1, 2), _f32("w2", w2, 3), _f32("b2", b2, 2)
+        w1, b1, w2, b2 = f32_array("w1", w1, 3), f32_array("b1", b1, 2), f32_array("w2", w2, 3), f32_array("b2", b2, 2)
         P, H, D = w1.shape
         A = w2.shape[1]
         if P < 1 or D < 1 or A < 1:
@@ -76,12 +65,11 @@ class WalkerPolicy(object):
                              % (w1.shape, b1.shape, w2.shape, b2.shape))
         self.w1, self.b1, self.w2, self.b2 = w1, b1, w2, b2
         self.num_policies, self.hidden, self.obs_dim, self.n_act = P, H, D, A
-        self._device = {}
 
     @classmethod
     def linear(cls, w, b):
         """a = b + w @ x in the order of the definition: w [P, A, D], b [P, A]."""
-        w, b = _f32("w", w, 3), _f32("b", b, 2)
+        w, b = f32_array("w", w, 3), f32_array("b", b, 2)
         P, A, D = w.shape
         if P < 1 or D < 1 or A < 1:
             raise ValueError("a policy set needs at least one policy, one input and one output; got w %s" % (w.shape,))
@@ -91,11 +79,7 @@ class WalkerPolicy(object):
         self.w1 = self.b1 = None
         self.w2, self.b2 = w, b                            # the output layer, read straight from x
         self.num_policies, self.hidden, self.obs_dim, self.n_act = P, 0, D, A
-        self._device = {}
         return self
-
-    def __len__(self):
-        return self.num_policies
 
     @property
     def param_count(self):
@@ -116,7 +100,7 @@ class WalkerPolicy(object):
     @classmethod
     def unpack(cls, packed, hidden, obs_dim, n_act):
         """The inverse of `pack`."""
-        packed = _f32("packed", packed, 2)
+        packed = f32_array("packed", packed, 2)
         P, H, D, A = packed.shape[0], int(hidden), int(obs_dim), int(n_act)
         if not (0 <= H <= MAX_HIDDEN) or D < 1 or A < 1 or packed.shape[1] != param_count(H, D, A):
             raise ValueError("packed has shape %s, hidden=%d, obs_dim=%d and n_act=%d need [P, %d]"
@@ -127,20 +111,11 @@ class WalkerPolicy(object):
         return cls(packed[:, H:at].reshape(P, D, H).transpose(0, 2, 1).copy(), packed[:, :H].copy(),
                    packed[:, at + A:].reshape(P, H, A).transpose(0, 2, 1).copy(), packed[:, at:at + A].copy())
 
-    def to(self, device):
-        """The packed parameters as a torch tensor on `device` (uploaded once per device)."""
-        import torch
-        from .. import _lib
-        key = str(_lib.canonical_device(device))
-        if key not in self._device:
-            self._device[key] = torch.from_numpy(self.pack()).to(_lib.canonical_device(device)).contiguous()
-        return self._device[key]
-
     def reference(self, obs, policy_ids):
         """The definition above in numpy float32, with exactly that association: obs [N, D] float32, policy_ids [N]
         -> float32 [N, A]. The oracle of the policy half of a closed-loop rollout."""
-        x = obs.detach().cpu().numpy() if hasattr(obs, "detach") else np.asarray(obs)
-        ids = policy_ids.detach().cpu().numpy() if hasattr(policy_ids, "detach") else np.asarray(policy_ids)
+        x = to_numpy(obs)
+        ids = to_numpy(policy_ids)
         if x.dtype != np.float32 or x.ndim != 2 or x.shape[1] != self.obs_dim:
             raise ValueError("obs must be float32 [N, %d], got %s %s" % (self.obs_dim, x.dtype, x.shape))
         if ids.shape != (x.shape[0],) or ids.dtype.kind not in "iu":
@@ -176,90 +151,27 @@ def recurrent_param_count(hidden, obs_dim, n_act):
     return H + (D + A + 2 + H) * H + A + H * A
 
 
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-class WalkerPolicyState(object):
-    """The carry of a recurrent closed-loop rollout, the policy's memory of each env: h float32 [N, H], prev_action float32
-    [N, A] (unclamped), prev_reward float32 [N], prev_done uint8 [N]. `WalkerPolicyState(num_envs, hidden, n_act, device)` is
-    the fresh carry, all zero: torch tensors on `device`, updated in place by a launch; device None gives numpy arrays, which
-    is what `WalkerRecurrentPolicy.reference` returns."""
+class WalkerPolicyState(ContinuousPolicyState):
+    """The carry of a recurrent closed-loop rollout (`ContinuousPolicyState` with A = n_joints actions): h float32 [N, H],
+    prev_action float32 [N, A] (unclamped), prev_reward float32 [N], prev_done uint8 [N]. `WalkerPolicyState(num_envs, hidden,
+    n_act, device)` is the fresh carry, all zero: torch tensors on `device`, updated in place by a launch; device None gives
+    numpy arrays, which is what `WalkerRecurrentPolicy.reference` returns. `WalkerPolicyState.of(...)` holds given arrays."""
     __slots__ = ("h", "prev_action", "prev_reward", "prev_done")
 
     def __init__(self, num_envs, hidden, n_act, device=None):
         N, H, A = int(num_envs), int(hidden), int(n_act)
         if N < 1 or not (1 <= H <= MAX_HIDDEN) or A < 1:
             raise ValueError("a carry needs num_envs >= 1, hidden in [1, %d] and n_act >= 1, got %d, %d and %d" % (MAX_HIDDEN, N, H, A))
-        if device is None:
-            self.h, self.prev_action = np.zeros((N, H), np.float32), np.zeros((N, A), np.float32)
-            self.prev_reward, self.prev_done = np.zeros(N, np.float32), np.zeros(N, np.uint8)
-        else:
-            import torch
-            self.h = torch.zeros(N, H, dtype=torch.float32, device=device)
-            self.prev_action = torch.zeros(N, A, dtype=torch.float32, device=device)
-            self.prev_reward = torch.zeros(N, dtype=torch.float32, device=device)
-            self.prev_done = torch.zeros(N, dtype=torch.uint8, device=device)
-
-    @classmethod
-    def of(cls, h, prev_action, prev_reward, prev_done):
-        """A carry that holds the given arrays (not copied)."""
-        self = cls.__new__(cls)
-        self.h, self.prev_action, self.prev_reward, self.prev_done = h, prev_action, prev_reward, prev_done
-        return self
-
-    @property
-    def num_envs(self):
-        return int(self.h.shape[0])
-
-    @property
-    def hidden(self):
-        return int(self.h.shape[1])
-
-    @property
-    def n_act(self):
-        return int(self.prev_action.shape[1])
-
-    @property
-    def device(self):
-        """The torch device of the arrays; None for a numpy carry."""
-        return self.h.device if hasattr(self.h, "detach") else None
-
-    def clone(self):
-        c = (lambda v: v.clone()) if hasattr(self.h, "clone") else (lambda v: v.copy())
-        return WalkerPolicyState.of(c(self.h), c(self.prev_action), c(self.prev_reward), c(self.prev_done))
-
-    def numpy(self):
-        """A host copy, as numpy arrays: what `WalkerRecurrentPolicy.reference` takes."""
-        return WalkerPolicyState.of(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.float32),
-                                    _np(self.prev_reward).astype(np.float32), _np(self.prev_done).astype(np.uint8))
-
-    def observed(self, reward, done, clear=None):
-        """The numpy carry after the env step that followed `reference`: prev_reward = float32(reward), prev_done = done, h
-        and prev_action kept. `clear` (bool [N] or None): the envs whose four fields are zeroed afterwards, which is what
-        `episodic=True` does at a done with `auto_reset`."""
-        out = WalkerPolicyState.of(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.float32),
-                                   _np(reward).astype(np.float32), (_np(done) != 0).astype(np.uint8))
-        if out.prev_reward.shape != (self.num_envs,) or out.prev_done.shape != (self.num_envs,):
-            raise ValueError("reward and done must have shape (%d,)" % self.num_envs)
-        if clear is not None:
-            c = _np(clear).astype(bool)
-            if c.shape != (self.num_envs,):
-                raise ValueError("clear must have shape (%d,)" % self.num_envs)
-            out.h[c] = 0.0
-            out.prev_action[c] = 0.0
-            out.prev_reward[c] = 0.0
-            out.prev_done[c] = 0
-        return out
+        self.h, self.prev_action, self.prev_reward, self.prev_done = self._zero_arrays(N, H, A, device)
 
 
-class WalkerRecurrentPolicy(object):
+class WalkerRecurrentPolicy(PackedPolicySet):
     """P recurrent policies: wx [P, H, D], wa [P, H, A], wr [P, H], wd [P, H], wh [P, H, H], b [P, H], wo [P, A, H], bo [P, A],
     all float32 and finite, 1 <= H <= 256. D and A are checked against the env when the policy is used."""
 
     def __init__(self, wx, wa, wr, wd, wh, b, wo, bo):
-        wx, wa, wr, wd = _f32("wx", wx, 3), _f32("wa", wa, 3), _f32("wr", wr, 2), _f32("wd", wd, 2)
-        wh, b, wo, bo = _f32("wh", wh, 3), _f32("b", b, 2), _f32("wo", wo, 3), _f32("bo", bo, 2)
+        wx, wa, wr, wd = f32_array("wx", wx, 3), f32_array("wa", wa, 3), f32_array("wr", wr, 2), f32_array("wd", wd, 2)
+        wh, b, wo, bo = f32_array("wh", wh, 3), f32_array("b", b, 2), f32_array("wo", wo, 3), f32_array("bo", bo, 2)
         P, H, D = wx.shape
         A = wo.shape[1]
         if P < 1 or D < 1 or A < 1:
@@ -273,10 +185,6 @@ class WalkerRecurrentPolicy(object):
                                                               bo.shape))
         self.wx, self.wa, self.wr, self.wd, self.wh, self.b, self.wo, self.bo = wx, wa, wr, wd, wh, b, wo, bo
         self.num_policies, self.hidden, self.obs_dim, self.n_act = P, H, D, A
-        self._device = {}
-
-    def __len__(self):
-        return self.num_policies
 
     @property
     def param_count(self):
@@ -296,7 +204,7 @@ class WalkerRecurrentPolicy(object):
     @classmethod
     def unpack(cls, packed, hidden, obs_dim, n_act):
         """The inverse of `pack`."""
-        packed = _f32("packed", packed, 2)
+        packed = f32_array("packed", packed, 2)
         P, H, D, A = packed.shape[0], int(hidden), int(obs_dim), int(n_act)
         if packed.shape[1] != recurrent_param_count(H, D, A):
             raise ValueError("packed has shape %s, hidden=%d, obs_dim=%d and n_act=%d need [P, %d]"
@@ -315,15 +223,6 @@ class WalkerRecurrentPolicy(object):
         wo = take(H, A)
         return cls(wx, wa, wr, wd, wh, b, wo, bo)
 
-    def to(self, device):
-        """The packed parameters as a torch tensor on `device` (uploaded once per device)."""
-        import torch
-        from .. import _lib
-        key = str(_lib.canonical_device(device))
-        if key not in self._device:
-            self._device[key] = torch.from_numpy(self.pack()).to(_lib.canonical_device(device)).contiguous()
-        return self._device[key]
-
     def reference(self, obs, policy_ids, state):
         """One step of the definition in numpy float32, with exactly that association: every unit's sum runs one term at a
         time over [N, H] arrays and every output's over [N, A] arrays (D + A + 2 + H + H array operations per step). obs
@@ -331,8 +230,8 @@ class WalkerRecurrentPolicy(object):
         new state): a numpy carry with h = hn and prev_action = the actions; its prev_reward and prev_done are still the old
         ones, since they come from the env step that follows (`WalkerPolicyState.observed`). The oracle of the policy half
         of a recurrent closed-loop rollout."""
-        x = _np(obs)
-        ids = _np(policy_ids)
+        x = to_numpy(obs)
+        ids = to_numpy(policy_ids)
         P, H, D, A = self.num_policies, self.hidden, self.obs_dim, self.n_act
         if x.dtype != np.float32 or x.ndim != 2 or x.shape[1] != D:
             raise ValueError("obs must be float32 [N, %d], got %s %s" % (D, x.dtype, x.shape))
@@ -341,7 +240,7 @@ class WalkerRecurrentPolicy(object):
             raise ValueError("policy_ids must be %d integers" % N)
         if N and (int(ids.min()) < 0 or int(ids.max()) >= P):
             raise ValueError("policy_ids must be in [0, %d)" % P)
-        h, pa, pr, pd = _np(state.h), _np(state.prev_action), _np(state.prev_reward), _np(state.prev_done)
+        h, pa, pr, pd = to_numpy(state.h), to_numpy(state.prev_action), to_numpy(state.prev_reward), to_numpy(state.prev_done)
         if h.shape != (N, H) or h.dtype != np.float32:
             raise ValueError("state.h must be float32 [%d, %d], got %s %s" % (N, H, h.dtype, h.shape))
         if pa.shape != (N, A) or pa.dtype != np.float32 or pr.shape != (N,) or pr.dtype != np.float32 or pd.shape != (N,):

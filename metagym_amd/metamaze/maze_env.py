@@ -27,7 +27,7 @@ Size limits (include/metagym_hip.h)
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, _policy
 from ..spaces import Box, Discrete
 from .maze_task import MAZE_TASK_MANAGER, DeviceTaskTable, TaskConfig, forget_when_freed  # noqa: F401  (TaskConfig re-exported like the reference's maze_env)
 
@@ -463,10 +463,11 @@ class MetaMaze2D(_MazeBatch):
         ret_episode, episode_len, episodes and state always; actions, reward, reward64, done [steps, N] when `record=True`,
         else None (the launch then writes nothing per step). `obs_every` >= 1 keeps a fresh [K, N, w, w] tensor of the
         observations `rollout_obs_steps` selects; 0 keeps the last one only, in the persistent buffer `step` returns, which
-        is written either way. Nothing synchronises when `policy_ids` is None or the array of the previous call. A refused
+        is written either way. Nothing synchronises when `policy_ids` is None, a host array, or the device tensor of the
+        previous call (the same object, unchanged; any other device tensor is read back once to validate it). A refused
         call (an id out of range, a policy built for another view_grid, a carry of another N or H, steps < 1) raises and
         leaves the env and the carry as they were."""
-        from .policy import MazePolicy, MazePolicyRollout, MazePolicyState
+        from .policy import MazePolicy, MazePolicyState
         if self.need_set_task:
             raise Exception("Must call \"set_task\" before rollout_policy")
         self._check_step()
@@ -478,38 +479,17 @@ class MetaMaze2D(_MazeBatch):
         idx = rollout_obs_steps(T, obs_every)
         if policy.view_grid != self.view_grid:
             raise ValueError("the policy was built for view_grid = %d, the env has %d" % (policy.view_grid, self.view_grid))
-        seed = int(seed)
-        if not (0 <= seed < 2 ** 64):
-            raise ValueError("seed must be in [0, 2^64), got %d" % seed)
-        if state is None:
-            state = MazePolicyState.zeros(N, H, dev)
-        elif not isinstance(state, MazePolicyState):
-            raise TypeError("state must be a MazePolicyState, got %s" % type(state).__name__)
-        want = (("h", (N, H), torch.float32), ("prev_action", (N,), torch.int32), ("prev_reward", (N,), torch.float32),
-                ("prev_done", (N,), torch.uint8))
-        for name, shape, dtype in want:
-            v = getattr(state, name)
-            if not isinstance(v, torch.Tensor) or tuple(v.shape) != shape or v.dtype != dtype:
-                raise ValueError("state.%s must be a %s tensor of shape %s (this env has %d envs, the policy %d hidden units)"
-                                 % (name, dtype, shape, N, H))
-        if not (0 <= state.step < 2 ** 64 - T):
-            raise ValueError("state.step = %d is outside [0, 2^64 - steps)" % state.step)
-        ids_d = self._policy_ids(policy_ids, P)
+        state, seed = _policy.check_discrete_carry(state, MazePolicyState, N, H, T, seed, dev)
+        ids_d = _policy.policy_ids(self, policy_ids, P)
         params, thr = policy.to(dev)
         # everything is checked: from here on the env and the new carry are written
-        carry = MazePolicyState(*[getattr(state, name).to(dev).clone().contiguous() for name, _, _ in want], step=state.step + T)
+        carry = MazePolicyState(*[v.to(dev).clone().contiguous() for v in (state.h, state.prev_action, state.prev_reward,
+                                                                           state.prev_done)], step=state.step + T)
         desc = _lib.MazePolicyDesc(P, H, policy.view_grid, params.data_ptr(), thr.data_ptr() if thr is not None else None)
         carry_c = _lib.MazePolicyCarry(carry.h.data_ptr(), carry.prev_action.data_ptr(), carry.prev_reward.data_ptr(),
                                        carry.prev_done.data_ptr())
-        obs = self._obs if int(obs_every) == 0 else torch.empty((len(idx),) + tuple(self._obs.shape), dtype=torch.float32, device=dev)
-        res = MazePolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
-                                torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
-                                carry, obs, idx)
-        if record:
-            res.actions = torch.empty(T, N, dtype=torch.int32, device=dev)
-            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
-            res.reward64 = torch.empty(T, N, dtype=torch.float64, device=dev)
-            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+        res = self._rollout_results(T, idx, obs_every, record, carry)
+        obs = res.obs
         rc = self._lib.mg_maze2d_policy_rollout(self._tasks_c, self._tt, self.max_steps, self.view_grid, int(self.auto_reset), N,
                                                 self._state_c, T, int(obs_every), desc, _lib.ptr(ids_d), carry_c, seed, state.step,
                                                 int(bool(episodic)), _lib.ptr(self._obs), _lib.ptr(res.ret_total),
@@ -530,7 +510,6 @@ class MetaMaze2D(_MazeBatch):
         actions through `rollout` gives the same records and end state bit for bit. Nothing synchronises. A refused call (a
         field of another n, T, kind or device, steps < 1, a call before set_task or reset) raises and leaves the env and the
         field as they were."""
-        from .policy import MazePolicyRollout
         T, N, dev = int(steps), self.num_envs, self.device
         if self.need_set_task:
             raise Exception("Must call \"set_task\" before rollout_expert")
@@ -539,15 +518,8 @@ class MetaMaze2D(_MazeBatch):
             raise ValueError("steps must be at least 1, got %d" % T)
         idx = rollout_obs_steps(T, obs_every)
         field = self._expert_field(field, "rollout_expert")
-        obs = self._obs if int(obs_every) == 0 else torch.empty((len(idx),) + tuple(self._obs.shape), dtype=torch.float32, device=dev)
-        res = MazePolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
-                                torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
-                                None, obs, idx)
-        if record:
-            res.actions = torch.empty(T, N, dtype=torch.int32, device=dev)
-            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
-            res.reward64 = torch.empty(T, N, dtype=torch.float64, device=dev)
-            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+        res = self._rollout_results(T, idx, obs_every, record, None)
+        obs = res.obs
         rc = self._lib.mg_maze2d_expert_rollout(self._tasks_c, self._tt, self.max_steps, self.view_grid, int(self.auto_reset), N,
                                                 self._state_c, T, int(obs_every), _lib.ptr(field.dist), _lib.ptr(self._obs),
                                                 _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len),
@@ -557,25 +529,22 @@ class MetaMaze2D(_MazeBatch):
         _lib.check(rc, "mg_maze2d_expert_rollout")
         return res
 
-    def _policy_ids(self, policy_ids, P):
-        """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a hipGraph
-        capture after its warm-up) neither uploads nor reads back."""
-        N = self.num_envs
-        if policy_ids is None:
-            ids_h = np.arange(N, dtype=np.int64) % P
-        else:
-            ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
-            if ids_h.shape != (N,):
-                raise ValueError("policy_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
-            if ids_h.dtype.kind not in "iu":
-                raise ValueError("policy_ids must be integers, got %s" % ids_h.dtype)
-            if int(ids_h.min()) < 0 or int(ids_h.max()) >= P:
-                raise ValueError("policy_ids must be in [0, %d)" % P)
-        key = (P, ids_h.astype(np.int32).tobytes())
-        keep = getattr(self, "_policy_ids_keep", None)
-        if keep is None or keep[0] != key:
-            keep = self._policy_ids_keep = (key, torch.as_tensor(ids_h.astype(np.int32), device=self.device).contiguous())
-        return keep[1]
+    def _rollout_results(self, T, idx, obs_every, record, carry):
+        """The `MazePolicyRollout` of a T-step launch, its tensors allocated: the four results always, the observations kept
+        (`obs_every` = 0: the persistent buffer), the four [T, N] records with `record`, else None. `rollout_policy` and
+        `rollout_expert` share it."""
+        from .policy import MazePolicyRollout
+        N, dev = self.num_envs, self.device
+        obs = self._obs if int(obs_every) == 0 else torch.empty((len(idx),) + tuple(self._obs.shape), dtype=torch.float32, device=dev)
+        res = MazePolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
+                                torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+                                carry, obs, idx)
+        if record:
+            res.actions = torch.empty(T, N, dtype=torch.int32, device=dev)
+            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+            res.reward64 = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+        return res
 
 
 class _Maze3D(_MazeBatch):

@@ -28,9 +28,9 @@ action = (out[0] < thr) ? (out[1] & 3) : greedy.
     res = env.rollout_policy(pol, steps=64)                 # env e plays policy e % P
     res = env.rollout_policy(pol, steps=64, state=res.state)   # and goes on, memory kept
 """
-import math
-
 import numpy as np
+
+from .._policy import PackedPolicySet, check_epsilon, eps_threshold, f32_array, philox4x32_10, to_numpy  # noqa: F401
 
 MAX_HIDDEN = 64
 VIEW_GRIDS = (1, 2, 3)
@@ -57,41 +57,6 @@ def param_count(hidden, view_grid):
     if not (1 <= int(hidden) <= MAX_HIDDEN):
         raise ValueError("hidden units must be in [1, %d], got %r" % (MAX_HIDDEN, hidden))
     return 4 + int(hidden) * _record(int(hidden), input_dim(view_grid))
-
-
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-def _f32(name, x, ndim):
-    a = _np(x)
-    if a.dtype != np.float32:
-        raise TypeError("%s must be float32, got %s" % (name, a.dtype))
-    if a.ndim != ndim:
-        raise ValueError("%s must have %d dimensions, got shape %s" % (name, ndim, a.shape))
-    if not np.isfinite(a).all():
-        raise ValueError("%s holds a value that is not finite" % name)
-    return np.ascontiguousarray(a)
-
-
-def eps_threshold(epsilon):
-    """thr = min(floor(epsilon * 2^32), 2^32 - 1) as uint32, elementwise; epsilon float64 in [0, 1]."""
-    e = np.asarray(epsilon, np.float64)
-    return np.asarray([min(int(math.floor(v * 4294967296.0)), 0xFFFFFFFF) for v in e.ravel()], np.uint32).reshape(e.shape)
-
-
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 (Salmon et al., SC'11) on numpy integers, the function of csrc/mg_philox.h: uint32 arrays (or scalars) in,
-    four uint32 arrays out."""
-    m32 = np.uint64(0xFFFFFFFF)
-    c0, c1, c2, c3, k0, k1 = np.broadcast_arrays(*[np.asarray(v, np.uint64) & m32 for v in (c0, c1, c2, c3, k0, k1)])
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
-        k0 = (k0 + np.uint64(0x9E3779B9)) & m32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & m32
-    return tuple(v.astype(np.uint32) for v in (c0, c1, c2, c3))
 
 
 class MazePolicyState(object):
@@ -127,16 +92,17 @@ class MazePolicyState(object):
 
     def numpy(self):
         """The same carry on the host, as numpy arrays."""
-        return MazePolicyState(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.int32),
-                               _np(self.prev_reward).astype(np.float32), _np(self.prev_done).astype(np.uint8), self.step)
+        return MazePolicyState(to_numpy(self.h).astype(np.float32), to_numpy(self.prev_action).astype(np.int32),
+                               to_numpy(self.prev_reward).astype(np.float32), to_numpy(self.prev_done).astype(np.uint8), self.step)
 
 
-class MazePolicy(object):
+class MazePolicy(PackedPolicySet):
     """P recurrent policies: wx [P, H, D], wh [P, H, H], b [P, H], wo [P, 4, H], bo [P, 4], all float32 and finite; epsilon
     float64 [P] in [0, 1] or None (no exploration). 1 <= H <= 64, D = (2 view_grid + 1)^2 + 6 with view_grid in {1, 2, 3}."""
 
     def __init__(self, wx, wh, b, wo, bo, epsilon=None):
-        wx, wh, b, wo, bo = _f32("wx", wx, 3), _f32("wh", wh, 3), _f32("b", b, 2), _f32("wo", wo, 3), _f32("bo", bo, 2)
+        wx, wh, b = f32_array("wx", wx, 3), f32_array("wh", wh, 3), f32_array("b", b, 2)
+        wo, bo = f32_array("wo", wo, 3), f32_array("bo", bo, 2)
         P, H, D = wx.shape
         if P < 1:
             raise ValueError("a policy set needs at least one policy")
@@ -147,32 +113,13 @@ class MazePolicy(object):
         if wh.shape != (P, H, H) or b.shape != (P, H) or wo.shape != (P, 4, H) or bo.shape != (P, 4):
             raise ValueError("shapes must be wx [P,H,D], wh [P,H,H], b [P,H], wo [P,4,H], bo [P,4]; got %s %s %s %s %s"
                              % (wx.shape, wh.shape, b.shape, wo.shape, bo.shape))
-        if epsilon is not None:
-            eps = _np(epsilon)
-            if eps.dtype != np.float64:
-                raise TypeError("epsilon must be float64, got %s" % eps.dtype)
-            if eps.shape != (P,):
-                raise ValueError("epsilon must have shape (%d,), got %s" % (P, eps.shape))
-            if not ((eps >= 0.0) & (eps <= 1.0)).all():
-                raise ValueError("epsilon must be in [0, 1]")
-            epsilon = np.ascontiguousarray(eps)
-        self.wx, self.wh, self.b, self.wo, self.bo, self.epsilon = wx, wh, b, wo, bo, epsilon
+        self.wx, self.wh, self.b, self.wo, self.bo = wx, wh, b, wo, bo
+        self.epsilon = None if epsilon is None else check_epsilon(epsilon, P)
         self.num_policies, self.hidden, self.input_dim, self.view_grid = P, H, D, _VIEW_OF_DIM[D]
-        self._device = {}
-
-    def __len__(self):
-        return self.num_policies
 
     @property
     def param_count(self):
         return param_count(self.hidden, self.view_grid)
-
-    @property
-    def thresholds(self):
-        """uint32 [P]: thr[p] = min(floor(epsilon[p] * 2^32), 2^32 - 1); zeros without epsilon."""
-        if self.epsilon is None:
-            return np.zeros(self.num_policies, np.uint32)
-        return eps_threshold(self.epsilon)
 
     def pack(self):
         """float32 [P, param_count]: the layout the kernel reads (documented in include/metagym_hip.h). bo[0..3], then per
@@ -192,7 +139,7 @@ class MazePolicy(object):
     @classmethod
     def unpack(cls, packed, hidden, view_grid, epsilon=None):
         """The inverse of `pack`."""
-        packed = _f32("packed", packed, 2)
+        packed = f32_array("packed", packed, 2)
         P, H, D = packed.shape[0], int(hidden), input_dim(view_grid)
         if packed.shape[1] != param_count(H, view_grid):
             raise ValueError("packed has shape %s, hidden=%d and view_grid=%d need [P, %d]"
@@ -202,18 +149,10 @@ class MazePolicy(object):
         return cls(rec[:, :, :D].copy(), rec[:, :, D + 1:D + 1 + H].copy(), rec[:, :, D].copy(),
                    rec[:, :, R - 4:].transpose(0, 2, 1).copy(), packed[:, :4].copy(), epsilon)
 
-    def to(self, device):
-        """(packed parameters, thresholds or None) as torch tensors on `device` (uploaded once per device). The thresholds
-        travel as the int32 tensor with the uint32's bits."""
-        import torch
-        from .. import _lib
-        dev = _lib.canonical_device(device)
-        key = str(dev)
-        if key not in self._device:
-            params = torch.from_numpy(self.pack()).to(dev).contiguous()
-            thr = None if self.epsilon is None else torch.from_numpy(self.thresholds.view(np.int32).copy()).to(dev).contiguous()
-            self._device[key] = (params, thr)
-        return self._device[key]
+    def _host(self):
+        """`to(device)` gives (packed parameters, thresholds or None); the thresholds travel as the int32 tensor with the
+        uint32's bits."""
+        return self.pack(), self._threshold_bits()
 
     def reference(self, obs, policy_ids, state, seed=0, env_ids=None, return_explored=False):
         """One step of the definition above in numpy float32 (and numpy integers for the exploration), with exactly that
@@ -223,8 +162,8 @@ class MazePolicy(object):
         [N] mask of the envs whose action was the exploratory draw. The oracle of the policy half of a closed-loop rollout."""
         P, H, D = self.num_policies, self.hidden, self.input_dim
         ww = D - 6
-        win = _np(obs)
-        ids = _np(policy_ids)
+        win = to_numpy(obs)
+        ids = to_numpy(policy_ids)
         if win.dtype != np.float32 or win.ndim not in (2, 3) or int(np.prod(win.shape[1:])) != ww:
             raise ValueError("obs must be float32 [N, %d] windows, got %s %s" % (ww, win.dtype, win.shape))
         N = win.shape[0]
@@ -233,8 +172,8 @@ class MazePolicy(object):
             raise ValueError("policy_ids must be %d integers" % N)
         if N and (int(ids.min()) < 0 or int(ids.max()) >= P):
             raise ValueError("policy_ids must be in [0, %d)" % P)
-        h = _np(state.h)
-        pa, pr, pd = _np(state.prev_action), _np(state.prev_reward), _np(state.prev_done)
+        h = to_numpy(state.h)
+        pa, pr, pd = to_numpy(state.prev_action), to_numpy(state.prev_reward), to_numpy(state.prev_done)
         if h.shape != (N, H) or h.dtype != np.float32:
             raise ValueError("state.h must be float32 [%d, %d], got %s %s" % (N, H, h.dtype, h.shape))
         if pa.shape != (N,) or pr.shape != (N,) or pd.shape != (N,) or pr.dtype != np.float32:
@@ -267,7 +206,7 @@ class MazePolicy(object):
                 best = np.where(better, logits[:, k], best)
         assert hn.dtype == np.float32 and logits.dtype == np.float32
         thr = self.thresholds[ids]
-        e = np.arange(N, dtype=np.uint64) if env_ids is None else _np(env_ids).astype(np.uint64)
+        e = np.arange(N, dtype=np.uint64) if env_ids is None else to_numpy(env_ids).astype(np.uint64)
         n, s = int(state.step), int(seed)
         out = philox4x32_10(e, n & 0xFFFFFFFF, (n >> 32) & 0xFFFFFFFF, PHILOX_TAG, s & 0xFFFFFFFF, (s >> 32) & 0xFFFFFFFF)
         explored = out[0] < thr

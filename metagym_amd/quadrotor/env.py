@@ -21,7 +21,7 @@ from collections.abc import Mapping
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, _policy
 from ..spaces import Box, Space
 
 TASKS = {"no_collision": 0, "velocity_control": 1, "hovering_control": 2}
@@ -419,19 +419,10 @@ class Quadrotor(object):
             if episodic and not self.auto_reset:
                 raise ValueError("episodic=True clears the carry at a fused reset: it needs an env built with auto_reset=True")
             if state is not None:
-                if not isinstance(state, QuadrotorPolicyState):
-                    raise TypeError("state must be a QuadrotorPolicyState, got %s" % type(state).__name__)
-                fields = (state.h, state.prev_action, state.prev_reward, state.prev_done)
-                if not all(isinstance(t, torch.Tensor) for t in fields):
-                    raise ValueError("state must hold torch tensors on %s (QuadrotorPolicyState.zeros(N, H, device))" % dev)
-                if any(t.device != dev for t in fields):
-                    raise ValueError("state lives on %s, the env on %s" % (state.h.device, dev))
-                want = (((N, policy.hidden), torch.float32), ((N, 4), torch.float32), ((N,), torch.float32), ((N,), torch.uint8))
-                for t, (shape, dtype), name in zip(fields, want, QuadrotorPolicyState.__slots__):
-                    if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-                        raise ValueError("state.%s must be a contiguous %s tensor of shape %s (num_envs=%d, hidden=%d), got %s %s"
-                                         % (name, dtype, shape, N, policy.hidden, t.dtype, tuple(t.shape)))
-        ids_d = self._policy_ids(policy_ids, P)
+                _policy.check_continuous_carry(state, QuadrotorPolicyState, N, policy.hidden, 4, dev,
+                                               "QuadrotorPolicyState.zeros(N, H, device)",
+                                               "num_envs=%d, hidden=%d" % (N, policy.hidden))
+        ids_d = _policy.policy_ids(self, policy_ids, P)
         params = policy.to(dev)
         desc = _lib.QuadrotorPolicyDesc(params.data_ptr(), ids_d.data_ptr(), P, policy.hidden, policy.obs_dim)
         res = PolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
@@ -465,32 +456,6 @@ class Quadrotor(object):
                                                    _raw_stream(self._dev_index))
         _lib.check(rc, "mg_quadrotor_policy_rollout")
         return res
-
-    def _policy_ids(self, policy_ids, P):
-        """int32 [N] device tensor of validated policy ids. The last one is kept: a repeated call (a search loop, a
-        hipGraph capture after its warm-up) neither uploads nor reads back."""
-        N = self.num_envs
-        keep = getattr(self, "_policy_ids_keep", None)
-        if isinstance(policy_ids, torch.Tensor) and keep is not None and keep[0] == P and policy_ids is keep[2] and \
-                policy_ids._version == keep[3]:
-            return keep[1]
-        if policy_ids is None:
-            ids_h = np.arange(N, dtype=np.int64) % P
-        else:
-            ids_h = policy_ids.detach().cpu().numpy() if isinstance(policy_ids, torch.Tensor) else np.asarray(policy_ids)
-            if ids_h.shape != (N,):
-                raise ValueError("policy_ids must have shape (%d,), got %s" % (N, tuple(ids_h.shape)))
-            if ids_h.dtype.kind not in "iu":
-                raise ValueError("policy_ids must be integers, got %s" % ids_h.dtype)
-            if N and (int(ids_h.min()) < 0 or int(ids_h.max()) >= P):
-                raise ValueError("policy_ids must be in [0, %d)" % P)
-        ids_h = ids_h.astype(np.int32)
-        if keep is not None and keep[0] == P and keep[4] == ids_h.tobytes():
-            return keep[1]
-        ids_d = torch.as_tensor(ids_h, device=self.device).contiguous()
-        src = policy_ids if isinstance(policy_ids, torch.Tensor) else None
-        self._policy_ids_keep = (P, ids_d, src, src._version if src is not None else None, ids_h.tobytes())
-        return ids_d
 
     def render(self, mode="human"):
         raise NotImplementedError("rendering is out of scope for the batched engine (SURVEY.md §2 row 5)")

@@ -40,6 +40,8 @@ done; `episodic=True` (with `auto_reset`) clears the carry of an env at its done
 """
 import numpy as np
 
+from .._policy import ContinuousPolicyState, PackedPolicySet, f32_array, pad4, to_numpy
+
 MAX_HIDDEN = 256
 MAX_RECURRENT_HIDDEN = 64
 OBS_DIMS = (16, 19)
@@ -51,25 +53,12 @@ def param_count(hidden, obs_dim):
     return _HEAD + _REC * hidden if hidden > 0 else _HEAD + 4 * obs_dim
 
 
-def _f32(name, x, ndim):
-    if hasattr(x, "detach"):                               # a torch tensor
-        x = x.detach().cpu().numpy()
-    a = np.asarray(x)
-    if a.dtype != np.float32:
-        raise TypeError("%s must be float32, got %s" % (name, a.dtype))
-    if a.ndim != ndim:
-        raise ValueError("%s must have %d dimensions, got shape %s" % (name, ndim, a.shape))
-    if not np.isfinite(a).all():
-        raise ValueError("%s holds a value that is not finite" % name)
-    return np.ascontiguousarray(a)
-
-
-class QuadrotorPolicy(object):
+class QuadrotorPolicy(PackedPolicySet):
     """P policies with one hidden ReLU layer: w1 [P, H, D], b1 [P, H], w2 [P, 4, H], b2 [P, 4], all float32 and finite.
     `QuadrotorPolicy.linear(w, b)` builds the H = 0 form."""
 
     def __init__(self, w1, b1, w2, b2):
-        w1, b1, w2, b2 = _f32("w1", w1, 3), _f32("b1", b1, 2), _f32("w2", w2, 3), _f32("b2", b2, 2)
+        w1, b1, w2, b2 = f32_array("w1", w1, 3), f32_array("b1", b1, 2), f32_array("w2", w2, 3), f32_array("b2", b2, 2)
         P, H, D = w1.shape
         if P < 1:
             raise ValueError("a policy set needs at least one policy")
@@ -82,12 +71,11 @@ class QuadrotorPolicy(object):
                              % (w1.shape, b1.shape, w2.shape, b2.shape))
         self.w1, self.b1, self.w2, self.b2 = w1, b1, w2, b2
         self.num_policies, self.hidden, self.obs_dim = P, H, D
-        self._device = {}
 
     @classmethod
     def linear(cls, w, b):
         """a = b + w @ x in the order of the definition: w [P, 4, D], b [P, 4]."""
-        w, b = _f32("w", w, 3), _f32("b", b, 2)
+        w, b = f32_array("w", w, 3), f32_array("b", b, 2)
         P, four, D = w.shape
         if P < 1:
             raise ValueError("a policy set needs at least one policy")
@@ -99,11 +87,7 @@ class QuadrotorPolicy(object):
         self.w1 = self.b1 = None
         self.w2, self.b2 = w, b                            # the output layer, read straight from x
         self.num_policies, self.hidden, self.obs_dim = P, 0, D
-        self._device = {}
         return self
-
-    def __len__(self):
-        return self.num_policies
 
     @property
     def param_count(self):
@@ -128,7 +112,7 @@ class QuadrotorPolicy(object):
     @classmethod
     def unpack(cls, packed, hidden, obs_dim):
         """The inverse of `pack`."""
-        packed = _f32("packed", packed, 2)
+        packed = f32_array("packed", packed, 2)
         P = packed.shape[0]
         if obs_dim not in OBS_DIMS or not (0 <= hidden <= MAX_HIDDEN) or packed.shape[1] != param_count(hidden, obs_dim):
             raise ValueError("packed has shape %s, hidden=%d and obs_dim=%d need [P, %d]"
@@ -138,15 +122,6 @@ class QuadrotorPolicy(object):
             return cls.linear(packed[:, _HEAD:].reshape(P, obs_dim, 4).transpose(0, 2, 1).copy(), b2)
         rec = packed[:, _HEAD:].reshape(P, hidden, _REC)
         return cls(rec[:, :, :obs_dim].copy(), rec[:, :, obs_dim].copy(), rec[:, :, _W2_AT:].transpose(0, 2, 1).copy(), b2)
-
-    def to(self, device):
-        """The packed parameters as a torch tensor on `device` (uploaded once per device)."""
-        import torch
-        from .. import _lib
-        key = str(_lib.canonical_device(device))
-        if key not in self._device:
-            self._device[key] = torch.from_numpy(self.pack()).to(_lib.canonical_device(device)).contiguous()
-        return self._device[key]
 
     def reference(self, obs, policy_ids):
         """The definition above in numpy float32, with exactly that association: obs [N, D] float32, policy_ids [N]
@@ -178,12 +153,8 @@ class QuadrotorPolicy(object):
         return a
 
 
-def _pad4(v):
-    return (int(v) + 3) & ~3
-
-
 def _rrecord(hidden, obs_dim):
-    return _pad4(obs_dim) + _pad4(hidden) + 12
+    return pad4(obs_dim) + pad4(hidden) + 12
 
 
 def recurrent_param_count(hidden, obs_dim):
@@ -196,14 +167,10 @@ def recurrent_param_count(hidden, obs_dim):
     return _HEAD + int(hidden) * _rrecord(hidden, obs_dim)
 
 
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
-class QuadrotorPolicyState(object):
-    """The carry of a recurrent closed-loop rollout, the policy's memory of each env: h float32 [N, H], prev_action float32
-    [N, 4] (unclamped), prev_reward float32 [N], prev_done uint8 [N]. Torch tensors on the env's device, updated in place by
-    a launch (or numpy arrays, for `QuadrotorRecurrentPolicy.reference`). All zero when fresh."""
+class QuadrotorPolicyState(ContinuousPolicyState):
+    """The carry of a recurrent closed-loop rollout (`ContinuousPolicyState` with four actions): h float32 [N, H], prev_action
+    float32 [N, 4] (unclamped), prev_reward float32 [N], prev_done uint8 [N]. `QuadrotorPolicyState.zeros(N, H, device)` is
+    the fresh carry."""
     __slots__ = ("h", "prev_action", "prev_reward", "prev_done")
 
     def __init__(self, h, prev_action, prev_reward, prev_done):
@@ -215,58 +182,16 @@ class QuadrotorPolicyState(object):
         N, H = int(num_envs), int(hidden)
         if N < 1 or not (1 <= H <= MAX_RECURRENT_HIDDEN):
             raise ValueError("a carry needs num_envs >= 1 and hidden in [1, %d], got %d and %d" % (MAX_RECURRENT_HIDDEN, N, H))
-        if device is None:
-            return cls(np.zeros((N, H), np.float32), np.zeros((N, 4), np.float32), np.zeros(N, np.float32), np.zeros(N, np.uint8))
-        import torch
-        return cls(torch.zeros(N, H, dtype=torch.float32, device=device), torch.zeros(N, 4, dtype=torch.float32, device=device),
-                   torch.zeros(N, dtype=torch.float32, device=device), torch.zeros(N, dtype=torch.uint8, device=device))
-
-    @property
-    def num_envs(self):
-        return int(self.h.shape[0])
-
-    @property
-    def hidden(self):
-        return int(self.h.shape[1])
-
-    @property
-    def device(self):
-        """The torch device of the arrays; None for a numpy carry."""
-        return getattr(self.h, "device", None) if hasattr(self.h, "detach") else None
-
-    def clone(self):
-        c = (lambda v: v.clone()) if hasattr(self.h, "clone") else (lambda v: v.copy())
-        return QuadrotorPolicyState(c(self.h), c(self.prev_action), c(self.prev_reward), c(self.prev_done))
-
-    def numpy(self):
-        """A host copy, as numpy arrays: what `QuadrotorRecurrentPolicy.reference` takes."""
-        return QuadrotorPolicyState(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.float32),
-                                    _np(self.prev_reward).astype(np.float32), _np(self.prev_done).astype(np.uint8))
-
-    def observed(self, reward, done, clear=None):
-        """The numpy carry after the env step that followed `reference`: prev_reward = float32(reward), prev_done = done, h
-        and prev_action kept. `clear` (bool [N] or None): the envs whose four fields are zeroed afterwards, which is what
-        `episodic=True` does at a done with `auto_reset`."""
-        out = QuadrotorPolicyState(_np(self.h).astype(np.float32), _np(self.prev_action).astype(np.float32),
-                                   _np(reward).astype(np.float32), (_np(done) != 0).astype(np.uint8))
-        if out.prev_reward.shape != (self.num_envs,) or out.prev_done.shape != (self.num_envs,):
-            raise ValueError("reward and done must have shape (%d,)" % self.num_envs)
-        if clear is not None:
-            c = _np(clear).astype(bool)
-            out.h[c] = 0.0
-            out.prev_action[c] = 0.0
-            out.prev_reward[c] = 0.0
-            out.prev_done[c] = 0
-        return out
+        return cls(*cls._zero_arrays(N, H, 4, device))
 
 
-class QuadrotorRecurrentPolicy(object):
+class QuadrotorRecurrentPolicy(PackedPolicySet):
     """P recurrent policies: wx [P, H, D], wa [P, H, 4], wr [P, H], wd [P, H], wh [P, H, H], b [P, H], wo [P, 4, H], bo [P, 4],
     all float32 and finite. 1 <= H <= 64, D = 16, or 19 for velocity_control."""
 
     def __init__(self, wx, wa, wr, wd, wh, b, wo, bo):
-        wx, wa, wr, wd = _f32("wx", wx, 3), _f32("wa", wa, 3), _f32("wr", wr, 2), _f32("wd", wd, 2)
-        wh, b, wo, bo = _f32("wh", wh, 3), _f32("b", b, 2), _f32("wo", wo, 3), _f32("bo", bo, 2)
+        wx, wa, wr, wd = f32_array("wx", wx, 3), f32_array("wa", wa, 3), f32_array("wr", wr, 2), f32_array("wd", wd, 2)
+        wh, b, wo, bo = f32_array("wh", wh, 3), f32_array("b", b, 2), f32_array("wo", wo, 3), f32_array("bo", bo, 2)
         P, H, D = wx.shape
         if P < 1:
             raise ValueError("a policy set needs at least one policy")
@@ -281,10 +206,6 @@ class QuadrotorRecurrentPolicy(object):
                                                               bo.shape))
         self.wx, self.wa, self.wr, self.wd, self.wh, self.b, self.wo, self.bo = wx, wa, wr, wd, wh, b, wo, bo
         self.num_policies, self.hidden, self.obs_dim = P, H, D
-        self._device = {}
-
-    def __len__(self):
-        return self.num_policies
 
     @property
     def param_count(self):
@@ -296,7 +217,7 @@ class QuadrotorRecurrentPolicy(object):
         to DP; b[j], wr[j], wd[j], 0; wa[j][0..3]; wh[j][0..H-1], zeros up to HP; wo[0..3][j]. Every piece starts on a
         multiple of four floats, so every 16-byte read is aligned."""
         P, H, D = self.num_policies, self.hidden, self.obs_dim
-        DP, HP = _pad4(D), _pad4(H)
+        DP, HP = pad4(D), pad4(H)
         out = np.zeros((P, self.param_count), np.float32)
         out[:, :_HEAD] = self.bo
         rec = out[:, _HEAD:].reshape(P, H, _rrecord(H, D))
@@ -312,25 +233,16 @@ class QuadrotorRecurrentPolicy(object):
     @classmethod
     def unpack(cls, packed, hidden, obs_dim):
         """The inverse of `pack`."""
-        packed = _f32("packed", packed, 2)
+        packed = f32_array("packed", packed, 2)
         P, H, D = packed.shape[0], int(hidden), obs_dim
         if packed.shape[1] != recurrent_param_count(H, D):
             raise ValueError("packed has shape %s, hidden=%d and obs_dim=%d need [P, %d]"
                              % (packed.shape, H, D, recurrent_param_count(H, D)))
-        DP, HP = _pad4(D), _pad4(H)
+        DP, HP = pad4(D), pad4(H)
         rec = packed[:, _HEAD:].reshape(P, H, _rrecord(H, D))
         return cls(rec[:, :, :D].copy(), rec[:, :, DP + 4:DP + 8].copy(), rec[:, :, DP + 1].copy(), rec[:, :, DP + 2].copy(),
                    rec[:, :, DP + 8:DP + 8 + H].copy(), rec[:, :, DP].copy(), rec[:, :, DP + 8 + HP:].transpose(0, 2, 1).copy(),
                    packed[:, :_HEAD].copy())
-
-    def to(self, device):
-        """The packed parameters as a torch tensor on `device` (uploaded once per device)."""
-        import torch
-        from .. import _lib
-        key = str(_lib.canonical_device(device))
-        if key not in self._device:
-            self._device[key] = torch.from_numpy(self.pack()).to(_lib.canonical_device(device)).contiguous()
-        return self._device[key]
 
     def reference(self, obs, policy_ids, state):
         """One step of the definition above in numpy float32, with exactly that association: the sums run one term at a
@@ -339,8 +251,8 @@ class QuadrotorRecurrentPolicy(object):
         carry with h = hn and prev_action = the actions; its prev_reward and prev_done are still the old ones, since they
         come from the env step that follows (`QuadrotorPolicyState.observed`). The oracle of the policy half of a
         recurrent closed-loop rollout."""
-        x = _np(obs)
-        ids = _np(policy_ids)
+        x = to_numpy(obs)
+        ids = to_numpy(policy_ids)
         P, H, D = self.num_policies, self.hidden, self.obs_dim
         if x.dtype != np.float32 or x.ndim != 2 or x.shape[1] != D:
             raise ValueError("obs must be float32 [N, %d], got %s %s" % (D, x.dtype, x.shape))
@@ -349,7 +261,7 @@ class QuadrotorRecurrentPolicy(object):
             raise ValueError("policy_ids must be %d integers" % N)
         if N and (int(ids.min()) < 0 or int(ids.max()) >= P):
             raise ValueError("policy_ids must be in [0, %d)" % P)
-        h, pa, pr, pd = _np(state.h), _np(state.prev_action), _np(state.prev_reward), _np(state.prev_done)
+        h, pa, pr, pd = to_numpy(state.h), to_numpy(state.prev_action), to_numpy(state.prev_reward), to_numpy(state.prev_done)
         if h.shape != (N, H) or h.dtype != np.float32:
             raise ValueError("state.h must be float32 [%d, %d], got %s %s" % (N, H, h.dtype, h.shape))
         if pa.shape != (N, 4) or pa.dtype != np.float32 or pr.shape != (N,) or pr.dtype != np.float32 or pd.shape != (N,):

@@ -555,3 +555,32 @@ def test_refused_calls_raise_and_launch_nothing():
     # and the env still runs
     res = env.rollout_policy(pol, 4, state=st)
     assert res.state.step == 9
+
+
+def test_a_device_policy_ids_tensor_is_kept_until_it_is_written():
+    """The same device tensor, unchanged, is not read back on a repeated call and gives the same rollout; an in-place write
+    is seen, validated again, and gives what a fresh env gives for that assignment as a host array."""
+    N, P, H, T, K, M = 65, 2, 2, 4, 5, 7                              # one full wave and one ragged wave
+    pol = make_policy(P, H, K, 31)
+    env, _ = make_env(N, K, M, "Uniform")
+    sd0 = env.state_dict()
+    ids = torch.from_numpy((np.arange(N) % P).astype(np.int32)).to(DEV)
+    first = env.rollout_policy(pol, T, policy_ids=ids, record=True)
+    keep = env._policy_ids_keep
+    assert keep[2] is ids and keep[3] == ids._version
+    env.load_state_dict(sd0)
+    again = env.rollout_policy(pol, T, policy_ids=ids, record=True)
+    assert env._policy_ids_keep is keep                               # the fast path: nothing read back, nothing stored
+    same_results(again, first, "the same tensor", RECORDS)
+    other = ((np.arange(N) // 3 + 1) % P).astype(np.int32)
+    ids.copy_(torch.from_numpy(other))
+    env.load_state_dict(sd0)
+    changed = env.rollout_policy(pol, T, policy_ids=ids, record=True)
+    assert env._policy_ids_keep is not keep and env._policy_ids_keep[3] == ids._version
+    fresh, _ = make_env(N, K, M, "Uniform")
+    fresh.load_state_dict(sd0)
+    want = fresh.rollout_policy(pol, T, policy_ids=other, record=True)
+    same_results(changed, want, "in-place write", RECORDS)
+    same_sd(env.state_dict(), fresh.state_dict(), "in-place write")
+    same_carry(changed.state, want.state, "in-place write")
+    assert not torch.equal(changed.actions, first.actions)            # the two assignments do play differently

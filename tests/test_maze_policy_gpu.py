@@ -422,3 +422,35 @@ def test_refused_calls_leave_the_env_and_the_carry_unchanged():
     assert res.state.step == 9
     from metagym_amd.metamaze import MetaMazeContinuous3D, MetaMazeDiscrete3D
     assert not hasattr(MetaMazeDiscrete3D, "rollout_policy") and not hasattr(MetaMazeContinuous3D, "rollout_policy")
+
+
+def test_a_device_policy_ids_tensor_is_kept_until_it_is_written():
+    """The same device tensor, unchanged, is not read back on a repeated call and gives the same rollout; an in-place write
+    is seen, validated again, and gives what a fresh env gives for that assignment as a host array."""
+    N, P, H, T, vg = 65, 2, 2, 4, 1                                   # one full wave and one ragged wave
+    pol = make_policy(P, H, vg, 31)
+    env = make_env(N, "SURVIVAL", True, vg)
+    sd0 = env.state_dict()
+    ids = torch.from_numpy((np.arange(N) % P).astype(np.int32)).to(DEV)
+    records = ("actions", "reward", "reward64", "done")
+    first = env.rollout_policy(pol, T, policy_ids=ids, record=True)
+    keep = env._policy_ids_keep
+    assert keep[2] is ids and keep[3] == ids._version
+    env.load_state_dict(sd0)
+    again = env.rollout_policy(pol, T, policy_ids=ids, record=True)
+    assert env._policy_ids_keep is keep                               # the fast path: nothing read back, nothing stored
+    for name in records:
+        assert torch.equal(getattr(again, name), getattr(first, name)), name
+    other = ((np.arange(N) // 3 + 1) % P).astype(np.int32)
+    ids.copy_(torch.from_numpy(other))
+    env.load_state_dict(sd0)
+    changed = env.rollout_policy(pol, T, policy_ids=ids, record=True)
+    assert env._policy_ids_keep is not keep and env._policy_ids_keep[3] == ids._version
+    fresh = make_env(N, "SURVIVAL", True, vg)
+    fresh.load_state_dict(sd0)
+    want = fresh.rollout_policy(pol, T, policy_ids=other, record=True)
+    for name in records:
+        assert torch.equal(getattr(changed, name), getattr(want, name)), name
+    _same_sd(env.state_dict(), fresh.state_dict(), "in-place write")
+    _same_carry(changed.state, want.state, "in-place write")
+    assert not torch.equal(changed.actions, first.actions)            # the two assignments do play differently
