@@ -263,7 +263,8 @@ def test_maze2d_survival_crumbs_outside_the_food_list():
 @pytest.mark.parametrize("continuous", [False, True])
 def test_maze3d_batch_matches_oracle(continuous):
     """9x9 mazes (config C3 geometry), 6 tasks x 96 envs, 64x64 and 40x24 frames, both task types;
-    discrete frames must be identical to the oracle's, continuous >= 99.9 %."""
+    discrete frames must be identical to the oracle's, continuous >= 99.9 %; the continuous envs' cell and heading equal the
+    oracle's at every step, their location within 1e-5."""
     import metagym_amd
     from metagym_amd.metamaze import MazeTaskSampler, MAZE_TASK_MANAGER
     tex_u8 = MAZE_TASK_MANAGER.grounds.astype(np.uint8)
@@ -296,6 +297,13 @@ def test_maze3d_batch_matches_oracle(continuous):
                 else:
                     r, dd = mo.step_disc3d(otasks[ids[e]], tt, 12, states[e], a[e])
                 assert r == r64[e] and dd == d[e], (t, e)
+            if continuous:
+                # every env's state against the oracle's, every step: the heading involves no transcendental and the cell is an
+                # integer, so both are equal; the location to the north-star 1e-5
+                grid, ori, loc = env.grid.cpu().numpy(), env.ori.cpu().numpy(), env.loc.cpu().numpy()
+                assert np.array_equal(grid.T, np.asarray([list(s.c.grid) for s in states])), t
+                assert np.array_equal(ori, np.asarray([s.c.ori for s in states])), t
+                assert np.allclose(loc.T, np.asarray([list(s.c.loc) for s in states], np.float32), rtol=1e-5, atol=1e-5), t
             for e in range(t % 7, n, 7):
                 ref = mo.observe_3d(otasks[ids[e]], tt, view, states[e], int(continuous))
                 bad += int((ob[e] != ref).sum())
