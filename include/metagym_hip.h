@@ -780,6 +780,80 @@ int mg_maze3d_expert_rollout(const mg_maze_tasks *tasks, const mg_maze_view *vie
                              double *ret_episode, int32_t *episode_len, int32_t *episodes, void *actions, float *reward,
                              double *reward64, uint8_t *done, void *stream);
 
+/* MetaMaze 3-D closed-loop rollouts: per-env recurrent policies that read the rendered frame (csrc/maze3d_policy.hip). The
+ * reference has no such function; the numbers are defined here and by metamaze/policy.py (Maze3DPolicy.reference,
+ * Maze3DSteerPolicy.reference, pool_reference).
+ *
+ * Features. The frame of an env is F[h][v][c], h < res_h, v < res_v, c < 3, int32 or uint8 as mg_maze3d_step writes it
+ * (mg_maze_view.obs_format). A grid (Gh, Gv), 1 <= Gh, Gv <= 16, must divide the resolution: bh = res_h / Gh, bv = res_v / Gv.
+ *   S[gh][gv][c] = the sum of F[h][v][c] over gh*bh <= h < (gh+1)*bh, gv*bv <= v < (gv+1)*bv, modulo 2^32, read as int32
+ *   x[(gh*Gv + gv)*3 + c] = float32(S) * scale     (int -> float32 round to nearest even; one float32 product)
+ *   scale = (float)(1.0 / (255.0 * bh * bv)), computed by the caller in float64 and rounded once; the rollout refuses another.
+ * Inputs after the 3*Gh*Gv features:
+ *   discrete   (continuous == 0, K = 4, D = 3*Gh*Gv + 6): prev_action == k ? 1 : 0 for k = 0..3, prev_reward, prev_done ? 1 : 0
+ *   continuous (continuous != 0, K = 2, D = 3*Gh*Gv + 4): prev_action[0], prev_action[1], prev_reward, prev_done ? 1 : 0
+ * The network is mg_maze2d_policy_rollout's, operation for operation (float32, rounded once, never fused, 1 <= H <= 64):
+ *   for j in 0..H-1:  z = b[j];  for i in 0..D-1: z = z + wx[j][i] * x[i];  for i in 0..H-1: z = z + wh[j][i] * h[i]
+ *                     hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+ *   h = hn
+ *   for k in 0..K-1:  l[k] = bo[k];  for j in 0..H-1: l[k] = l[k] + wo[k][j] * h[j]
+ * Discrete: greedy = the lowest index of the largest logit (ties and NaN logits: the lowest index), and the exploration rule
+ * of mg_maze2d_policy_rollout with c3 = 0x4D33:
+ *   out = philox4x32_10(c0 = e, c1 = n & 0xFFFFFFFF, c2 = n >> 32, c3 = 0x4D33, k0 = seed & 0xFFFFFFFF, k1 = seed >> 32)
+ *   action = (out[0] < thr) ? (out[1] & 3) : greedy          (n = step0 + t; thr = 0 draws nothing)
+ * Continuous: a[k] = l[k] != l[k] ? 0 : (l[k] > 1 ? 1 : (l[k] < -1 ? -1 : l[k])); this value is stepped with, recorded and fed
+ * back as the previous action (the env's own clip is idempotent on it, so a replay through mg_maze3d_rollout is exact).
+ * After the step: prev_action = action, prev_reward = (float)reward, prev_done = done; episodic != 0 clears the carry at a done
+ * with auto_reset (h = 0, prev_action = -1 or (0, 0), prev_reward = 0, prev_done = 0).
+ *
+ * Packed parameters, DEVICE f32, 16-byte aligned, mg_maze3d_policy_param_count floats per policy, policy p at params + p * count.
+ * With HS = H rounded up to a multiple of 4 the block is j-minor (the 64 lanes of a wave, lane j owning hidden unit j, read one
+ * input's weights from consecutive addresses):
+ *   [0 .. K-1]                          bo[k], zeros up to [3]
+ *   [4 + j]                             b[j]
+ *   [4 + HS * (1 + i) + j]              wx[j][i], i < D
+ *   [4 + HS * (1 + D + i) + j]          wh[j][i], i < H
+ *   [4 + HS * (1 + D + H + k) + j]      wo[k][j], k < K
+ *   count = 4 + HS * (1 + D + H + K); entries with j >= H are zero and never read.
+ * Additive entry points; MG_ABI_VERSION is unchanged. */
+typedef struct mg_maze3d_policy {
+    int32_t n_policies, hidden, grid_h, grid_v, continuous;
+    float scale;                       /* (float)(1.0 / (255.0 * bh * bv)) */
+    const float *params;               /* DEVICE f32 [n_policies][count] */
+    const uint32_t *eps_threshold;     /* DEVICE u32 [n_policies], or NULL: no exploration (ignored by the continuous form) */
+} mg_maze3d_policy;
+
+/* Floats per packed policy (host only); a negative error code for hidden outside [1, 64] or a grid side outside [1, 16]. */
+int32_t mg_maze3d_policy_param_count(int32_t hidden, int32_t grid_h, int32_t grid_v, int32_t continuous);
+
+/* The pooling alone, one launch, one wave per env: out f32 [N][3*Gh*Gv] = x of the definition above for the N frames at
+ * `frame` (int32 or uint8 by view->obs_format; only res_h, res_v and obs_format of the view are read). Refused: NULL pointers,
+ * n_envs < 1, a grid side outside [1, 16] (MG_ERR_BAD_SIZE) or a grid that does not divide the resolution (MG_ERR_BAD_CONFIG).
+ * Nothing is allocated and nothing synchronises. */
+int mg_maze3d_pool_features(const mg_maze_view *view, int32_t n_envs, const void *frame, int32_t grid_h, int32_t grid_v,
+                            float scale, float *out, void *stream);
+
+/* The closed loop. First one render of the state the envs hold into `frame` (mg_maze3d_step's observe-only form: the call is
+ * right whatever `frame` held before), then per step one launch that pools the frame last rendered, evaluates env e's policy
+ * policy_ids[e] (i32 [N], clamped in the kernel) and runs mg_maze3d_expert_rollout's step body with the result, and one render:
+ * into the next slice of `obs` when obs != NULL and the step is one obs_every selects (as for mg_maze3d_rollout), else into
+ * `frame`. So the call makes n_steps + 1 renders and n_steps advance launches; with obs == NULL the last frame ends in `frame`.
+ * `frame` is the env's persistent [N][res_h][res_v][3] buffer (required); obs is [K] such buffers or NULL.
+ * carry: mg_maze_policy_carry, updated in place; in the continuous form its prev_action points at f32 [N][2] (a fresh one is
+ * zeros), in the discrete form at i32 [N] (-1 = none). Per env, all required: ret_total, ret_episode (f64 [N]), episode_len,
+ * episodes (i32 [N]) as for mg_maze3d_expert_rollout. Optional records, NULL = not written: actions (discrete i32 [n_steps][N],
+ * continuous f32 [n_steps][N][2]), reward f32, reward64 f64, done u8, each [n_steps][N].
+ * Refused before the first launch: NULL required pointers (MG_ERR_NULL_POINTER); n_steps or n_policies < 1, obs_every < 0,
+ * hidden outside [1, 64], a grid side outside [1, 16] (MG_ERR_BAD_SIZE); a grid that does not divide the resolution, params not
+ * 16-byte aligned, `continuous` not the policy's form, a scale that is not the defined one (MG_ERR_BAD_CONFIG); and whatever
+ * mg_maze3d_step refuses. Nothing is allocated and nothing synchronises: the call is hipGraph-capturable as it stands. */
+int mg_maze3d_policy_rollout(const mg_maze_tasks *tasks, const mg_maze_view *view, int32_t task_type, int32_t max_steps,
+                             int32_t continuous, int32_t auto_reset, int32_t n_envs, const mg_maze_state *state,
+                             int32_t n_steps, int32_t obs_every, const mg_maze3d_policy *policy, const int32_t *policy_ids,
+                             const mg_maze_policy_carry *carry, uint64_t seed, uint64_t step0, int32_t episodic, void *frame,
+                             void *obs, double *ret_total, double *ret_episode, int32_t *episode_len, int32_t *episodes,
+                             void *actions, float *reward, double *reward64, uint8_t *done, void *stream);
+
 /* ========================================================================================
  * MetaLocomotion walkers (humanoid / ant) — replaces, for N envs, WalkerBaseEnv.step
  * (metalocomotion/envs/utils/walker_base_env.py:43-82) including the physics the reference

@@ -136,6 +136,12 @@ class MazePolicyCarry(C.Structure):
     _fields_ = [("h", C.c_void_p), ("prev_action", C.c_void_p), ("prev_reward", C.c_void_p), ("prev_done", C.c_void_p)]
 
 
+class Maze3DPolicyDesc(C.Structure):
+    """mg_maze3d_policy (device pointers)"""
+    _fields_ = [("n_policies", C.c_int32), ("hidden", C.c_int32), ("grid_h", C.c_int32), ("grid_v", C.c_int32),
+                ("continuous", C.c_int32), ("scale", C.c_float), ("params", C.c_void_p), ("eps_threshold", C.c_void_p)]
+
+
 class MazeView(C.Structure):
     """mg_maze_view"""
     _fields_ = [("res_h", C.c_int32), ("res_v", C.c_int32), ("max_vision", C.c_double), ("l_focal", C.c_double),
@@ -423,6 +429,12 @@ SIGNATURES = {
     "mg_maze3d_expert_rollout": (C.c_int, [C.POINTER(MazeTasks), C.POINTER(MazeView), C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.POINTER(MazeState), C.c_int32, C.c_int32, _P, _P, _P, _P,
                                            _P, _P, _P, _P, _P, _P, _P]),
+    "mg_maze3d_policy_param_count": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mg_maze3d_pool_features": (C.c_int, [C.POINTER(MazeView), C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    "mg_maze3d_policy_rollout": (C.c_int, [C.POINTER(MazeTasks), C.POINTER(MazeView), C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.POINTER(MazeState), C.c_int32, C.c_int32,
+                                           C.POINTER(Maze3DPolicyDesc), _P, C.POINTER(MazePolicyCarry), C.c_uint64, C.c_uint64,
+                                           C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mg_walker_reset": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),
                                   C.c_int32, C.POINTER(WalkerState), _P, _P, _P, _P]),
     "mg_walker_step": (C.c_int, [C.POINTER(WalkerTopology), C.POINTER(WalkerModels), C.POINTER(WalkerParams),

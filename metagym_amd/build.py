@@ -33,7 +33,7 @@ FILE_FLAGS = {"quadrotor.hip": ["-fno-slp-vectorize"], "quadrotor_tasks.hip": ["
 # Sources a .hip includes besides the headers: its object is stale when one of them is newer.
 FILE_DEPS = {"quadrotor_tasks.hip": ["quadrotor.hip"], "quadrotor_policy.hip": ["quadrotor.hip"],
              "walker_policy.hip": ["walker.hip"], "walker_rpolicy.hip": ["walker.hip"], "maze_policy.hip": ["maze.hip"],
-             "maze_expert.hip": ["maze.hip"],
+             "maze_expert.hip": ["maze.hip"], "maze3d_policy.hip": ["maze.hip"],
              "bandits_policy.hip": ["bandits.hip"], "bandits_learner.hip": ["bandits.hip"], "liftsim_policy.hip": ["liftsim.hip"]}
 
 

@@ -3,8 +3,9 @@ meta-maze-discrete-3D-v0, meta-maze-continuous-3D-v0)."""
 from .expert import MazeDistanceField, distance_field_reference, expert_action_reference
 from .maze_env import MetaMaze2D, MetaMazeDiscrete3D, MetaMazeContinuous3D, rollout_obs_steps
 from .maze_task import MAZE_TASK_MANAGER, DeviceTaskTable, MazeTaskManager, MazeTaskSampler, TaskConfig
-from .policy import MazePolicy, MazePolicyRollout, MazePolicyState
+from .policy import Maze3DPolicy, Maze3DPolicyState, Maze3DSteerPolicy, MazePolicy, MazePolicyRollout, MazePolicyState
 
 __all__ = ["MetaMaze2D", "MetaMazeDiscrete3D", "MetaMazeContinuous3D", "MazeTaskSampler", "MazeTaskManager",
            "MAZE_TASK_MANAGER", "TaskConfig", "DeviceTaskTable", "rollout_obs_steps", "MazePolicy", "MazePolicyState",
-           "MazePolicyRollout", "MazeDistanceField", "distance_field_reference", "expert_action_reference"]
+           "MazePolicyRollout", "MazeDistanceField", "distance_field_reference", "expert_action_reference", "Maze3DPolicy",
+           "Maze3DSteerPolicy", "Maze3DPolicyState"]

@@ -563,6 +563,16 @@ class _Maze3D(_MazeBatch):
         self._obs = torch.zeros(self.num_envs, H, V, 3, dtype=obs_dtype, device=self.device)
         self._tex_version = None
 
+    def __getattr__(self, name):
+        # `env.rollout_policy` of a 3-D env is looked up here, on the env, and the 3-D classes carry no attribute of that
+        # name: the 2-D policy tests pin that `rollout_policy`, which there takes a `MazePolicy` on the window, is an attribute
+        # of the 2-D class alone (tests/test_maze_policy.py, tests/test_maze_policy_gpu.py: hasattr on the 3-D classes is
+        # False). The method itself, with its documentation, is `_rollout_policy_3d` of the env's class. No bound method is
+        # kept on the env, so the env stays free of reference cycles.
+        if name == "rollout_policy":
+            return self._rollout_policy_3d
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
     def _max_ray_records(self, min_cell_size):
         return 2 * int(self.max_vision_range / min_cell_size) + 5
 
@@ -674,6 +684,86 @@ class _Maze3D(_MazeBatch):
         _lib.check(rc, "mg_maze3d_expert_rollout")
         return res
 
+    _pooled = None
+
+    def pooled_observation(self, grid):
+        """The persistent frame buffer pooled over `grid` = (Gh, Gv), float32 [N, Gh, Gv, 3], one launch
+        (mg_maze3d_pool_features): the features a `Maze3DPolicy` reads (metamaze/policy.py `pool_reference` is the
+        definition, reproduced bit for bit), a cheap low-resolution observation for a policy kept in torch. The grid sides
+        are in [1, 16] and must divide the resolution. The output is a persistent buffer per grid, overwritten by the next
+        call with that grid; nothing synchronises, so `step` followed by `pooled_observation` can be captured in a hipGraph."""
+        from . import policy as mp
+        bh, bv = mp.check_grid_divides(grid, (self.resolution_horizon, self.resolution_vertical))
+        gh, gv = mp.check_grid(grid)
+        if self.need_set_task:
+            raise Exception("Must call \"set_task\" before pooled_observation")
+        if self._pooled is None:
+            self._pooled = {}
+        if (gh, gv) not in self._pooled:
+            self._pooled[(gh, gv)] = torch.zeros(self.num_envs, gh, gv, 3, dtype=torch.float32, device=self.device)
+        out = self._pooled[(gh, gv)]
+        rc = self._lib.mg_maze3d_pool_features(self._view_c, self.num_envs, _lib.ptr(self._obs), gh, gv, float(mp.pool_scale(bh, bv)),
+                                               _lib.ptr(out), _lib.current_stream(self.device))
+        _lib.check(rc, "mg_maze3d_pool_features")
+        return out
+
+    def _rollout_policy(self, policy, steps, policy_ids, state, seed, record, obs_every, episodic):
+        """`rollout_policy` of the two 3-D envs. Everything is checked before anything is written."""
+        from . import policy as mp
+        cls = mp.Maze3DSteerPolicy if self._CONTINUOUS else mp.Maze3DPolicy
+        if self.need_set_task:
+            raise Exception("Must call \"set_task\" before rollout_policy")
+        self._check_step()
+        if not isinstance(policy, cls):
+            raise TypeError("policy must be a %s, got %s" % (cls.__name__, type(policy).__name__))
+        T, N, dev, P, H = int(steps), self.num_envs, self.device, policy.num_policies, policy.hidden
+        if T < 1:
+            raise ValueError("steps must be at least 1, got %d" % T)
+        idx = rollout_obs_steps(T, obs_every)
+        bh, bv = mp.check_grid_divides(policy.grid, (self.resolution_horizon, self.resolution_vertical))
+        if self._CONTINUOUS:
+            if state is None:
+                state = mp.Maze3DPolicyState(N, H, dev)
+            else:
+                _policy.check_continuous_carry(state, mp.Maze3DPolicyState, N, H, 2, dev, "Maze3DPolicyState(N, H, device)",
+                                               "num_envs=%d, hidden=%d" % (N, H))
+            step0 = 0
+        else:
+            state, seed = _policy.check_discrete_carry(state, mp.MazePolicyState, N, H, T, seed, dev)
+            step0 = state.step
+        ids_d = _policy.policy_ids(self, policy_ids, P)
+        up = policy.to(dev)
+        params, thr = (up, None) if self._CONTINUOUS else up
+        if self._tex_version != MAZE_TASK_MANAGER.version:
+            self._build_view()
+        # everything is checked: from here on the env, the frame buffer and the new carry are written
+        fields = [v.to(dev).clone().contiguous() for v in (state.h, state.prev_action, state.prev_reward, state.prev_done)]
+        carry = mp.Maze3DPolicyState.of(*fields) if self._CONTINUOUS else mp.MazePolicyState(*fields, step=state.step + T)
+        desc = _lib.Maze3DPolicyDesc(P, H, policy.grid[0], policy.grid[1], int(self._CONTINUOUS), float(mp.pool_scale(bh, bv)),
+                                     params.data_ptr(), thr.data_ptr() if thr is not None else None)
+        carry_c = _lib.MazePolicyCarry(carry.h.data_ptr(), carry.prev_action.data_ptr(), carry.prev_reward.data_ptr(),
+                                       carry.prev_done.data_ptr())
+        obs = self._obs if int(obs_every) == 0 else torch.empty((len(idx),) + tuple(self._obs.shape), dtype=self._obs.dtype,
+                                                                 device=dev)
+        res = mp.MazePolicyRollout(torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
+                                   torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+                                   carry, obs, idx)
+        if record:
+            res.actions = (torch.empty(T, N, 2, dtype=torch.float32, device=dev) if self._CONTINUOUS
+                           else torch.empty(T, N, dtype=torch.int32, device=dev))
+            res.reward = torch.empty(T, N, dtype=torch.float32, device=dev)
+            res.reward64 = torch.empty(T, N, dtype=torch.float64, device=dev)
+            res.done = torch.empty(T, N, dtype=torch.bool, device=dev)
+        rc = self._lib.mg_maze3d_policy_rollout(self._tasks_c, self._view_c, self._tt, self.max_steps, int(self._CONTINUOUS),
+                                                int(self.auto_reset), N, self._state_c, T, int(obs_every), desc, _lib.ptr(ids_d),
+                                                carry_c, seed, step0, int(bool(episodic)), _lib.ptr(self._obs),
+                                                _lib.ptr(obs) if int(obs_every) > 0 else None, _lib.ptr(res.ret_total),
+                                                _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len), _lib.ptr(res.episodes),
+                                                _lib.ptr(res.actions), _lib.ptr(res.reward), _lib.ptr(res.reward64),
+                                                _lib.ptr(res.done), _lib.current_stream(dev))
+        _lib.check(rc, "mg_maze3d_policy_rollout")
+        return res
+
 
 class MetaMazeDiscrete3D(_Maze3D):
     """maze_env.py:16-83. action int in {0..3}: turn left / right, step back / forward."""
@@ -684,6 +774,25 @@ class MetaMazeDiscrete3D(_Maze3D):
         self.action_space = Discrete(4)
 
     _FIELD_KIND = 2       # expert.TURNS
+
+    def _rollout_policy_3d(self, policy, steps, policy_ids=None, state=None, seed=0, record=False, obs_every=0, episodic=False):
+        """`steps` closed-loop env steps with the controller inside the launches (mg_maze3d_policy_rollout): env e pools the
+        frame of the state it holds over the policy's grid, evaluates policy `policy_ids[e]` of `policy` (a `Maze3DPolicy`;
+        None = e % P) on the features, its previous action, reward and done, and steps with the result (metamaze/policy.py
+        defines the arithmetic exactly; `Maze3DPolicy.reference` is the oracle). One render of the current state first (so
+        the call is right after `load_state_dict`, whatever the frame buffer holds), then one advance launch and one render
+        per step. `state` is the carry of the previous call (a `MazePolicyState`; None = a fresh one); it is not written, the
+        end carry comes back as `.state` with `step` advanced by `steps`. `seed` keys the exploration draws of a policy with
+        epsilon. With `auto_reset` the memory survives a done; `episodic=True` clears the carry at a done instead. Returns a
+        `MazePolicyRollout` as `MetaMaze2D.rollout_policy` does: ret_total, ret_episode, episode_len, episodes and state
+        always; actions int32, reward, reward64, done [steps, N] when `record=True`, else None; obs and obs_steps as in
+        `demonstrate` (obs_every == 0: the persistent buffer with the last frame; k >= 1: a fresh [K, N, H, V, 3] tensor, the
+        persistent buffer then holds the last frame that was not kept). Replaying the recorded actions through `rollout`
+        gives the same records, frames and end state bit for bit. Nothing synchronises (`policy_ids` as for
+        `MetaMaze2D.rollout_policy`). A refused call (another policy class, a grid that does not divide the resolution, a
+        carry of another N or H, an id out of range, steps < 1, obs_every < 0, a call before set_task or reset) raises and
+        leaves the env, the carry and the frame buffer as they were."""
+        return self._rollout_policy(policy, steps, policy_ids, state, seed, record, obs_every, episodic)
 
     def _observe(self):
         self._launch(None, False)
@@ -716,6 +825,13 @@ class MetaMazeContinuous3D(_Maze3D):
             raise ValueError("rollout actions must be float32 [T, num_envs = %d, 2] with T >= 1, got %s"
                              % (self.num_envs, tuple(a.shape)))
         return a.contiguous()
+
+    def _rollout_policy_3d(self, policy, steps, policy_ids=None, state=None, record=False, obs_every=0, episodic=False):
+        """`env.rollout_policy` of the discrete 3-D maze (`MetaMazeDiscrete3D._rollout_policy_3d`) for the continuous maze: `policy` is a `Maze3DSteerPolicy`, whose two outputs,
+        NaN -> 0 and clamped to [-1, 1], are (turn, walk): that value is stepped with, recorded (actions float32
+        [steps, N, 2]) and fed back as the previous action. No exploration, so no seed. `state` is a `Maze3DPolicyState`
+        (None = a fresh one); it is not written, the end carry comes back as `.state`."""
+        return self._rollout_policy(policy, steps, policy_ids, state, 0, record, obs_every, episodic)
 
     def _observe(self):
         self._launch(None, True)

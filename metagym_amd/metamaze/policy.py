@@ -30,7 +30,7 @@ action = (out[0] < thr) ? (out[1] & 3) : greedy.
 """
 import numpy as np
 
-from .._policy import PackedPolicySet, check_epsilon, eps_threshold, f32_array, philox4x32_10, to_numpy  # noqa: F401
+from .._policy import ContinuousPolicyState, PackedPolicySet, check_epsilon, eps_threshold, f32_array, philox4x32_10, to_numpy  # noqa: F401
 
 MAX_HIDDEN = 64
 VIEW_GRIDS = (1, 2, 3)
@@ -229,3 +229,261 @@ class MazePolicyRollout(object):
         self.ret_total, self.ret_episode, self.episode_len, self.episodes = ret_total, ret_episode, episode_len, episodes
         self.state, self.obs, self.obs_steps = state, obs, obs_steps
         self.actions, self.reward, self.reward64, self.done = actions, reward, reward64, done
+
+
+# ------------------------------------------------------------------------------------------------ the 3-D mazes
+# The policies of the 3-D mazes read the rendered frame (include/metagym_hip.h, mg_maze3d_policy_rollout). The frame
+# F[h][v][c] (int32 or uint8, as `step` returns it) is pooled over a grid (Gh, Gv) that divides the resolution, bh = res_h / Gh,
+# bv = res_v / Gv: S[gh][gv][c] is the sum of the block modulo 2^32 read as int32, x[(gh * Gv + gv) * 3 + c] = float32(S) * scale
+# with scale = np.float32(1.0 / (255 * bh * bv)). After the 3 * Gh * Gv features come, discrete: the one-hot of the previous
+# action, the previous reward and done (D = 3 Gh Gv + 6); continuous: the two previous actions as recorded, the previous reward
+# and done (D = 3 Gh Gv + 4). The network is the one above with K = 4 logits or K = 2 steering outputs
+# a[k] = l[k] != l[k] ? 0 : clamp(l[k], -1, 1); the discrete exploration draw uses c3 = 0x4D33.
+MAX_GRID = 16
+PHILOX_TAG_3D = 0x4D33       # c3 of the 3-D exploration draw
+
+
+def check_grid(grid):
+    """(Gh, Gv) as two ints in [1, 16]."""
+    try:
+        gh, gv = grid
+    except (TypeError, ValueError):
+        raise ValueError("grid must be a pair (Gh, Gv), got %r" % (grid,))
+    if int(gh) != gh or int(gv) != gv or not (1 <= gh <= MAX_GRID and 1 <= gv <= MAX_GRID):
+        raise ValueError("grid sides must be integers in [1, %d], got %r" % (MAX_GRID, grid))
+    return int(gh), int(gv)
+
+
+def check_grid_divides(grid, resolution):
+    """(bh, bv) of a grid on frames of `resolution` = (res_h, res_v); ValueError when it does not divide them."""
+    gh, gv = check_grid(grid)
+    res_h, res_v = int(resolution[0]), int(resolution[1])
+    if res_h < 1 or res_v < 1 or res_h % gh or res_v % gv:
+        raise ValueError("grid %d x %d does not divide the resolution %d x %d" % (gh, gv, res_h, res_v))
+    return res_h // gh, res_v // gv
+
+
+def pool_scale(bh, bv):
+    """np.float32(1.0 / (255 * bh * bv)): what the kernel multiplies a block sum with."""
+    return np.float32(1.0 / (255 * int(bh) * int(bv)))
+
+
+def pool_reference(frames, grid):
+    """The features of [N, res_h, res_v, 3] int32 or uint8 frames: float32 [N, Gh, Gv, 3], block sums modulo 2^32 read as
+    int32, converted to float32 (round to nearest even) and multiplied by `pool_scale(bh, bv)`."""
+    f = to_numpy(frames)
+    if f.ndim != 4 or f.shape[3] != 3 or f.dtype not in (np.dtype(np.int32), np.dtype(np.uint8)):
+        raise ValueError("frames must be int32 or uint8 [N, res_h, res_v, 3], got %s %s" % (f.dtype, f.shape))
+    gh, gv = check_grid(grid)
+    bh, bv = check_grid_divides(grid, f.shape[1:3])
+    N = f.shape[0]
+    s = f.astype(np.int64).reshape(N, gh, bh, gv, bv, 3).sum(axis=(2, 4))         # exact: at most 2^16 terms below 2^32
+    s = (s & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+    return s.astype(np.float32) * pool_scale(bh, bv)
+
+
+def _input_dim_3d(grid, continuous):
+    return 3 * grid[0] * grid[1] + (4 if continuous else 6)
+
+
+def param_count_3d(hidden, grid, continuous):
+    """Floats per packed 3-D policy (what mg_maze3d_policy_param_count returns)."""
+    if not (1 <= int(hidden) <= MAX_HIDDEN):
+        raise ValueError("hidden units must be in [1, %d], got %r" % (MAX_HIDDEN, hidden))
+    gh, gv = check_grid(grid)
+    H, K = int(hidden), 2 if continuous else 4
+    return 4 + ((H + 3) & ~3) * (1 + _input_dim_3d((gh, gv), continuous) + H + K)
+
+
+class Maze3DPolicyState(ContinuousPolicyState):
+    """The carry of `MetaMazeContinuous3D.rollout_policy` (`ContinuousPolicyState` with A = 2): h float32 [N, H], prev_action
+    float32 [N, 2] (the actions as recorded), prev_reward float32 [N], prev_done uint8 [N]. `Maze3DPolicyState(num_envs,
+    hidden, device)` is the fresh carry, all zero; device None gives numpy arrays, for `Maze3DSteerPolicy.reference`."""
+    __slots__ = ("h", "prev_action", "prev_reward", "prev_done")
+
+    def __init__(self, num_envs, hidden, device=None):
+        N, H = int(num_envs), int(hidden)
+        if N < 1 or not (1 <= H <= MAX_HIDDEN):
+            raise ValueError("a carry needs num_envs >= 1 and hidden in [1, %d], got %d and %d" % (MAX_HIDDEN, N, H))
+        self.h, self.prev_action, self.prev_reward, self.prev_done = self._zero_arrays(N, H, 2, device)
+
+
+class _Maze3DPolicyBase(PackedPolicySet):
+    """What the two 3-D policy classes share: the shapes, the packed layout and the network on a batch."""
+    CONTINUOUS = False
+
+    def _init(self, wx, wh, b, wo, bo, grid):
+        K = 2 if self.CONTINUOUS else 4
+        wx, wh, b = f32_array("wx", wx, 3), f32_array("wh", wh, 3), f32_array("b", b, 2)
+        wo, bo = f32_array("wo", wo, 3), f32_array("bo", bo, 2)
+        gh, gv = check_grid(grid)
+        P, H, D = wx.shape
+        if P < 1:
+            raise ValueError("a policy set needs at least one policy")
+        if not (1 <= H <= MAX_HIDDEN):
+            raise ValueError("hidden units must be in [1, %d], got %d" % (MAX_HIDDEN, H))
+        if D != _input_dim_3d((gh, gv), self.CONTINUOUS):
+            raise ValueError("grid %d x %d gives %d inputs, wx has %d" % (gh, gv, _input_dim_3d((gh, gv), self.CONTINUOUS), D))
+        if wh.shape != (P, H, H) or b.shape != (P, H) or wo.shape != (P, K, H) or bo.shape != (P, K):
+            raise ValueError("shapes must be wx [P,H,D], wh [P,H,H], b [P,H], wo [P,%d,H], bo [P,%d]; got %s %s %s %s %s"
+                             % (K, K, wx.shape, wh.shape, b.shape, wo.shape, bo.shape))
+        self.wx, self.wh, self.b, self.wo, self.bo = wx, wh, b, wo, bo
+        self.num_policies, self.hidden, self.input_dim, self.grid, self.n_out = P, H, D, (gh, gv), K
+
+    @property
+    def param_count(self):
+        return param_count_3d(self.hidden, self.grid, self.CONTINUOUS)
+
+    def pack(self):
+        """float32 [P, param_count]: the j-minor layout the kernel reads (written out in include/metagym_hip.h). With HS = H
+        rounded up to a multiple of 4: bo[0..K-1] and zeros up to 4, then rows of HS floats: b, wx[:, 0] .. wx[:, D-1],
+        wh[:, 0] .. wh[:, H-1], wo[0] .. wo[K-1]; entries j >= H are zero."""
+        P, H, D, K = self.num_policies, self.hidden, self.input_dim, self.n_out
+        HS = (H + 3) & ~3
+        out = np.zeros((P, self.param_count), np.float32)
+        out[:, :K] = self.bo
+        rows = out[:, 4:].reshape(P, 1 + D + H + K, HS)
+        rows[:, 0, :H] = self.b
+        rows[:, 1:1 + D, :H] = self.wx.transpose(0, 2, 1)
+        rows[:, 1 + D:1 + D + H, :H] = self.wh.transpose(0, 2, 1)
+        rows[:, 1 + D + H:, :H] = self.wo
+        return out
+
+    @classmethod
+    def _unpack(cls, packed, hidden, grid):
+        packed = f32_array("packed", packed, 2)
+        gh, gv = check_grid(grid)
+        P, H, K = packed.shape[0], int(hidden), 2 if cls.CONTINUOUS else 4
+        D = _input_dim_3d((gh, gv), cls.CONTINUOUS)
+        if packed.shape[1] != param_count_3d(H, (gh, gv), cls.CONTINUOUS):
+            raise ValueError("packed has shape %s, hidden=%d and grid=%s need [P, %d]"
+                             % (packed.shape, H, (gh, gv), param_count_3d(H, (gh, gv), cls.CONTINUOUS)))
+        HS = (H + 3) & ~3
+        rows = packed[:, 4:].reshape(P, 1 + D + H + K, HS)
+        return (rows[:, 1:1 + D, :H].transpose(0, 2, 1).copy(), rows[:, 1 + D:1 + D + H, :H].transpose(0, 2, 1).copy(),
+                rows[:, 0, :H].copy(), rows[:, 1 + D + H:, :H].copy(), packed[:, :K].copy())
+
+    def _features(self, frames, N):
+        f = to_numpy(frames)
+        if f.ndim != 4 or f.shape[0] != N:
+            raise ValueError("frames must be [N = %d, res_h, res_v, 3], got %s" % (N, f.shape))
+        return pool_reference(f, self.grid).reshape(N, -1)
+
+    def _network(self, x, ids, h):
+        """(hn [N, H], l [N, K]) of the definition, numpy float32 with exactly its association."""
+        N, D = x.shape
+        H, K = self.hidden, self.n_out
+        assert D == self.input_dim and x.dtype == np.float32
+        wx, wh, b, wo, bo = self.wx[ids], self.wh[ids], self.b[ids], self.wo[ids], self.bo[ids]
+        one = np.float32(1.0)
+        hn = np.empty((N, H), np.float32)
+        with np.errstate(all="ignore"):
+            for j in range(H):
+                z = b[:, j].copy()
+                for i in range(D):
+                    z = z + wx[:, j, i] * x[:, i]
+                for i in range(H):
+                    z = z + wh[:, j, i] * h[:, i]
+                hn[:, j] = np.where(z > one, one, np.where(z < -one, -one, z))
+            out = bo.copy()                                  # [N, K]
+            for j in range(H):
+                out = out + wo[:, :, j] * hn[:, j:j + 1]
+        assert hn.dtype == np.float32 and out.dtype == np.float32
+        return hn, out
+
+    def _check_batch(self, policy_ids, state, prev_action_shape):
+        ids = to_numpy(policy_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("policy_ids must be [N] integers")
+        N, P, H = ids.shape[0], self.num_policies, self.hidden
+        if N and (int(ids.min()) < 0 or int(ids.max()) >= P):
+            raise ValueError("policy_ids must be in [0, %d)" % P)
+        h = to_numpy(state.h)
+        pa, pr, pd = to_numpy(state.prev_action), to_numpy(state.prev_reward), to_numpy(state.prev_done)
+        if h.shape != (N, H) or h.dtype != np.float32:
+            raise ValueError("state.h must be float32 [%d, %d], got %s %s" % (N, H, h.dtype, h.shape))
+        if pa.shape != (N,) + prev_action_shape or pr.shape != (N,) or pd.shape != (N,) or pr.dtype != np.float32:
+            raise ValueError("state.prev_action %s / prev_reward (float32) / prev_done must have %d rows" % (prev_action_shape, N))
+        return ids, h, pa, pr, pd
+
+
+class Maze3DPolicy(_Maze3DPolicyBase):
+    """P recurrent policies of the discrete 3-D maze: wx [P, H, D], wh [P, H, H], b [P, H], wo [P, 4, H], bo [P, 4], all
+    float32 and finite; grid = (Gh, Gv), sides in [1, 16], D = 3 Gh Gv + 6; epsilon float64 [P] in [0, 1] or None (no
+    exploration). 1 <= H <= 64. The carry is a `MazePolicyState`."""
+    CONTINUOUS = False
+
+    def __init__(self, wx, wh, b, wo, bo, grid, epsilon=None):
+        self._init(wx, wh, b, wo, bo, grid)
+        self.epsilon = None if epsilon is None else check_epsilon(epsilon, self.num_policies)
+
+    @classmethod
+    def unpack(cls, packed, hidden, grid, epsilon=None):
+        """The inverse of `pack`."""
+        return cls(*cls._unpack(packed, hidden, grid), grid=grid, epsilon=epsilon)
+
+    def _host(self):
+        return self.pack(), self._threshold_bits()
+
+    def reference(self, frames, policy_ids, state, seed=0, env_ids=None, return_explored=False):
+        """One step of the definition in numpy. frames: int32 or uint8 [N, res_h, res_v, 3], the frames of the states the envs
+        hold; policy_ids [N]; state: a `MazePolicyState` (read, not written); env e draws with counter c0 = env_ids[e]
+        (default e). Returns (actions int32 [N], next h float32 [N, H]), with `return_explored` also the bool [N] mask of
+        the exploratory draws."""
+        ids, h, pa, pr, pd = self._check_batch(policy_ids, state, ())
+        N, D = ids.shape[0], self.input_dim
+        x = np.zeros((N, D), np.float32)
+        x[:, :D - 6] = self._features(frames, N)
+        for k in range(4):
+            x[:, D - 6 + k] = (pa == k).astype(np.float32)
+        x[:, D - 2] = pr
+        x[:, D - 1] = (pd != 0).astype(np.float32)
+        hn, logits = self._network(x, ids, h)
+        greedy = np.zeros(N, np.int32)
+        best = logits[:, 0].copy()
+        with np.errstate(all="ignore"):
+            for k in range(1, 4):
+                better = logits[:, k] > best
+                greedy = np.where(better, np.int32(k), greedy)
+                best = np.where(better, logits[:, k], best)
+        thr = self.thresholds[ids]
+        e = np.arange(N, dtype=np.uint64) if env_ids is None else to_numpy(env_ids).astype(np.uint64)
+        n, s = int(state.step), int(seed)
+        out = philox4x32_10(e, n & 0xFFFFFFFF, (n >> 32) & 0xFFFFFFFF, PHILOX_TAG_3D, s & 0xFFFFFFFF, (s >> 32) & 0xFFFFFFFF)
+        explored = out[0] < thr
+        actions = np.where(explored, (out[1] & np.uint32(3)).astype(np.int32), greedy).astype(np.int32)
+        return (actions, hn, explored) if return_explored else (actions, hn)
+
+
+class Maze3DSteerPolicy(_Maze3DPolicyBase):
+    """P recurrent policies of the continuous 3-D maze: wx [P, H, D], wh [P, H, H], b [P, H], wo [P, 2, H], bo [P, 2], all
+    float32 and finite; grid = (Gh, Gv), sides in [1, 16], D = 3 Gh Gv + 4; no exploration. 1 <= H <= 64. The carry is a
+    `Maze3DPolicyState`."""
+    CONTINUOUS = True
+    epsilon = None
+
+    def __init__(self, wx, wh, b, wo, bo, grid):
+        self._init(wx, wh, b, wo, bo, grid)
+
+    @classmethod
+    def unpack(cls, packed, hidden, grid):
+        """The inverse of `pack`."""
+        return cls(*cls._unpack(packed, hidden, grid), grid=grid)
+
+    def reference(self, frames, policy_ids, state):
+        """One step of the definition in numpy. frames: int32 or uint8 [N, res_h, res_v, 3]; policy_ids [N]; state: a
+        `Maze3DPolicyState` (read, not written). Returns (actions float32 [N, 2] = (turn, walk), next h float32 [N, H])."""
+        ids, h, pa, pr, pd = self._check_batch(policy_ids, state, (2,))
+        if pa.dtype != np.float32:
+            raise ValueError("state.prev_action must be float32, got %s" % pa.dtype)
+        N, D = ids.shape[0], self.input_dim
+        x = np.zeros((N, D), np.float32)
+        x[:, :D - 4] = self._features(frames, N)
+        x[:, D - 4:D - 2] = pa
+        x[:, D - 2] = pr
+        x[:, D - 1] = (pd != 0).astype(np.float32)
+        hn, out = self._network(x, ids, h)
+        one = np.float32(1.0)
+        with np.errstate(all="ignore"):
+            a = np.where(out != out, np.float32(0.0), np.where(out > one, one, np.where(out < -one, -one, out)))
+        return a.astype(np.float32), hn
