@@ -21,12 +21,13 @@
 #define MG_LIFTSIM_CORE_ONLY
 #include "liftsim.hip"
 
+#include "mg_closed_loop.h"
+
 namespace {
 
 constexpr int LP_MAX_HIDDEN = 64;
-constexpr size_t LP_LDS_LIMIT = 160 * 1024;      // gfx950: LDS per CU, the most one workgroup can have
 
-typedef float lp_v4f __attribute__((ext_vector_type(4)));
+typedef mg::v4f lp_v4f;
 
 __host__ __device__ constexpr int lp_pad4(int n) { return (n + 3) & ~3; }
 // floats of one hidden unit's record: b[j] 0 0 0 | ws[j][0..7] | we[j][0..E-1] | wt[j][0..F] | wr[j][0..F-1] | wu | wd,
@@ -232,16 +233,10 @@ __global__ __launch_bounds__(64) void liftsim_policy_rollout_kernel(K k, Lay l, 
 
     // The env's policy, clamped. One id in the whole wave (a ballot: wave-uniform) and room for it: stage it in LDS once.
     const int count = lp_count(H, k.F, k.E);
-    int pid = pa.ids[ec];
-    pid = pid < 0 ? 0 : (pid >= pa.n_policies ? pa.n_policies - 1 : pid);
-    const int pid0 = __builtin_amdgcn_readfirstlane(pid);
-    const bool staged = stage != 0 && __builtin_amdgcn_ballot_w64(pid != pid0) == 0;
-    const float *__restrict__ own = pa.params + (size_t)pid * (size_t)count;
-    if (staged) {
-        const lp_v4f *src = reinterpret_cast<const lp_v4f *>(pa.params + (size_t)pid0 * (size_t)count);
-        lp_v4f *dst = reinterpret_cast<lp_v4f *>(smem + lds.policy);
-        for (int i = lane; i < count / 4; i += 64) dst[i] = src[i];
-    }
+    const mg::StagedPolicy sp = mg::stage_policy(pa.params, count, pa.ids[ec], pa.n_policies, lane, stage != 0,
+                                                 reinterpret_cast<lp_v4f *>(smem + lds.policy));
+    const bool staged = sp.staged;
+    const float *__restrict__ own = sp.own;
     __syncthreads();                                                       // (one wave) the staged policy is in place
 
     const size_t A = (size_t)(2 * k.E);
@@ -305,14 +300,10 @@ extern "C" int mg_liftsim_policy_rollout(const mg_liftsim_config *cfg, int32_t n
     if (((uintptr_t)policy->params & 15u) != 0)
         return mg::set_error(MG_ERR_BAD_CONFIG, "mg_liftsim_policy.params must be 16-byte aligned");
     // launch-uniform: the policy is staged when the whole need fits a workgroup's LDS; the rest always fits (< 27 KiB)
-    const bool stage = (size_t)lp_lds_layout(policy->hidden, cfg->floors, cfg->elevators, true).bytes <= LP_LDS_LIMIT;
+    const bool stage = (size_t)lp_lds_layout(policy->hidden, cfg->floors, cfg->elevators, true).bytes <= mg::LDS_LIMIT;
     const LpLds lds = lp_lds_layout(policy->hidden, cfg->floors, cfg->elevators, stage);
     mg::DeviceGuard guard(mg::device_of(arena));
-    if (lds.bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(liftsim_policy_rollout_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes);
-        if (e != hipSuccess) return mg::check_hip(e, "hipFuncSetAttribute(liftsim_policy_rollout_kernel)");
-    }
+    if (int rc = mg::opt_in_dynamic_lds(liftsim_policy_rollout_kernel, lds.bytes, "liftsim_policy_rollout_kernel")) return rc;
     LpPolicy pa{policy->params, policy_ids, policy->n_policies, policy->hidden, {}};
     for (int i = 0; i < 8; ++i) pa.scale[i] = policy->scale[i];
     const Records rec{ret, rec_reward, rec_time_consume, rec_energy_consume, rec_given_up, rec_actions};

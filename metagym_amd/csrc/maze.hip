@@ -225,39 +225,87 @@ __device__ __forceinline__ void eval_cells(const Task &t, const mg_maze_state &s
 }
 
 // ------------------------------------------------------------------------------------------------
-// MetaMaze2D: one lane per env
+// one env step: what every kernel that steps shares
 // ------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(MZ_BLOCK) void maze2d_step_kernel(mg_maze_tasks T, mg_maze_state st, int task_type,
-                                                               int max_steps, int vg, int auto_reset, int n_envs,
-                                                               const int32_t *action, float *obs, float *reward,
-                                                               double *reward64, uint8_t *done) {
-    const int e = blockIdx.x * MZ_BLOCK + threadIdx.x;
-    if (e >= n_envs) return;
-    const Task t = load_task(T, st.task_id[e]);
-    Agent a = load_agent(st, n_envs, e);
-    if (action != nullptr) {
-        const int act = action[e] & 3;
-        // DISCRETE_ACTIONS maze_env.py:14 = [(-1,0),(1,0),(0,-1),(0,1)]; maze_2d.py:24-29
-        const int ti = a.gx + (act == 0 ? -1 : (act == 1 ? 1 : 0));
-        const int tj = a.gy + (act == 2 ? -1 : (act == 3 ? 1 : 0));
-        const int wi = ti < 0 ? ti + t.n : ti, wj = tj < 0 ? tj + t.n : tj;   // python negative index
-        if (wi < t.n && wj < t.n && t.walls[wi * t.n + wj] < 1) { a.gx = ti; a.gy = tj; }
-        double r;
-        int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
-        if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);
-        if (reward) reward[e] = (float)r;
-        if (reward64) reward64[e] = r;
-        done[e] = (uint8_t)d;
-        if (d && auto_reset) {
-            reset_agent(t, task_type, a);
-            if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
+// MazeCore2D.do_action maze_2d.py:24-29
+__device__ __forceinline__ void move_2d(const Task &t, int act, Agent &a) {
+    // DISCRETE_ACTIONS maze_env.py:14 = [(-1,0),(1,0),(0,-1),(0,1)]
+    const int ti = a.gx + (act == 0 ? -1 : (act == 1 ? 1 : 0));
+    const int tj = a.gy + (act == 2 ? -1 : (act == 3 ? 1 : 0));
+    const int wi = ti < 0 ? ti + t.n : ti, wj = tj < 0 ? tj + t.n : tj;   // python negative index
+    if (wi < t.n && wj < t.n && t.walls[wi * t.n + wj] < 1) { a.gx = ti; a.gy = tj; }
+}
+
+struct RolloutOut {                         // the per-env results of a closed-loop launch
+    float *obs_last;                        // [n][w][w] (2-D only)
+    double *ret_total, *ret_episode;        // [n]
+    int32_t *episode_len, *episodes;        // [n]
+};
+struct RolloutRec {                         // [T][n] each, obs [K][n][w][w] (2-D only); each may be null
+    void *actions;                          // int32, or float32 [T][n][2] for the continuous maze
+    float *reward;
+    double *reward64;
+    uint8_t *done;
+    float *obs;
+};
+
+// The returns of a launch: float64 sums in step order; the episode's stops with the first done ("the episode has ended" is
+// episodes > 0). A kernel that steps a stretch of a rollout picks them up from `po` and leaves them there.
+struct Returns {
+    double ret_total = 0.0, ret_episode = 0.0;
+    int episode_len = 0, episodes = 0;
+    __device__ __forceinline__ void add(double r, int d) {
+        ret_total = ret_total + r;
+        if (episodes == 0) {
+            ret_episode = ret_episode + r;
+            episode_len += 1;
         }
-        store_agent(st, n_envs, e, a);
+        episodes += d;
     }
-    // update_observation maze_2d.py:89-121
+    __device__ __forceinline__ void load(const RolloutOut &po, int e) {
+        ret_total = po.ret_total[e];
+        ret_episode = po.ret_episode[e];
+        episode_len = po.episode_len[e];
+        episodes = po.episodes[e];
+    }
+    __device__ __forceinline__ void store(const RolloutOut &po, int e) const {
+        po.ret_total[e] = ret_total;
+        po.ret_episode[e] = ret_episode;
+        po.episode_len[e] = episode_len;
+        po.episodes[e] = episodes;
+    }
+};
+
+// The step after the move, by the lane that owns env e alone: evaluation_rule (maze_base.py:65-95), the records that are asked
+// for at index `at`, and the auto-reset. reset_agent writes only the Agent in registers; reset_cells(..., false) reads only the
+// task and writes only the SURVIVAL arrays: the two commute, and this is the one order. Returns done, the reward in `r`.
+__device__ __forceinline__ int step_tail(const Task &t, const mg_maze_state &st, int e, int task_type, int max_steps,
+                                         int auto_reset, Agent &a, size_t at, float *reward, double *reward64, uint8_t *done,
+                                         double &r) {
+    const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
+    if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);          // :83-88
+    if (reward) reward[at] = (float)r;
+    if (reward64) reward64[at] = r;
+    if (done) done[at] = (uint8_t)d;
+    if (d && auto_reset) {
+        reset_agent(t, task_type, a);
+        if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
+    }
+    return d;
+}
+
+// Which steps of a rollout leave an observation: obs_every = 0 the last one only, k >= 1 the steps t with (t + 1) % k == 0 and
+// always the last one (metamaze/maze_env.py rollout_obs_steps restates the rule for the host).
+__host__ __device__ __forceinline__ bool rollout_records(int t, int n_steps, int obs_every) {
+    return t == n_steps - 1 || (obs_every > 0 && (t + 1) % obs_every == 0);
+}
+
+// update_observation maze_2d.py:89-121; `put(i, v)` receives window entry i.
+template <class Put>
+__device__ __forceinline__ void observe_2d(const Task &t, const mg_maze_state &st, int e, int task_type, int vg, const Agent &a,
+                                           Put &&put) {
     const int w = 2 * vg + 1;
-    float *o = obs + (size_t)e * w * w;
     for (int p = 0; p < w; ++p)
         for (int q = 0; q < w; ++q) {
             const int x = a.gx - vg + p, y = a.gy - vg + q;
@@ -276,9 +324,31 @@ __global__ __launch_bounds__(MZ_BLOCK) void maze2d_step_kernel(mg_maze_tasks T, 
                 }
                 else v = (float)((double)v + ((x == t.gx && y == t.gy) ? 1.0 : 0.0));       // :120
             }
-            o[p * w + q] = v;
+            if (task_type == MG_MAZE_SURVIVAL && p == vg && q == vg) v = (float)a.life;     // :118
+            put(p * w + q, v);
         }
-    if (task_type == MG_MAZE_SURVIVAL) o[vg * w + vg] = (float)a.life;                      // :118
+}
+
+// ------------------------------------------------------------------------------------------------
+// MetaMaze2D: one lane per env
+// ------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(MZ_BLOCK) void maze2d_step_kernel(mg_maze_tasks T, mg_maze_state st, int task_type,
+                                                               int max_steps, int vg, int auto_reset, int n_envs,
+                                                               const int32_t *action, float *obs, float *reward,
+                                                               double *reward64, uint8_t *done) {
+    const int e = blockIdx.x * MZ_BLOCK + threadIdx.x;
+    if (e >= n_envs) return;
+    const Task t = load_task(T, st.task_id[e]);
+    Agent a = load_agent(st, n_envs, e);
+    if (action != nullptr) {
+        move_2d(t, action[e] & 3, a);
+        double r;
+        step_tail(t, st, e, task_type, max_steps, auto_reset, a, (size_t)e, reward, reward64, done, r);
+        store_agent(st, n_envs, e, a);
+    }
+    float *o = obs + (size_t)e * (2 * vg + 1) * (2 * vg + 1);
+    observe_2d(t, st, e, task_type, vg, a, [&](int i, float v) { o[i] = v; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1078,41 +1148,9 @@ __global__ __launch_bounds__(MZ_BLOCK) void maze_cont_move_kernel(mg_maze_tasks 
 // rollouts: T steps per call (mg_maze2d_rollout, mg_maze3d_rollout)
 // ------------------------------------------------------------------------------------------------
 
-// Which steps of a rollout leave an observation: obs_every = 0 the last one only, k >= 1 the steps t with (t + 1) % k == 0 and
-// always the last one (metamaze/maze_env.py rollout_obs_steps restates the rule for the host).
-__host__ __device__ __forceinline__ bool rollout_records(int t, int n_steps, int obs_every) {
-    return t == n_steps - 1 || (obs_every > 0 && (t + 1) % obs_every == 0);
-}
-
-// update_observation maze_2d.py:89-121, value by value as maze2d_step_kernel computes it; `put(i, v)` receives window entry i.
-template <class Put>
-__device__ __forceinline__ void observe_2d(const Task &t, const mg_maze_state &st, int e, int task_type, int vg, const Agent &a,
-                                           Put &&put) {
-    const int w = 2 * vg + 1;
-    for (int p = 0; p < w; ++p)
-        for (int q = 0; q < w; ++q) {
-            const int x = a.gx - vg + p, y = a.gy - vg + q;
-            float v = -1.0f;
-            if (x >= 0 && x < t.n && y >= 0 && y < t.n) {
-                v = (float)(-(int)t.walls[x * t.n + y]);                                   // :113
-                if (task_type == MG_MAZE_SURVIVAL) {                                       // :117
-                    double food;
-                    if (st.food_by_slot) {
-                        const int k = t.cell_slot[x * t.n + y];
-                        food = k >= 0 ? st.cur_food[fidx(st, e, k)] : (k == -1 ? 0.0 : t.food[x * t.n + y]);
-                    } else food = st.cur_food[fidx(st, e, x * t.n + y)];
-                    v = (float)((double)v + food);
-                }
-                else v = (float)((double)v + ((x == t.gx && y == t.gy) ? 1.0 : 0.0));       // :120
-            }
-            if (task_type == MG_MAZE_SURVIVAL && p == vg && q == vg) v = (float)a.life;     // :118
-            put(p * w + q, v);
-        }
-}
-
 // MetaMaze2D.step (maze_env.py:189-204 -> maze_2d.py:21-34 + maze_base.py:65-95) n_steps times, one lane per env, one wave per
-// workgroup. Task and agent stay in registers for the whole call; the SURVIVAL cells go through the same eval_scalar /
-// eval_cells / reset_cells as the step kernel (a lane only ever reads its own writes). STAGE: the 64 windows of the wave are
+// workgroup. Task and agent stay in registers for the whole call; a step is the step kernel's move_2d and step_tail (a lane
+// only ever reads its own writes to the SURVIVAL cells). STAGE: the 64 windows of the wave are
 // written to LDS lane-major (lane * w*w + i; w*w is odd, so the 32 lanes of a ds_write_b32 group fall on 32 different banks) and
 // leave as one contiguous run of 64 * w*w floats, 256 bytes per store instruction; !STAGE keeps the step kernel's per-lane
 // store (one dword per lane at a stride of w*w floats) for windows too large for LDS.
@@ -1139,22 +1177,9 @@ __global__ __launch_bounds__(MZ_ROLL_BLOCK) void maze2d_rollout_kernel(mg_maze_t
     for (int s = 0; s < n_steps; ++s) {
         const size_t rec = (size_t)s * n_envs + el;
         if (live) {
-            const int act = actions[rec] & 3;
-            // DISCRETE_ACTIONS maze_env.py:14 = [(-1,0),(1,0),(0,-1),(0,1)]; maze_2d.py:24-29
-            const int ti = a.gx + (act == 0 ? -1 : (act == 1 ? 1 : 0));
-            const int tj = a.gy + (act == 2 ? -1 : (act == 3 ? 1 : 0));
-            const int wi = ti < 0 ? ti + t.n : ti, wj = tj < 0 ? tj + t.n : tj;   // python negative index
-            if (wi < t.n && wj < t.n && t.walls[wi * t.n + wj] < 1) { a.gx = ti; a.gy = tj; }
+            move_2d(t, actions[rec] & 3, a);
             double r;
-            const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
-            if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);
-            if (reward) reward[rec] = (float)r;
-            if (reward64) reward64[rec] = r;
-            done[rec] = (uint8_t)d;
-            if (d && auto_reset) {
-                reset_agent(t, task_type, a);
-                if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
-            }
+            step_tail(t, st, e, task_type, max_steps, auto_reset, a, rec, reward, reward64, done, r);
         }
         if (!rollout_records(s, n_steps, obs_every)) continue;               // (uniform: every lane is at step s)
         if (STAGE) {
@@ -1179,9 +1204,9 @@ __global__ __launch_bounds__(MZ_ROLL_BLOCK) void maze2d_rollout_kernel(mg_maze_t
 // The part of a 3-D maze step that is not the picture — MazeCoreDiscrete3D.turn / move (maze_discrete_3d.py:51-72) or
 // MazeCoreContinuous3D.do_action (maze_continuous_3d.py:47-56 -> dynamics.py:59-92), then evaluation_rule (maze_base.py:65-95)
 // and the auto-reset — for the steps s0 .. s1-1 of a rollout, one lane per env like maze_cont_move_kernel, the agent in
-// registers for the stretch. The same device functions in the same order as phase 0 of maze3d_step_kernel; there the 256
-// threads of an env share its cells, here the lane sweeps them alone (the sweeps touch disjoint cells, so the order among
-// cells does not matter). The SURVIVAL arrays are read through the strides of mg_maze_state: [N][n*n] for the 3-D envs, i.e.
+// registers for the stretch: the transition, then step_tail written out. Phase 0 of maze3d_step_kernel calls the same functions;
+// there the 256 threads of an env share its cells, here the lane sweeps them alone (the sweeps touch disjoint cells, so the
+// order among cells does not matter). The SURVIVAL arrays are read through the strides of mg_maze_state: [N][n*n] for the 3-D envs, i.e.
 // lane e at e * n*n + c — one line per lane per access, a handful of accesses per step with the food-cell list.
 __global__ __launch_bounds__(MZ_BLOCK) void maze3d_advance_kernel(mg_maze_tasks T, mg_maze_state st, double col_dist,
                                                                   int task_type, int max_steps, int continuous,
@@ -1200,6 +1225,7 @@ __global__ __launch_bounds__(MZ_BLOCK) void maze3d_advance_kernel(mg_maze_tasks 
         } else {
             transition_discrete(t, static_cast<const int32_t *>(actions)[rec] & 3, a);
         }
+        // step_tail, written out: through the helper this kernel measured 0.3 - 0.5 % slower than before
         double r;
         const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
         if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);      // :83-88

@@ -2,8 +2,7 @@
 // (mg_maze3d_policy_param_count, mg_maze3d_pool_features, mg_maze3d_policy_rollout).
 //
 // A translation unit of its own, like maze_policy.hip and maze_expert.hip and for the same reason: it takes maze.hip's device
-// functions (load_task, load_agent, transition_discrete, transition_continuous, eval_scalar, eval_cells, reset_cells,
-// reset_agent, rollout_records) by including it with MG_MAZE_CORE_ONLY, so the step, rollout and render kernels are compiled
+// functions (load_task, load_agent, transition_discrete, transition_continuous, step_tail, Returns, rollout_records) by including it with MG_MAZE_CORE_ONLY, so the step, rollout and render kernels are compiled
 // from the text they were compiled from before. Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes the
 // policy definition of include/metagym_hip.h hold (one rounding per operation).
 //
@@ -23,11 +22,11 @@
 //   hidden    lane j < H owns unit j and walks the D + H inputs in ascending order; the weights are packed j-minor, so the
 //             wave's read of one input's H weights is one coalesced line, served by L2 for every env after the first.
 //   outputs   lanes k < K (4 logits or 2 steering outputs) walk j in ascending order.
-//   env step  lane 0 runs maze3d_expert_advance_kernel's step body in its order with the action taken from the outputs.
+//   env step  lane 0 runs maze3d_advance_kernel's step (the transition, step_tail) with the action taken from the outputs.
 #define MG_MAZE_CORE_ONLY
 #include "maze.hip"
 
-#include "mg_philox.h"
+#include "mg_closed_loop.h"
 
 namespace {
 
@@ -65,16 +64,6 @@ struct M3Policy {
     const uint32_t *__restrict__ thr;             // [n_policies] or null (no exploration)
     const int32_t *__restrict__ ids;              // [n]
     int n_policies, hidden;
-};
-struct M3Out {
-    double *ret_total, *ret_episode;              // [n]
-    int32_t *episode_len, *episodes;              // [n]
-};
-struct M3Rec {                                    // [T][n] each (continuous actions [T][n][2]); each may be null
-    void *actions;
-    float *reward;
-    double *reward64;
-    uint8_t *done;
 };
 
 // what one lane wrote to the wave's LDS is there for the others (one wave: no s_barrier)
@@ -204,17 +193,15 @@ __global__ __launch_bounds__(M3_BLOCK) void maze3d_pool_kernel(int n_envs, M3Fra
     for (int i = lane; i < nf; i += mg::WAVE) out[(size_t)e * nf + i] = __int_as_float(bins[wave][i]);
 }
 
-__device__ __forceinline__ int m3_clamp_task(int tid, int n_tasks) { return tid < 0 ? 0 : (tid >= n_tasks ? n_tasks - 1 : tid); }
-
 // Step s of a closed-loop rollout for every env: the policy on the frame `frame` holds (the frame of the state the env is
-// in), then maze3d_expert_advance_kernel's step body in its order. The returns travel from launch to launch through `po`
-// (step 0 begins them; "the episode has ended" is episodes > 0), the policy's memory through `ca`.
+// in), then maze3d_advance_kernel's step (the transition, step_tail). The returns travel from launch to launch through `po`
+// (step 0 begins them: Returns), the policy's memory through `ca`.
 template <bool CONT, typename E>
 __global__ __launch_bounds__(M3_BLOCK) void maze3d_policy_advance_kernel(mg_maze_tasks T, mg_maze_state st, double col_dist,
                                                                          int task_type, int max_steps, int auto_reset, int n_envs,
                                                                          int s, M3Frame fr, const E *__restrict__ frame,
                                                                          M3Policy pa, mg_maze_policy_carry ca, uint64_t seed,
-                                                                         uint64_t step0, int episodic, M3Out po, M3Rec rec) {
+                                                                         uint64_t step0, int episodic, RolloutOut po, RolloutRec rec) {
     __shared__ M3Wave lds[M3_WAVES];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int e = blockIdx.x * M3_WAVES + wave;
@@ -227,8 +214,7 @@ __global__ __launch_bounds__(M3_BLOCK) void maze3d_policy_advance_kernel(mg_maze
     // The env's policy id, clamped, and its carry are asked for before the pooling, so these round trips run under it. The
     // task row and the agent are not: some thirty live values across the pooling and the hidden layer cost two waves per
     // SIMD, and the kernel is bound by latency inside a wave, where occupancy is what hides it.
-    int pid = pa.ids[e];
-    pid = pid < 0 ? 0 : (pid >= pa.n_policies ? pa.n_policies - 1 : pid);
+    const int pid = mg::clamp_index(pa.ids[e], pa.n_policies);
     const float *__restrict__ p = pa.params + (size_t)pid * (size_t)m3_count(H, D, K);
     const uint32_t thr = (!CONT && pa.thr != nullptr) ? pa.thr[pid] : 0u;
     float *prev_cont = static_cast<float *>(static_cast<void *>(ca.prev_action)) + 2 * (size_t)e;   // CONT: f32 [N][2]
@@ -272,7 +258,7 @@ __global__ __launch_bounds__(M3_BLOCK) void maze3d_policy_advance_kernel(mg_maze
     m3_wave_sync();
 
     if (lane == 0) {
-        const Task t = load_task(T, m3_clamp_task(st.task_id[e], T.n_tasks));
+        const Task t = load_task(T, mg::clamp_index(st.task_id[e], T.n_tasks));
         Agent a = load_agent(st, n_envs, e);
         const size_t r_at = (size_t)s * n_envs + e;
         int act = 0;
@@ -292,45 +278,18 @@ __global__ __launch_bounds__(M3_BLOCK) void maze3d_policy_advance_kernel(mg_maze
             if (w.out[1] > best) { act = 1; best = w.out[1]; }
             if (w.out[2] > best) { act = 2; best = w.out[2]; }
             if (w.out[3] > best) { act = 3; }
-            if (thr != 0u) {
-                const uint64_t n = step0 + (uint64_t)s;
-                uint32_t o[4];
-                philox4x32_10((uint32_t)e, (uint32_t)n, (uint32_t)(n >> 32), M3_PHILOX_TAG, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-                if (o[0] < thr) act = (int)(o[1] & 3u);
-            }
+            uint32_t word;
+            if (mg::explore_draw((uint32_t)e, step0 + (uint64_t)s, M3_PHILOX_TAG, seed, thr, word)) act = (int)(word & 3u);
             if (rec.actions) static_cast<int32_t *>(rec.actions)[r_at] = act;
             transition_discrete(t, act, a);
         }
         double r;
-        const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
-        if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);
-        if (rec.reward) rec.reward[r_at] = (float)r;
-        if (rec.reward64) rec.reward64[r_at] = r;
-        if (rec.done) rec.done[r_at] = (uint8_t)d;
-        if (d && auto_reset) {
-            if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
-            reset_agent(t, task_type, a);
-        }
-        // the returns: float64 sums in step order; the episode's stops with the first done
-        double ret_total = 0.0, ret_episode = 0.0;
-        int episode_len = 0, episodes = 0;
-        if (s > 0) {
-            ret_total = po.ret_total[e];
-            ret_episode = po.ret_episode[e];
-            episode_len = po.episode_len[e];
-            episodes = po.episodes[e];
-        }
-        ret_total = ret_total + r;
-        if (episodes == 0) {
-            ret_episode = ret_episode + r;
-            episode_len += 1;
-        }
-        episodes += d;
+        const int d = step_tail(t, st, e, task_type, max_steps, auto_reset, a, r_at, rec.reward, rec.reward64, rec.done, r);
+        Returns ret;
+        if (s > 0) ret.load(po, e);
+        ret.add(r, d);
         store_agent(st, n_envs, e, a);
-        po.ret_total[e] = ret_total;
-        po.ret_episode[e] = ret_episode;
-        po.episode_len[e] = episode_len;
-        po.episodes[e] = episodes;
+        ret.store(po, e);
         // the carry: the action as it was stepped with, the reward as the record holds it
         const bool clear = episodic && d && auto_reset;                    // the next episode starts from a fresh carry
         if (CONT) {
@@ -437,8 +396,8 @@ extern "C" int mg_maze3d_policy_rollout(const mg_maze_tasks *T, const mg_maze_vi
     const size_t frame_bytes = (size_t)n * view->res_h * view->res_v * 3 * (view->obs_format == 1 ? 1 : sizeof(int32_t));
     unsigned char *slice = static_cast<unsigned char *>(obs);
     const M3Policy pa{policy->params, policy->eps_threshold, policy_ids, policy->n_policies, policy->hidden};
-    const M3Out po{ret_total, ret_episode, episode_len, episodes};
-    const M3Rec rec{actions, reward, reward64, done};
+    const RolloutOut po{nullptr, ret_total, ret_episode, episode_len, episodes};
+    const RolloutRec rec{actions, reward, reward64, done, nullptr};
     const dim3 grid((unsigned)((n + M3_WAVES - 1) / M3_WAVES)), block(M3_BLOCK);
     const bool u8 = view->obs_format == 1;
     // the frame of the state the envs hold now: the buffer may be stale (load_state_dict, a rollout that kept slices)

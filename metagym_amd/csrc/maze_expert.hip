@@ -2,9 +2,8 @@
 // mg_maze_expert_action, mg_maze2d_expert_rollout, mg_maze_steer_action, mg_maze3d_expert_rollout).
 //
 // A translation unit of its own, like maze_policy.hip and for the same reason: it takes maze.hip's device functions
-// (load_task, load_agent, transition_discrete, eval_scalar, eval_cells, reset_cells, reset_agent, observe_2d, rollout_records)
-// and host checks by including it with MG_MAZE_CORE_ONLY, so the step and rollout kernels are compiled from the text they were
-// compiled from before. Same flags (metagym_amd/build.py).
+// (load_task, load_agent, transition_discrete, move_2d, step_tail, eval_scalar, eval_cells, reset_cells, reset_agent, Returns,
+// observe_2d, rollout_records) and host checks by including it with MG_MAZE_CORE_ONLY. Same flags (metagym_amd/build.py).
 //
 // The field. dist[t][k][c] is the length of the shortest action sequence that takes state (k, c) of task t onto a source cell
 // under the step's own passability rule (include/metagym_hip.h states the three rules). One workgroup per task runs a
@@ -19,8 +18,8 @@
 // lane ever meets a stale vector-L1 line). No workgroup talks to another.
 //
 // The expert. One lane per env looks at the (at most four) successors of the env's state under the step's own rule and takes
-// the lowest action whose successor is one step nearer; mg_maze2d_expert_rollout is maze2d_rollout_kernel's step body in its
-// order with the action load replaced by that choice.
+// the lowest action whose successor is one step nearer; mg_maze2d_expert_rollout is maze2d_rollout_kernel's step (move_2d,
+// step_tail) with the action load replaced by that choice.
 //
 // The 3-D demonstrations (mg_maze_steer_action, mg_maze3d_expert_rollout). The continuous maze's expert steers: towards the
 // centre of the first neighbour cell one step nearer in a CELLS_3D field, walking inside a +-9 degree dead band and turning
@@ -30,11 +29,12 @@
 #define MG_MAZE_CORE_ONLY
 #include "maze.hip"
 
+#include "mg_closed_loop.h"
+
 namespace {
 
 constexpr int ME_BLOCK = 256;                    // threads of a field workgroup
 constexpr int ME_QUEUE_CAP = 2048;               // states one level's queue holds (mg_maze_distance_queue_capacity)
-constexpr size_t ME_LDS_LIMIT = 160 * 1024;      // gfx950: LDS per CU, the most one workgroup can have
 constexpr int ME_ROLL_BLOCK = mg::WAVE;
 
 __host__ __device__ constexpr int me_orientations(int kind) { return kind == MG_MAZE_FIELD_TURNS ? 4 : 1; }
@@ -48,7 +48,7 @@ __host__ __device__ inline MeLds me_lds_layout(int states) {
     l.queue0 = 16;
     l.queue1 = l.queue0 + ME_QUEUE_CAP * (int)sizeof(int32_t);
     l.field = l.queue1 + ME_QUEUE_CAP * (int)sizeof(int32_t);
-    l.field_in_lds = (size_t)l.field + (size_t)states * sizeof(int32_t) <= ME_LDS_LIMIT;
+    l.field_in_lds = (size_t)l.field + (size_t)states * sizeof(int32_t) <= mg::LDS_LIMIT;
     l.bytes = l.field + (l.field_in_lds ? states * (int)sizeof(int32_t) : 0);
     return l;
 }
@@ -193,76 +193,40 @@ __device__ __forceinline__ int me_expert_pick(const Task &t, int kind, const int
     return d0 > 0 ? best : 0;
 }
 
-__device__ __forceinline__ int me_clamp_task(int tid, int n_tasks) { return tid < 0 ? 0 : (tid >= n_tasks ? n_tasks - 1 : tid); }
-
 __global__ __launch_bounds__(ME_BLOCK) void maze_expert_action_kernel(mg_maze_tasks T, int kind, const int32_t *dist, int n_envs,
                                                                       mg_maze_state st, int32_t *action) {
     const int e = blockIdx.x * ME_BLOCK + threadIdx.x;
     if (e >= n_envs) return;
-    const int tid = me_clamp_task(st.task_id[e], T.n_tasks);
+    const int tid = mg::clamp_index(st.task_id[e], T.n_tasks);
     const Task t = load_task(T, tid);
     const int32_t *field = dist + (size_t)tid * me_orientations(kind) * t.nn;
     action[e] = me_expert_pick(t, kind, field, st.grid[e], st.grid[n_envs + e], st.ori_idx ? st.ori_idx[e] : 0);
 }
 
-struct MeOut {
-    float *obs_last;                        // [n][w][w]
-    double *ret_total, *ret_episode;        // [n]
-    int32_t *episode_len, *episodes;        // [n]
-};
-struct MeRec {                              // [T][n] each, obs [K][n][w][w]; each may be null
-    int32_t *actions;
-    float *reward;
-    double *reward64;
-    uint8_t *done;
-    float *obs;
-};
-
-// maze2d_rollout_kernel's step body in its order, one lane per env, one wave per workgroup, the action chosen from the field
+// maze2d_rollout_kernel's step (move_2d, step_tail), one lane per env, one wave per workgroup, the action chosen from the field
 // on the state the lane holds. Inside the step loop the kernel stores only what `rec` asks for.
 __global__ __launch_bounds__(ME_ROLL_BLOCK) void maze2d_expert_rollout_kernel(mg_maze_tasks T, mg_maze_state st, int task_type,
                                                                               int max_steps, int vg, int auto_reset, int n_envs,
                                                                               int n_steps, int obs_every, const int32_t *dist,
-                                                                              MeOut po, MeRec rec) {
+                                                                              RolloutOut po, RolloutRec rec) {
     const int e = blockIdx.x * ME_ROLL_BLOCK + threadIdx.x;
     if (e >= n_envs) return;
-    const int tid = me_clamp_task(st.task_id[e], T.n_tasks);
+    const int tid = mg::clamp_index(st.task_id[e], T.n_tasks);
     const Task t = load_task(T, tid);
     const int32_t *field = dist + (size_t)tid * t.nn;
     Agent a = load_agent(st, n_envs, e);
     const int ww = (2 * vg + 1) * (2 * vg + 1);
     const size_t slice = (size_t)n_envs * ww;
     float *out = rec.obs;
-    double ret_total = 0.0, ret_episode = 0.0;
-    int episode_len = 0, episodes = 0;
-    bool ended = false;
+    Returns ret;
     for (int s = 0; s < n_steps; ++s) {
         const size_t r_at = (size_t)s * n_envs + e;
         const int act = me_expert_pick(t, MG_MAZE_FIELD_MOVES_2D, field, a.gx, a.gy, 0);
-        if (rec.actions) rec.actions[r_at] = act;
-        // DISCRETE_ACTIONS maze_env.py:14 = [(-1,0),(1,0),(0,-1),(0,1)]; maze_2d.py:24-29
-        const int ti = a.gx + (act == 0 ? -1 : (act == 1 ? 1 : 0));
-        const int tj = a.gy + (act == 2 ? -1 : (act == 3 ? 1 : 0));
-        const int wi = ti < 0 ? ti + t.n : ti, wj = tj < 0 ? tj + t.n : tj;   // python negative index
-        if (wi < t.n && wj < t.n && t.walls[wi * t.n + wj] < 1) { a.gx = ti; a.gy = tj; }
+        if (rec.actions) static_cast<int32_t *>(rec.actions)[r_at] = act;
+        move_2d(t, act, a);
         double r;
-        const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
-        if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);
-        if (rec.reward) rec.reward[r_at] = (float)r;
-        if (rec.reward64) rec.reward64[r_at] = r;
-        if (rec.done) rec.done[r_at] = (uint8_t)d;
-        if (d && auto_reset) {
-            reset_agent(t, task_type, a);
-            if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
-        }
-        // the returns: float64 sums in step order; the episode's stops with the first done
-        ret_total = ret_total + r;
-        if (!ended) {
-            ret_episode = ret_episode + r;
-            episode_len += 1;
-            ended = d != 0;
-        }
-        episodes += d;
+        const int d = step_tail(t, st, e, task_type, max_steps, auto_reset, a, r_at, rec.reward, rec.reward64, rec.done, r);
+        ret.add(r, d);
         if (out == nullptr || !rollout_records(s, n_steps, obs_every)) continue;
         float *o = out + (size_t)e * ww;
         observe_2d(t, st, e, task_type, vg, a, [&](int i, float v) { o[i] = v; });
@@ -271,10 +235,7 @@ __global__ __launch_bounds__(ME_ROLL_BLOCK) void maze2d_expert_rollout_kernel(mg
     store_agent(st, n_envs, e, a);
     float *o = po.obs_last + (size_t)e * ww;
     observe_2d(t, st, e, task_type, vg, a, [&](int i, float v) { o[i] = v; });
-    po.ret_total[e] = ret_total;
-    po.ret_episode[e] = ret_episode;
-    po.episode_len[e] = episode_len;
-    po.episodes[e] = episodes;
+    ret.store(po, e);
 }
 
 // The steering expert's action in the state `a` holds (include/metagym_hip.h states the rule; metamaze/expert.py
@@ -316,7 +277,7 @@ __global__ __launch_bounds__(ME_BLOCK) void maze_steer_action_kernel(mg_maze_tas
                                                                      mg_maze_state st, float *action) {
     const int e = blockIdx.x * ME_BLOCK + threadIdx.x;
     if (e >= n_envs) return;
-    const int tid = me_clamp_task(st.task_id[e], T.n_tasks);
+    const int tid = mg::clamp_index(st.task_id[e], T.n_tasks);
     const Task t = load_task(T, tid);
     Agent a;
     a.gx = st.grid[e];
@@ -341,7 +302,8 @@ struct Me3Rec {                             // [T][n] each (continuous actions [
     uint8_t *done;
 };
 
-// maze3d_advance_kernel's body in its order for the steps s0 .. s1-1 of a demonstration, one lane per env, one wave per
+// maze3d_advance_kernel's body in its order (step_tail and Returns written out: through the helpers the continuous form
+// measured 1.6 % slower than before) for the steps s0 .. s1-1 of a demonstration, one lane per env, one wave per
 // workgroup, the agent in registers, the action chosen from the field on the state the lane holds. The returns travel from
 // stretch to stretch through `po`: the stretch that starts at step 0 begins them, a later one picks them up; "the episode has
 // ended" is episodes > 0. Inside the step loop the kernel stores only what `rec` asks for.
@@ -352,7 +314,7 @@ __global__ __launch_bounds__(ME_ROLL_BLOCK) void maze3d_expert_advance_kernel(mg
                                                                               Me3Out po, Me3Rec rec) {
     const int e = blockIdx.x * ME_ROLL_BLOCK + threadIdx.x;
     if (e >= n_envs) return;
-    const int tid = me_clamp_task(st.task_id[e], T.n_tasks);
+    const int tid = mg::clamp_index(st.task_id[e], T.n_tasks);
     const Task t = load_task(T, tid);
     const int32_t *field = dist + (size_t)tid * (CONT ? 1 : 4) * t.nn;
     Agent a = load_agent(st, n_envs, e);
@@ -423,10 +385,7 @@ extern "C" int mg_maze_distance_field(const mg_maze_tasks *T, int32_t kind, cons
     const MeLds lds = me_lds_layout(me_orientations(kind) * T->n * T->n);
     const auto kernel = lds.field_in_lds ? maze_distance_field_kernel<true> : maze_distance_field_kernel<false>;
     mg::DeviceGuard guard(mg::device_of(dist));
-    if (lds.bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes);
-        if (e != hipSuccess) return mg::check_hip(e, "hipFuncSetAttribute(maze_distance_field_kernel)");
-    }
+    if (int rc = mg::opt_in_dynamic_lds(kernel, lds.bytes, "maze_distance_field_kernel")) return rc;
     hipLaunchKernelGGL(kernel, dim3((unsigned)T->n_tasks), dim3(ME_BLOCK), (size_t)lds.bytes, (hipStream_t)stream, *T, kind, sources,
                        dist);
     return mg::check_launch("maze_distance_field_kernel");
@@ -473,8 +432,8 @@ extern "C" int mg_maze2d_expert_rollout(const mg_maze_tasks *T, int32_t task_typ
     if (int rc = check_mstate(st, task_type)) return rc;
     if (int rc = check_slots(T, st, task_type)) return rc;
     mg::DeviceGuard guard(mg::device_of(st->grid));
-    MeOut po{obs_last, ret_total, ret_episode, episode_len, episodes};
-    MeRec rec{actions, reward, reward64, done, obs};
+    RolloutOut po{obs_last, ret_total, ret_episode, episode_len, episodes};
+    RolloutRec rec{actions, reward, reward64, done, obs};
     hipLaunchKernelGGL(maze2d_expert_rollout_kernel, dim3((unsigned)((n + ME_ROLL_BLOCK - 1) / ME_ROLL_BLOCK)), dim3(ME_ROLL_BLOCK),
                        0, (hipStream_t)stream, *T, *st, task_type, max_steps, view_grid, auto_reset, n, n_steps, obs_every, dist, po,
                        rec);

@@ -1,8 +1,8 @@
 // maze_policy.hip — MetaMaze 2-D closed-loop rollouts: per-env recurrent policies inside the launch (mg_maze2d_policy_*).
 //
 // A translation unit of its own, like quadrotor_policy.hip and walker_policy.hip and for the same reason: it takes maze.hip's
-// device functions (load_task, load_agent, eval_scalar, eval_cells, reset_cells, reset_agent, observe_2d, rollout_records)
-// and host checks by including it with MG_MAZE_CORE_ONLY, so the step and rollout kernels are compiled from the text they
+// device functions (load_task, load_agent, move_2d, step_tail, Returns, observe_2d, rollout_records) and host checks by
+// including it with MG_MAZE_CORE_ONLY, so the step and rollout kernels are compiled from the text they
 // were compiled from before. Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes the policy definition
 // of include/metagym_hip.h hold (one rounding per operation).
 //
@@ -16,16 +16,15 @@
 #define MG_MAZE_CORE_ONLY
 #include "maze.hip"
 
-#include "mg_philox.h"
+#include "mg_closed_loop.h"
 
 namespace {
 
 constexpr int MP_BLOCK = mg::WAVE;
 constexpr int MP_MAX_HIDDEN = 64;
-constexpr size_t MP_LDS_LIMIT = 160 * 1024;      // gfx950: LDS per CU, the most one workgroup can have
 constexpr uint32_t MP_PHILOX_TAG = 0x4D5Au;      // c3 of the exploration draw
 
-typedef float mp_v4f __attribute__((ext_vector_type(4)));
+typedef mg::v4f mp_v4f;
 
 __host__ __device__ constexpr int mp_input_dim(int vg) { return (2 * vg + 1) * (2 * vg + 1) + 6; }
 __host__ __device__ constexpr int mp_hidden_pad(int hidden) { return (hidden + 3) & ~3; }
@@ -53,18 +52,6 @@ struct MpPolicy {
     const uint32_t *__restrict__ thr;       // [n_policies] or null (no exploration)
     const int32_t *__restrict__ ids;        // [n]
     int n_policies, hidden;
-};
-struct MpOut {
-    float *obs_last;                        // [n][w][w]
-    double *ret_total, *ret_episode;        // [n]
-    int32_t *episode_len, *episodes;        // [n]
-};
-struct MpRec {                              // [T][n] each, obs [K][n][w][w]; each may be null
-    int32_t *actions;
-    float *reward;
-    double *reward64;
-    uint8_t *done;
-    float *obs;
 };
 
 // The policy of include/metagym_hip.h on one packed parameter block, from LDS (every lane the same address: broadcast reads)
@@ -112,7 +99,7 @@ __device__ __forceinline__ int policy_eval(const float *__restrict__ p, int hidd
     return g;
 }
 
-// maze2d_rollout_kernel's step body in its order, with the action load replaced by the policy. x is computed from the state
+// maze2d_rollout_kernel's step (move_2d, step_tail) with the action load replaced by the policy. x is computed from the state
 // the lane holds (observe_2d into registers) before the loop and after every step: the observation buffer is never read.
 // Inside the step loop the kernel stores only what `rec` asks for; the agent, the carry, the four per-env results and the
 // last window go out once, at the end.
@@ -120,8 +107,8 @@ template <int VG>
 __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze_tasks T, mg_maze_state st, int task_type,
                                                                          int max_steps, int auto_reset, int n_envs, int n_steps,
                                                                          int obs_every, MpPolicy pa, mg_maze_policy_carry ca,
-                                                                         uint64_t seed, uint64_t step0, int episodic, MpOut po,
-                                                                         MpRec rec) {
+                                                                         uint64_t seed, uint64_t step0, int episodic, RolloutOut po,
+                                                                         RolloutRec rec) {
     constexpr int W = 2 * VG + 1, WW = W * W, D = WW + 6;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int H = pa.hidden;
@@ -138,17 +125,11 @@ __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze
 
     // The env's policy, clamped. One id in the whole wave (a ballot: wave-uniform): stage it in LDS once.
     const int count = mp_count(H, D);
-    int pid = pa.ids[el];
-    pid = pid < 0 ? 0 : (pid >= pa.n_policies ? pa.n_policies - 1 : pid);
-    const int pid0 = __builtin_amdgcn_readfirstlane(pid);
-    const bool staged = __builtin_amdgcn_ballot_w64(pid != pid0) == 0;
-    const float *__restrict__ own = pa.params + (size_t)pid * (size_t)count;
-    if (staged) {
-        const mp_v4f *src = reinterpret_cast<const mp_v4f *>(pa.params + (size_t)pid0 * (size_t)count);
-        mp_v4f *dst = reinterpret_cast<mp_v4f *>(smem + lds.policy);
-        for (int i = lane; i < count / 4; i += MP_BLOCK) dst[i] = src[i];
-    }
-    const uint32_t thr = pa.thr != nullptr ? pa.thr[pid] : 0u;
+    const mg::StagedPolicy sp = mg::stage_policy(pa.params, count, pa.ids[el], pa.n_policies, lane, true,
+                                                 reinterpret_cast<mp_v4f *>(smem + lds.policy));
+    const bool staged = sp.staged;
+    const float *__restrict__ own = sp.own;
+    const uint32_t thr = pa.thr != nullptr ? pa.thr[sp.pid] : 0u;
 
     const Task t = load_task(T, st.task_id[el]);
     Agent a = load_agent(st, n_envs, el);
@@ -160,9 +141,7 @@ __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze
 
     float x[D];
     observe_2d(t, st, el, task_type, VG, a, [&](int i, float v) { x[i] = v; });
-    double ret_total = 0.0, ret_episode = 0.0;
-    int episode_len = 0, episodes = 0;
-    bool ended = false;
+    Returns ret;
     const int run = min(MP_BLOCK, n_envs - e0) * WW;                       // floats this wave owns in a slice of obs
     const size_t slice = (size_t)n_envs * WW;
     float *out = rec.obs;
@@ -174,38 +153,15 @@ __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze
         x[WW + 5] = prev_done ? 1.0f : 0.0f;
         int act = staged ? policy_eval<D>(policy_lds, H, x, hc, hx) : policy_eval<D>(own, H, x, hc, hx);
         { float *sw = hc; hc = hx; hx = sw; }                              // h = hn
-        if (thr != 0u) {
-            const uint64_t n = step0 + (uint64_t)s;
-            uint32_t o[4];
-            philox4x32_10((uint32_t)el, (uint32_t)n, (uint32_t)(n >> 32), MP_PHILOX_TAG, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-            if (o[0] < thr) act = (int)(o[1] & 3u);
-        }
+        uint32_t word;
+        if (mg::explore_draw((uint32_t)el, step0 + (uint64_t)s, MP_PHILOX_TAG, seed, thr, word)) act = (int)(word & 3u);
         if (live) {
             const size_t r_at = (size_t)s * n_envs + e;
-            if (rec.actions) rec.actions[r_at] = act;
-            // DISCRETE_ACTIONS maze_env.py:14 = [(-1,0),(1,0),(0,-1),(0,1)]; maze_2d.py:24-29
-            const int ti = a.gx + (act == 0 ? -1 : (act == 1 ? 1 : 0));
-            const int tj = a.gy + (act == 2 ? -1 : (act == 3 ? 1 : 0));
-            const int wi = ti < 0 ? ti + t.n : ti, wj = tj < 0 ? tj + t.n : tj;   // python negative index
-            if (wi < t.n && wj < t.n && t.walls[wi * t.n + wj] < 1) { a.gx = ti; a.gy = tj; }
+            if (rec.actions) static_cast<int32_t *>(rec.actions)[r_at] = act;
+            move_2d(t, act, a);
             double r;
-            const int d = eval_scalar(t, st, e, task_type, max_steps, a, r);
-            if (task_type == MG_MAZE_SURVIVAL) eval_cells(t, st, e, 0, 1);
-            if (rec.reward) rec.reward[r_at] = (float)r;
-            if (rec.reward64) rec.reward64[r_at] = r;
-            if (rec.done) rec.done[r_at] = (uint8_t)d;
-            if (d && auto_reset) {
-                reset_agent(t, task_type, a);
-                if (task_type == MG_MAZE_SURVIVAL) reset_cells(t, st, e, 0, 1, false);
-            }
-            // the returns: float64 sums in step order; the episode's stops with the first done
-            ret_total = ret_total + r;
-            if (!ended) {
-                ret_episode = ret_episode + r;
-                episode_len += 1;
-                ended = d != 0;
-            }
-            episodes += d;
+            const int d = step_tail(t, st, e, task_type, max_steps, auto_reset, a, r_at, rec.reward, rec.reward64, rec.done, r);
+            ret.add(r, d);
             prev_action = act;
             prev_reward = (float)r;
             prev_done = d;
@@ -242,10 +198,7 @@ __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze
     float *o = po.obs_last + (size_t)e * WW;
 #pragma unroll
     for (int i = 0; i < WW; ++i) o[i] = x[i];
-    po.ret_total[e] = ret_total;
-    po.ret_episode[e] = ret_episode;
-    po.episode_len[e] = episode_len;
-    po.episodes[e] = episodes;
+    ret.store(po, e);
 }
 
 typedef decltype(&maze2d_policy_rollout_kernel<1>) MpKernel;
@@ -297,17 +250,14 @@ extern "C" int mg_maze2d_policy_rollout(const mg_maze_tasks *T, int32_t task_typ
     if (int rc = check_mstate(st, task_type)) return rc;
     if (int rc = check_slots(T, st, task_type)) return rc;
     const MpLds lds = mp_lds_layout(policy->hidden, view_grid, obs != nullptr);
-    if ((size_t)lds.bytes > MP_LDS_LIMIT)
+    if ((size_t)lds.bytes > mg::LDS_LIMIT)
         return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d view_grid=%d needs %d B of LDS (> 160 KiB)", policy->hidden, view_grid, lds.bytes);
     const MpKernel kernel = pick_policy_kernel(view_grid);
     mg::DeviceGuard guard(mg::device_of(st->grid));
-    if (lds.bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes);
-        if (e != hipSuccess) return mg::check_hip(e, "hipFuncSetAttribute(maze2d_policy_rollout_kernel)");
-    }
+    if (int rc = mg::opt_in_dynamic_lds(kernel, lds.bytes, "maze2d_policy_rollout_kernel")) return rc;
     MpPolicy pa{policy->params, policy->eps_threshold, policy_ids, policy->n_policies, policy->hidden};
-    MpOut po{obs_last, ret_total, ret_episode, episode_len, episodes};
-    MpRec rec{actions, reward, reward64, done, obs};
+    RolloutOut po{obs_last, ret_total, ret_episode, episode_len, episodes};
+    RolloutRec rec{actions, reward, reward64, done, obs};
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + MP_BLOCK - 1) / MP_BLOCK)), dim3(MP_BLOCK), (size_t)lds.bytes,
                        (hipStream_t)stream, *T, *st, task_type, max_steps, auto_reset, n, n_steps, obs_every, pa, *carry, seed, step0,
                        episodic, po, rec);
