@@ -25,16 +25,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 # v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 (the dynamic VALU count does not change, round 4), and the step kernel is 1 % slower:
 # five alternating A/B pairs of `bench.py --steps 400 --launch eager`, 14.61 / 14.59 / 14.60 / 14.51 us per step with, 14.41 / 14.49 /
 # 14.52 / 14.37 without (round 6). Bit-identical results (packed float32 arithmetic is IEEE per lane); the GPU parity tests run on it.
-# quadrotor_tasks.hip and quadrotor_policy.hip are built from the same device functions (they include quadrotor.hip) and take the same flag.
+# quadrotor_tasks.hip and quadrotor_policy.hip are built from the same device functions (quadrotor_core.h) and take the same flag.
 FILE_FLAGS = {"quadrotor.hip": ["-fno-slp-vectorize"], "quadrotor_tasks.hip": ["-fno-slp-vectorize"],
               "quadrotor_policy.hip": ["-fno-slp-vectorize"]}
-
-
-# Sources a .hip includes besides the headers: its object is stale when one of them is newer.
-FILE_DEPS = {"quadrotor_tasks.hip": ["quadrotor.hip"], "quadrotor_policy.hip": ["quadrotor.hip"],
-             "walker_policy.hip": ["walker.hip"], "walker_rpolicy.hip": ["walker.hip"], "maze_policy.hip": ["maze.hip"],
-             "maze_expert.hip": ["maze.hip"], "maze3d_policy.hip": ["maze.hip"],
-             "bandits_policy.hip": ["bandits.hip"], "bandits_learner.hip": ["bandits.hip"], "liftsim_policy.hip": ["liftsim.hip"]}
 
 
 def sources():
@@ -63,13 +56,33 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 COMPILE_FLAGS = [f for f in FLAGS if f != "-shared"]
 
 
-def _headers():
-    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
-        [os.path.join(os.path.dirname(HERE), "include", "metagym_hip.h"), os.path.abspath(__file__)]
-
-
 def _object_of(src):
     return os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + ".o")
+
+
+def depfile_paths(text, base):
+    """The files a compiler-written depfile (-MD, Make syntax) names as prerequisites: `\\`-continued lines, `\\ ` for a
+    space inside a name, names relative to `base` (the directory the compiler ran in). A rule is split at its first colon:
+    the target (our own object path) is assumed to contain none."""
+    paths = []
+    for rule in text.replace("\\\n", " ").split("\n"):
+        if ": " not in rule and not rule.endswith(":"):
+            continue
+        for name in rule.split(":", 1)[1].replace("\\ ", "\0").split():
+            paths.append(os.path.normpath(os.path.join(base, name.replace("\0", " "))))
+    return paths
+
+
+def object_is_stale(obj, depfile, base, recipe):
+    """True when `obj` has to be compiled again: it or its depfile is missing or unreadable, or a file the depfile names
+    (read relative to `base`) or `recipe` (this build script) is missing or newer than the object. Flags are not its business."""
+    try:
+        t = os.path.getmtime(obj)
+        with open(depfile, errors="replace") as f:
+            deps = depfile_paths(f.read(), base)
+        return not deps or any(os.path.getmtime(d) > t for d in deps + [recipe])
+    except OSError:
+        return True
 
 
 def build(force=False, verbose=True, extra_flags=()):
@@ -85,20 +98,18 @@ def build(force=False, verbose=True, extra_flags=()):
         try:
             if not force and not extra_flags and not is_stale():      # another process built it while we waited
                 return LIB_PATH
-            hdr_t = max(os.path.getmtime(h) for h in _headers())
             flags_file = os.path.join(OBJ_DIR, "flags.txt")
             flags_now = " ".join(COMPILE_FLAGS + list(extra_flags)) + " | " + repr(sorted(FILE_FLAGS.items()))
             same_flags = os.path.exists(flags_file) and open(flags_file).read() == flags_now
             jobs = []
             for src in sources():
                 obj = _object_of(src)
-                if force or not same_flags or not os.path.exists(obj) or \
-                        os.path.getmtime(obj) < max([os.path.getmtime(src), hdr_t] + [os.path.getmtime(os.path.join(CSRC, d))
-                                                                                       for d in FILE_DEPS.get(os.path.basename(src), [])]):
-                    cmd = [HIPCC] + COMPILE_FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + list(extra_flags) + ["-c", src, "-o", obj]
+                if force or not same_flags or object_is_stale(obj, obj + ".d", CSRC, os.path.abspath(__file__)):
+                    cmd = [HIPCC] + COMPILE_FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + list(extra_flags) + \
+                          ["-MD", "-MF", obj + ".d", "-c", src, "-o", obj]
                     if verbose:
                         print(" ".join(cmd), flush=True)
-                    jobs.append((cmd, subprocess.Popen(cmd)))
+                    jobs.append((cmd, subprocess.Popen(cmd, cwd=CSRC)))
             for cmd, proc in jobs:
                 if proc.wait() != 0:
                     raise subprocess.CalledProcessError(proc.returncode, cmd)

@@ -1,11 +1,9 @@
 // bandits_learner.hip — Bandits closed-loop rollouts with a classical learner inside the launch (mg_bandits_learner_*):
 // greedy on a Beta prior, UCB, an index table (Gittins) and Thompson sampling, each defined exactly in include/metagym_hip.h.
 //
-// A translation unit of its own, like bandits_policy.hip and for the same reason: it takes bandits.hip's device functions
-// (Streams, sample_task), BanditsK and the host checks by including it with MG_BANDITS_CORE_ONLY, so the seed, sample, reset
-// and step kernels are compiled from the text they were compiled from before. Same flags (metagym_amd/build.py):
-// -ffp-contract=off, which is what makes the definition hold (one rounding per operation); `/` and sqrtf are the correctly
-// rounded float32 operations.
+// A translation unit of its own on bandits_core.h (Streams, sample_task, BanditsK, the host checks). Same flags
+// (metagym_amd/build.py): -ffp-contract=off, which is what makes the definition hold (one rounding per operation); `/` and
+// sqrtf are the correctly rounded float32 operations.
 //
 // Mapping: bandits_policy_rollout_kernel's — one lane per env, one wave per workgroup. The env scalars, the running argmax
 // and the five results live in registers for n_steps steps; the two count arrays live in LDS lane-minor
@@ -14,8 +12,7 @@
 // over (arm, draw, attempt) has a length of its own in every lane and holds no collective. The refill inside Streams::next is a
 // workgroup-collective (__syncthreads): the env half of a step is reached by all 64 lanes at every step, with act = false
 // for the lanes that draw nothing. Table rows are read per lane from global memory; lanes sharing a row hit in cache.
-#define MG_BANDITS_CORE_ONLY
-#include "bandits.hip"
+#include "bandits_core.h"
 
 #include "mg_philox.h"
 

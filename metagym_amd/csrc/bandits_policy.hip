@@ -1,9 +1,9 @@
 // bandits_policy.hip — Bandits closed-loop rollouts: per-env recurrent policies inside the launch (mg_bandits_policy_*).
 //
-// A translation unit of its own, like maze_policy.hip and for the same reason: it takes bandits.hip's device functions
-// (Streams, sample_task, clip01), BanditsK and the host checks by including it with MG_BANDITS_CORE_ONLY, so the seed, sample,
-// reset and step kernels are compiled from the text they were compiled from before. Same flags (metagym_amd/build.py):
-// -ffp-contract=off, which is what makes the policy definition of include/metagym_hip.h hold (one rounding per operation).
+// A translation unit of its own on bandits_core.h (Streams, sample_task, clip01, BanditsK, the host checks). Same flags
+// (metagym_amd/build.py): -ffp-contract=off, which is what makes the policy definition of include/metagym_hip.h hold (one
+// rounding per operation). The kernel keeps its own staging and exploration draw; only the host side
+// takes the LDS limit and the opt-in from mg_closed_loop.h.
 //
 // Mapping: bandits_step_kernel's — one lane per env, one wave per workgroup; steps, over, the stream position, the gauss
 // cache, the carry scalars, the best gain of the row in force and the five results live in registers for n_steps steps.
@@ -16,17 +16,15 @@
 // The refill inside Streams::next is a workgroup-collective (__syncthreads). The env half of a step is therefore reached
 // by all 64 lanes at every step, with act = false for the lanes that draw nothing: the spare lanes, the envs that are over,
 // and at the task draw the envs whose episode did not end.
-#define MG_BANDITS_CORE_ONLY
-#include "bandits.hip"
+#include "bandits_core.h"
 
-#include "mg_philox.h"
+#include "mg_closed_loop.h"
 
 namespace {
 
 constexpr int BP_BLOCK = mg::WAVE;
 constexpr int BP_MAX_HIDDEN = 64;
 constexpr int BP_MAX_ARMS = 64;
-constexpr size_t BP_LDS_LIMIT = 160 * 1024;      // gfx950: LDS per CU, the most one workgroup can have
 constexpr uint32_t BP_PHILOX_TAG = 0x4241u;      // c3 of the exploration draw
 
 typedef float bp_v4f __attribute__((ext_vector_type(4)));
@@ -311,14 +309,10 @@ extern "C" int mg_bandits_policy_rollout(const mg_bandits_config *cfg, int32_t n
     if (((uintptr_t)policy->params & 15u) != 0)
         return mg::set_error(MG_ERR_BAD_CONFIG, "mg_bandits_policy.params must be 16-byte aligned");
     const BpLds lds = bp_lds_layout(policy->hidden, policy->arms);
-    if ((size_t)lds.bytes > BP_LDS_LIMIT)
+    if ((size_t)lds.bytes > mg::LDS_LIMIT)
         return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d arms=%d needs %d B of LDS (> 160 KiB)", policy->hidden, policy->arms, lds.bytes);
     mg::DeviceGuard guard(mg::device_of(state->mt));
-    if (lds.bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(bandits_policy_rollout_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes);
-        if (e != hipSuccess) return mg::check_hip(e, "hipFuncSetAttribute(bandits_policy_rollout_kernel)");
-    }
+    if (int rc = mg::opt_in_dynamic_lds(bandits_policy_rollout_kernel, lds.bytes, "bandits_policy_rollout_kernel")) return rc;
     BpPolicy pa{policy->params, policy->eps_threshold, policy_ids, policy->n_policies, policy->hidden};
     BpOut po{ret_total, ret_episode, episode_len, episodes, regret};
     BpRec rec{actions, reward, done, info_steps, expected_gain, best_gain, invalid};

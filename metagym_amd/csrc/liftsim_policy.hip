@@ -1,10 +1,8 @@
 // liftsim_policy.hip — LiftSim closed-loop rollouts: learned dispatchers inside the launch (mg_liftsim_policy_*).
 //
-// A translation unit of its own, like bandits_policy.hip and for the same reason: it takes liftsim.hip's device functions
-// (refill_streams, step_body), K, Lay, Records and the host checks by including it with MG_LIFTSIM_CORE_ONLY, so the seed,
-// reset, step, rollout, rule-policy and statistics kernels are compiled from the text they were compiled from before.
-// Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes the policy definition of
-// include/metagym_hip.h hold (one rounding per operation).
+// A translation unit of its own on liftsim_core.h (refill_streams, step_body, K, Lay, Records, the host checks). Same flags
+// (metagym_amd/build.py): -ffp-contract=off, which is what makes the policy definition of include/metagym_hip.h hold (one
+// rounding per operation).
 //
 // Mapping: liftsim_rollout_kernel's — one lane per building, one wave per workgroup, {refill, policy, step_body} T times.
 // The policy of a step runs between two step_body calls, when nothing of the step is live: per elevator the eight scaled
@@ -18,8 +16,7 @@
 //
 // All LDS is dynamic, carved at multiples of 16 bytes from a 16-byte aligned base (a static array ahead of it would shift
 // the base of the 16-byte reads).
-#define MG_LIFTSIM_CORE_ONLY
-#include "liftsim.hip"
+#include "liftsim_core.h"
 
 #include "mg_closed_loop.h"
 

@@ -1,9 +1,8 @@
 // maze3d_policy.hip — MetaMaze 3-D closed-loop rollouts: per-env recurrent policies that read the rendered frame
 // (mg_maze3d_policy_param_count, mg_maze3d_pool_features, mg_maze3d_policy_rollout).
 //
-// A translation unit of its own, like maze_policy.hip and maze_expert.hip and for the same reason: it takes maze.hip's device
-// functions (load_task, load_agent, transition_discrete, transition_continuous, step_tail, Returns, rollout_records) by including it with MG_MAZE_CORE_ONLY, so the step, rollout and render kernels are compiled
-// from the text they were compiled from before. Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes the
+// A translation unit of its own on maze_core.h (load_task, load_agent, transition_discrete, transition_continuous, step_tail,
+// Returns, rollout_records, the host checks). Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes the
 // policy definition of include/metagym_hip.h hold (one rounding per operation).
 //
 // Launch pattern: mg_maze3d_expert_rollout's, one step per stretch. The host loop renders the frame of the state the envs
@@ -23,8 +22,7 @@
 //             wave's read of one input's H weights is one coalesced line, served by L2 for every env after the first.
 //   outputs   lanes k < K (4 logits or 2 steering outputs) walk j in ascending order.
 //   env step  lane 0 runs maze3d_advance_kernel's step (the transition, step_tail) with the action taken from the outputs.
-#define MG_MAZE_CORE_ONLY
-#include "maze.hip"
+#include "maze_core.h"
 
 #include "mg_closed_loop.h"
 

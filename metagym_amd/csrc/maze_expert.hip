@@ -1,9 +1,9 @@
 // maze_expert.hip — MetaMaze shortest-path fields and the expert that descends them (mg_maze_distance_field,
 // mg_maze_expert_action, mg_maze2d_expert_rollout, mg_maze_steer_action, mg_maze3d_expert_rollout).
 //
-// A translation unit of its own, like maze_policy.hip and for the same reason: it takes maze.hip's device functions
-// (load_task, load_agent, transition_discrete, move_2d, step_tail, eval_scalar, eval_cells, reset_cells, reset_agent, Returns,
-// observe_2d, rollout_records) and host checks by including it with MG_MAZE_CORE_ONLY. Same flags (metagym_amd/build.py).
+// A translation unit of its own on maze_core.h (load_task, load_agent, transition_discrete, transition_continuous, move_2d,
+// step_tail, eval_scalar, eval_cells, reset_cells, reset_agent, Returns, observe_2d, rollout_records, the host checks). Same
+// flags (metagym_amd/build.py).
 //
 // The field. dist[t][k][c] is the length of the shortest action sequence that takes state (k, c) of task t onto a source cell
 // under the step's own passability rule (include/metagym_hip.h states the three rules). One workgroup per task runs a
@@ -26,8 +26,7 @@
 // otherwise, every decision a comparison (me_steer_pick). mg_maze3d_expert_rollout follows mg_maze3d_rollout's launch pattern:
 // per recorded frame one lane-per-env launch of maze3d_advance_kernel's body with the action load replaced by the pick
 // (maze3d_expert_advance_kernel), then the untouched renderer through mg_maze3d_step's observe-only form.
-#define MG_MAZE_CORE_ONLY
-#include "maze.hip"
+#include "maze_core.h"
 
 #include "mg_closed_loop.h"
 

@@ -1,10 +1,8 @@
 // maze_policy.hip — MetaMaze 2-D closed-loop rollouts: per-env recurrent policies inside the launch (mg_maze2d_policy_*).
 //
-// A translation unit of its own, like quadrotor_policy.hip and walker_policy.hip and for the same reason: it takes maze.hip's
-// device functions (load_task, load_agent, move_2d, step_tail, Returns, observe_2d, rollout_records) and host checks by
-// including it with MG_MAZE_CORE_ONLY, so the step and rollout kernels are compiled from the text they
-// were compiled from before. Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes the policy definition
-// of include/metagym_hip.h hold (one rounding per operation).
+// A translation unit of its own on maze_core.h (load_task, load_agent, move_2d, step_tail, Returns, observe_2d,
+// rollout_records, the host checks). Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes the policy
+// definition of include/metagym_hip.h hold (one rounding per operation).
 //
 // Mapping: maze2d_rollout_kernel's — one lane per env, one wave per workgroup, task and agent in registers for n_steps steps.
 // The policy input x (the window, the previous action one-hot, the previous reward and done) lives in registers (the kernel is
@@ -13,8 +11,7 @@
 // Weights: a wave whose lanes all hold one policy id stages that policy in LDS once and reads it with same-address
 // (broadcast) 16-byte reads; a wave with mixed ids reads per lane from global memory. Both inline policy_eval, so the bits
 // are equal.
-#define MG_MAZE_CORE_ONLY
-#include "maze.hip"
+#include "maze_core.h"
 
 #include "mg_closed_loop.h"
 

@@ -1,12 +1,10 @@
 // quadrotor_policy.hip — quadrotor closed-loop rollouts: per-env MLP policies inside the launch (mg_quadrotor_policy_*), and
 // per-env recurrent policies with a carry between launches (mg_quadrotor_rpolicy_*, the RECURRENT instantiations).
 //
-// A translation unit of its own, like quadrotor_tasks.hip and for the same reason: it takes quadrotor.hip's device
-// functions and host-side folding by including it with MG_QUADROTOR_CORE_ONLY, so the tuned single-config kernels are
-// compiled from the text they were compiled from before. Same flags (metagym_amd/build.py): -ffp-contract=off, which is
-// what makes the policy definition of include/metagym_hip.h hold (one rounding per operation), and no SLP vectoriser.
-#define MG_QUADROTOR_CORE_ONLY
-#include "quadrotor.hip"
+// A translation unit of its own on quadrotor_core.h (the device functions and the host-side folding), like
+// quadrotor_tasks.hip and for the same reason. Same flags (metagym_amd/build.py): -ffp-contract=off, which is what makes
+// the policy definition of include/metagym_hip.h hold (one rounding per operation), and no SLP vectoriser.
+#include "quadrotor_core.h"
 
 #include "quadrotor_task_table.h"
 

@@ -1,6 +1,6 @@
 // quadrotor_task_table.h — the quadrotor task table's device view: the folded row, the table and the lane's constants.
 // Included by quadrotor_tasks.hip (the table step) and quadrotor_policy.hip (the closed-loop rollout), each after
-// quadrotor.hip (MG_QUADROTOR_CORE_ONLY), whose QuadK the row overlays. Not a header for anything else.
+// quadrotor_core.h, whose QuadK the row overlays. Not a header for anything else.
 #pragma once
 
 namespace {

@@ -1,13 +1,10 @@
 // quadrotor_tasks.hip — the quadrotor task table: per-env simulator parameters in one launch (mg_quadrotor_tasks_*).
 //
-// A translation unit of its own, next to quadrotor.hip: it takes that file's device functions (substep<>, failure_code,
-// observe, collision, reset_draw, ...) and its host-side folding (fold_config, config_is_simple) by including it with
-// MG_QUADROTOR_CORE_ONLY, which leaves out the uniform path's plan, launch code and C entry points. The single-config
-// kernels are therefore compiled from exactly the text they were compiled from before this file existed: a kernel added
-// to quadrotor.hip itself perturbs the register allocation of its neighbours, and those kernels are tuned.
+// A translation unit of its own on quadrotor_core.h (substep<>, failure_code, observe, collision, reset_draw, ..., and the
+// host-side folding: fold_config, config_is_simple), next to quadrotor.hip and not inside it: a kernel added to
+// quadrotor.hip itself perturbs the register allocation of its neighbours, and those kernels are tuned.
 // Same flags as quadrotor.hip (metagym_amd/build.py): -ffp-contract=off, no SLP vectoriser.
-#define MG_QUADROTOR_CORE_ONLY
-#include "quadrotor.hip"
+#include "quadrotor_core.h"
 
 #include "quadrotor_task_table.h"
 

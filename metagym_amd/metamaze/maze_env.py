@@ -77,7 +77,7 @@ def food_lists(food_rewards, food_interval, by_slot):
 def rollout_obs_steps(n_steps, obs_every):
     """The steps (0-based, ascending) of a `rollout` of `n_steps` steps that leave an observation: `obs_every` 0 = the last
     step only; k >= 1 = every step t with (t + 1) % k == 0, and always the last one (never twice). The kernels apply the same
-    rule (csrc/maze.hip rollout_records)."""
+    rule (csrc/maze_core.h rollout_records)."""
     n_steps, obs_every = int(n_steps), int(obs_every)
     if n_steps < 1:
         raise ValueError("a rollout needs at least one step (got %d)" % n_steps)

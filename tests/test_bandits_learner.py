@@ -389,7 +389,7 @@ def _header():
 
 
 def test_entry_points_are_declared_in_the_header_and_the_binding():
-    from metagym_amd import _lib, build
+    from metagym_amd import _lib
     lib = _lib.load()
     text = _header()
     for name in ("mg_bandits_learner_rollout", "mg_bandits_learner_scores"):
@@ -405,9 +405,8 @@ def test_entry_points_are_declared_in_the_header_and_the_binding():
     for name, code in L.KINDS.items():
         assert re.search(r"#define\s+MG_BANDITS_LEARNER_%s\s+%d\b" % (name.upper(), code), text), name
     assert len(_lib.SIGNATURES["mg_bandits_learner_rollout"][1]) == 23 and len(_lib.SIGNATURES["mg_bandits_learner_scores"][1]) == 9
-    assert build.FILE_DEPS["bandits_learner.hip"] == ["bandits.hip"]
-    src = open(os.path.join(ROOT, "metagym_amd", "csrc", "bandits_learner.hip")).read()
-    assert "#define MG_BANDITS_CORE_ONLY" in src and '#include "bandits.hip"' in src
+    from csrc_structure import assert_unit_sits_on_the_bandits_core
+    assert_unit_sits_on_the_bandits_core("bandits_learner.hip")
 
 
 def test_abi_refuses_on_the_host_before_any_device_call():

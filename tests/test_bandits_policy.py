@@ -333,11 +333,8 @@ def test_entry_points_are_declared_in_the_header_and_the_binding():
     assert re.search(r"typedef\s+mg_maze_policy_carry\s+mg_bandits_policy_carry\s*;", text)
     assert _lib.BanditsPolicyCarry is _lib.MazePolicyCarry
     assert len(_lib.SIGNATURES["mg_bandits_policy_rollout"][1]) == 23
-    # the step and its kernels were left alone: bandits.hip differs from a text without the guard by the guard's two lines
-    src = open(os.path.join(ROOT, "metagym_amd", "csrc", "bandits.hip")).read()
-    assert src.count("MG_BANDITS_CORE_ONLY") == 2 and "#ifndef MG_BANDITS_CORE_ONLY" in src
-    from metagym_amd import build
-    assert build.FILE_DEPS["bandits_policy.hip"] == ["bandits.hip"]
+    from csrc_structure import assert_unit_sits_on_the_bandits_core
+    assert_unit_sits_on_the_bandits_core("bandits_policy.hip")
 
 
 def test_abi_refuses_on_the_host_before_any_device_call():

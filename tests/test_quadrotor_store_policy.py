@@ -1,4 +1,4 @@
-"""The store / load policy macros of csrc/quadrotor.hip (MG_QUAD_ST_*, MG_QUAD_STP_*, MG_QUAD_LD_STATE): the two quadrotor
+"""The store / load policy macros of csrc/quadrotor_core.h (MG_QUAD_ST_*, MG_QUAD_STP_*, MG_QUAD_LD_STATE): the two quadrotor
 translation units compile for gfx950 with every policy value, and a value that names no policy is a compile-time error
 (static_assert). Compiles only (hipcc cross-compiles without a GPU); what the policies do on the device is
 tests/test_quadrotor_store_policy_gpu.py."""
