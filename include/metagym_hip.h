@@ -1870,6 +1870,84 @@ int mg_liftsim_policy_rollout(const mg_liftsim_config *cfg, int32_t n_envs, void
                               double *rec_time_consume, double *rec_energy_consume, int32_t *rec_given_up,
                               int32_t *rec_actions, void *stream);
 
+/* ---- LiftSim closed-loop rollouts: recurrent dispatchers with a carry (additive; MG_ABI_VERSION unchanged) ----
+ *
+ * mg_liftsim_policy_rollout with a memory: each of the n_policies networks is still shared by its building's elevators,
+ * and each elevator has a memory of its own, H floats clamped to [-1, 1], which the network reads and rewrites at every
+ * step together with that elevator's previous choice and the building's previous reward. The step is mg_liftsim_step's,
+ * unchanged, and the recorded actions replay as mg_liftsim_policy_rollout's do.
+ *
+ * The policy, defined exactly. F floors, E elevators, H hidden units (1 <= H <= 64), A = 2F + 2 choices. Every operation is
+ * float32, rounded once, never fused, in this order. h[el] is elevator el's memory before the step, pc[el] its previous
+ * choice (-1: none), pr the building's previous reward. For elevator el of an env, from the state before the step:
+ *   x[0..7] = f32(raw[i]) * scale[i]      (raw as for mg_liftsim_policy)
+ *   for j in 0..H-1:
+ *       z = b[j]
+ *       for i in 0..7:  z = z + ws[j][i] * x[i]
+ *       z = z + we[j][el]
+ *       d = CurrentDispatchTarget;  if 0 <= d <= F:  z = z + wt[j][d]
+ *       for f in 1..F ascending, if f in ReservedTargetFloors[el]:   z = z + wr[j][f-1]
+ *       for f in 1..F ascending, if f in RequiringUpwardFloors:      z = z + wu[j][f-1]
+ *       for f in 1..F ascending, if f in RequiringDownwardFloors:    z = z + wd[j][f-1]
+ *       if pc[el] >= 0:  z = z + wc[j][pc[el]]
+ *       z = z + wq[j] * pr
+ *       for i in 0..H-1:  z = z + wh[j][i] * h[el][i]
+ *       hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+ *   h[el] = hn
+ *   for c in 0..A-1:  l[c] = bo[c];  for j in 0..H-1:  l[c] = l[c] + wo[c][j] * h[el][j]
+ *   choice = 0;  for c in 1..A-1:  if l[c] > l[choice]:  choice = c
+ *   pc[el] = choice
+ * The E elevators of a step are all evaluated on the same pre-step state and see the same pr. After the step,
+ * pr = f32(reward), the value the reward record holds for that step. Lookups (we, wt, wr, wu, wd, wc) are one add or none,
+ * never a multiply-add, and padding is never added into a sum: a pre-activation of -0 stays -0, and a NaN z (inf - inf)
+ * stays NaN through the clamp. Ties and NaN logits resolve to the lowest index. The choice maps to an action as for
+ * mg_liftsim_policy. There is no done input (LiftSim never ends an episode) and no exploration draw.
+ * An env frozen by OVERFLOW or UNSUPPORTED when a step begins evaluates nothing, records (0, 0) per elevator and keeps its
+ * carry as it stood. In the step in which an env overflows the policy has run, so h and pc are that step's, and pr is f32
+ * of the 0 that the step's reward record holds.
+ *
+ * The carry, DEVICE, env index fastest (the arena's convention), 4-byte aligned, updated in place by a launch:
+ *   h f32 [E][H][N], prev_choice i32 [E][N] (-1 or a choice in [0, A)), prev_reward f32 [N]
+ * All zero except prev_choice = -1 when fresh. n1 steps and then n2 steps on one carry equal n1 + n2 steps in one call.
+ * A mg_liftsim_step or mg_liftsim_rollout between two calls is not seen by the carry: pr stays the last reward of this
+ * call's kind.
+ *
+ * Packed parameters, DEVICE f32, 16-byte aligned, mg_liftsim_rpolicy_param_count(H, F, E) floats per policy, policy p at
+ * params + p * count. With P4(n) = n rounded up to a multiple of 4, RU = 12 + P4(E) + P4(F+1) + 3 P4(F) + P4(A) + P4(H),
+ * RC = 4 + P4(H):
+ *   one record of RU floats per hidden unit j, at RU j, its groups in this order, each zero-padded to a multiple of 4:
+ *     [0] b[j], [1] wq[j], [2..3] 0 | [4..11] ws[j][0..7] | we[j][0..E-1] | wt[j][0..F] | wr[j][0..F-1] | wu[j][0..F-1] |
+ *     wd[j][0..F-1] | wc[j][0..A-1] | wh[j][0..H-1]
+ *   then one record of RC floats per choice c, at H RU + RC c:
+ *     [0] bo[c], [1..3] 0 | [4 .. 3+H] wo[c][0..H-1], zeros up to [3+P4(H)]
+ *   (count = H RU + A RC; F = 128, E = 32, H = 64: 74 120 floats)
+ * Parameters must be finite and are read-only for the launch. scale is the same for all policies. */
+typedef struct mg_liftsim_rpolicy {
+    const float *params;               /* DEVICE f32 [n_policies][count] */
+    int32_t n_policies, hidden, floors, elevators;
+    float scale[8];                    /* x[i] = f32(raw[i]) * scale[i] */
+} mg_liftsim_rpolicy;
+
+typedef struct mg_liftsim_policy_state {
+    float *h;                          /* DEVICE f32 [E][H][N] */
+    int32_t *prev_choice;              /* DEVICE i32 [E][N] */
+    float *prev_reward;                /* DEVICE f32 [N] */
+} mg_liftsim_policy_state;
+
+/* Floats per packed recurrent policy (host only); MG_ERR_BAD_SIZE as mg_liftsim_policy_param_count. */
+int32_t mg_liftsim_rpolicy_param_count(int32_t hidden, int32_t floors, int32_t elevators);
+
+/* One launch of n_steps steps, mapped and staged as mg_liftsim_policy_rollout (the LDS need now holds two memory columns
+ * of H * 64 floats; the result does not depend on the staging). policy_ids, ret and the records are that call's.
+ * Refused on the host, before anything is launched: what mg_liftsim_policy_rollout refuses, a NULL state or a NULL array in
+ * it (MG_ERR_NULL_POINTER), a state array that is not 4-byte aligned (MG_ERR_BAD_CONFIG). Nothing is allocated and nothing
+ * synchronises: the call is hipGraph-capturable as it stands. */
+int mg_liftsim_rpolicy_rollout(const mg_liftsim_config *cfg, int32_t n_envs, void *arena, int32_t n_steps,
+                               const mg_liftsim_rpolicy *policy, const int32_t *policy_ids,
+                               const mg_liftsim_policy_state *state, double *ret, double *rec_reward,
+                               double *rec_time_consume, double *rec_energy_consume, int32_t *rec_given_up,
+                               int32_t *rec_actions, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -347,6 +347,17 @@ class LiftsimPolicyDesc(C.Structure):
                 ("elevators", C.c_int32), ("scale", C.c_float * 8)]
 
 
+class LiftsimRPolicyDesc(C.Structure):
+    """mg_liftsim_rpolicy (params: a device pointer)"""
+    _fields_ = [("params", C.c_void_p), ("n_policies", C.c_int32), ("hidden", C.c_int32), ("floors", C.c_int32),
+                ("elevators", C.c_int32), ("scale", C.c_float * 8)]
+
+
+class LiftsimPolicyState(C.Structure):
+    """mg_liftsim_policy_state (device pointers): h f32 [E][H][N], prev_choice i32 [E][N], prev_reward f32 [N]"""
+    _fields_ = [("h", C.c_void_p), ("prev_choice", C.c_void_p), ("prev_reward", C.c_void_p)]
+
+
 # the MG_LS_* fields of the LiftSim state arena, in the header's order
 LIFTSIM_FIELDS = ["pos", "vel", "load", "door", "keep", "alarm", "floor", "dir", "dispatch", "dispatch_dir", "ntarget",
                   "eflags", "targets", "opening", "closing", "clicked", "nloaded", "lw", "lt", "nent", "ew", "et", "el",
@@ -479,6 +490,9 @@ SIGNATURES = {
     "mg_liftsim_policy_param_count": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "mg_liftsim_policy_rollout": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, C.c_int32, C.POINTER(LiftsimPolicyDesc),
                                             _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mg_liftsim_rpolicy_param_count": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "mg_liftsim_rpolicy_rollout": (C.c_int, [C.POINTER(LiftsimConfig), C.c_int32, _P, C.c_int32, C.POINTER(LiftsimRPolicyDesc),
+                                             _P, C.POINTER(LiftsimPolicyState), _P, _P, _P, _P, _P, _P, _P]),
     "mg_bandits_seed": (C.c_int, [C.c_int32, C.c_uint32, _P, C.POINTER(BanditsState), _P]),
     "mg_bandits_sample_task": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P, _P]),
     "mg_bandits_reset": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), _P, _P]),

@@ -1,6 +1,9 @@
 """What the Python front ends of the closed-loop rollouts share (quadrotor, MetaLocomotion, MetaMaze 2-D, bandits, LiftSim):
 the argument helpers, Philox and the exploration threshold, the upload-once cache of a packed policy set, the carry of the
 continuous-action recurrent policies, the validator and cache of `policy_ids`, and the carry checks of `rollout_policy`.
+LiftSim's recurrent form (`LiftRecurrentPolicy`, `liftsim/policy.py`) takes the argument helpers, `PackedPolicySet` and
+`policy_ids`; its carry (`LiftPolicyState`: a memory per elevator, stored env index fastest) and that carry's checks stay
+with it, since no other family shares their shape.
 
 What differs per env stays with the env: the `reference` arithmetic, `pack` / `unpack` and the layout constants, and the ctypes
 calls. Nothing here needs a GPU to import; torch is imported inside the functions."""

@@ -1,7 +1,7 @@
 // liftsim_core.h — the LiftSim family's shared core: the arena layout (Lay, Env), one env.step as a device function
-// (step_body and what it calls), the wave's stream refill (refill_streams), Records and the host checks. liftsim.hip and
-// liftsim_policy.hip include it; each keeps its own copy (anonymous namespace) and defines the kernels it launches. The
-// step's order and the mapping are described in liftsim.hip.
+// (step_body and what it calls), the wave's stream refill (refill_streams), Records and the host checks. liftsim.hip,
+// liftsim_policy.hip and liftsim_rpolicy.hip include it; each keeps its own copy (anonymous namespace) and defines the
+// kernels it launches. The step's order and the mapping are described in liftsim.hip.
 #pragma once
 #include <cmath>
 

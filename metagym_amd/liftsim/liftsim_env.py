@@ -367,7 +367,7 @@ class LiftSim(object):
             _lib.ptr(out.get("given_up_persons")), _lib.ptr(out.get("actions")), self._stream()), "mg_liftsim_rollout")
         return out
 
-    def rollout_policy(self, policy, steps, policy_ids=None, record=()):
+    def rollout_policy(self, policy, steps, policy_ids=None, record=(), state=None):
         """`steps` closed-loop env steps of every building in ONE launch: building e is dispatched by policy
         `policy_ids[e]` of `policy` (a `LiftPolicy`; `policy_ids=None` = policy 0 for all), evaluated inside the kernel
         once per elevator on the state before each step (liftsim/policy.py defines the arithmetic exactly). The step is
@@ -376,11 +376,23 @@ class LiftSim(object):
         named in `record` (of RECORDS; "actions" [T, N, 2E] holds the policy's actions, (0, 0) for an env that was
         frozen when the step began). The ids are validated once: nothing synchronises when `policy_ids` is None, a host
         array, or the (unchanged) tensor of the previous call, so after `policy.to(device)` the call can be captured in a hipGraph. A refused call
-        (a policy for another F or E, an id out of range, steps < 1) raises and leaves the arena untouched."""
+        (a policy for another F or E, an id out of range, steps < 1) raises and leaves the arena untouched.
+
+        With a `LiftRecurrentPolicy` every elevator has a memory, kept in `state` (a `LiftPolicyState` on this device,
+        updated in place; None: a fresh `LiftPolicyState.zeros(N, E, H, device)`), and the dict also holds "state", that
+        same object: the end carry. T1 steps and then T2 steps through one state equal T1 + T2 steps in one call. The
+        carry sees `rollout_policy` steps only: a `step()` or `rollout(actions)` between two calls moves the arena, and
+        prev_reward stays the last `rollout_policy` reward. An env that is frozen when a step begins keeps its carry; in
+        the step in which it overflows the policy has run and prev_reward becomes the recorded 0. A refused call (also: a
+        state of another class, on another device, or of wrong shapes, dtypes or layout) leaves arena and state
+        untouched. With a `LiftPolicy`, passing `state` is a ValueError."""
         import torch
-        from .policy import LiftPolicy
+        from .policy import LiftPolicy, LiftPolicyState, LiftRecurrentPolicy
         if not isinstance(policy, LiftPolicy):
-            raise TypeError("policy must be a LiftPolicy, got %s" % type(policy).__name__)
+            raise TypeError("policy must be a LiftPolicy or a LiftRecurrentPolicy, got %s" % type(policy).__name__)
+        recurrent = isinstance(policy, LiftRecurrentPolicy)
+        if state is not None and not recurrent:
+            raise ValueError("a LiftPolicy has no memory: state is for a LiftRecurrentPolicy")
         T, N, E = int(steps), self.num_envs, self.E
         if T < 1:
             raise ValueError("steps must be at least 1, got %d" % T)
@@ -391,10 +403,30 @@ class LiftSim(object):
         unknown = set(record) - set(self.RECORDS)
         if unknown:
             raise ValueError("unknown records: %s (known: %s)" % (sorted(unknown), list(self.RECORDS)))
+        if recurrent:
+            H = policy.hidden
+            if state is None:
+                state = LiftPolicyState.zeros(N, E, H, self.device)
+            elif not isinstance(state, LiftPolicyState):
+                raise TypeError("state must be a LiftPolicyState, got %s" % type(state).__name__)
+            # (field, shape, dtype, the permutation that gives the storage order: env index fastest)
+            want = (("h", (N, E, H), torch.float32, (1, 2, 0)), ("prev_choice", (N, E), torch.int32, (1, 0)),
+                    ("prev_reward", (N,), torch.float32, (0,)))
+            for name, shape, dtype, order in want:
+                v = getattr(state, name)
+                if not isinstance(v, torch.Tensor):
+                    raise ValueError("state must hold torch tensors on %s (LiftPolicyState.zeros(N, E, H, device))" % (self.device,))
+                if v.device != self.device:
+                    raise ValueError("state lives on %s, the env on %s" % (v.device, self.device))
+                if tuple(v.shape) != shape or v.dtype != dtype or not v.permute(*order).is_contiguous():
+                    raise ValueError("state.%s must be a %s tensor of shape %s stored env index fastest (this env has %d envs "
+                                     "and %d elevators, the policy %d hidden units), got %s %s"
+                                     % (name, dtype, shape, N, E, H, v.dtype, tuple(v.shape)))
         ids = _policy.policy_ids(self, policy_ids, policy.num_policies, default="zero")
         params = policy.to(self.device)
-        desc = _lib.LiftsimPolicyDesc(params.data_ptr(), policy.num_policies, policy.hidden, policy.floors, policy.elevators,
-                                      (C.c_float * 8)(*[float(v) for v in policy.scale]))
+        desc_cls = _lib.LiftsimRPolicyDesc if recurrent else _lib.LiftsimPolicyDesc
+        desc = desc_cls(params.data_ptr(), policy.num_policies, policy.hidden, policy.floors, policy.elevators,
+                        (C.c_float * 8)(*[float(v) for v in policy.scale]))
         out = {"return": torch.empty(N, dtype=torch.float64, device=self.device)}
         for name in record:
             if name == "actions":
@@ -402,6 +434,15 @@ class LiftSim(object):
             else:
                 out[name] = torch.empty(T, N, dtype=torch.int32 if name == "given_up_persons" else torch.float64,
                                         device=self.device)
+        if recurrent:
+            carry = _lib.LiftsimPolicyState(state.h.data_ptr(), state.prev_choice.data_ptr(), state.prev_reward.data_ptr())
+            _lib.check(self._lib.mg_liftsim_rpolicy_rollout(
+                self._cfg, N, _lib.ptr(self.arena), T, desc, _lib.ptr(ids), carry, _lib.ptr(out["return"]),
+                _lib.ptr(out.get("reward")), _lib.ptr(out.get("time_consume")), _lib.ptr(out.get("energy_consume")),
+                _lib.ptr(out.get("given_up_persons")), _lib.ptr(out.get("actions")), self._stream()),
+                "mg_liftsim_rpolicy_rollout")
+            out["state"] = state
+            return out
         _lib.check(self._lib.mg_liftsim_policy_rollout(
             self._cfg, N, _lib.ptr(self.arena), T, desc, _lib.ptr(ids), _lib.ptr(out["return"]),
             _lib.ptr(out.get("reward")), _lib.ptr(out.get("time_consume")), _lib.ptr(out.get("energy_consume")),

@@ -28,6 +28,38 @@ whatever the weights hold). Ties and NaN logits resolve to the lowest index. Cho
 
     pol = LiftPolicy(ws, we, wt, wr, wu, wd, b, wo, bo)     # [P,H,8] [P,H,E] [P,H,F+1] [P,H,F] x3 [P,H] [P,A,H] [P,A]
     out = env.rollout_policy(pol, steps=600, policy_ids=ids, record=("reward", "actions"))
+
+The recurrent form (`LiftRecurrentPolicy`, mg_liftsim_rpolicy_rollout): the network is still shared by its building's
+elevators, and each elevator has a memory of its own. h[el] is elevator el's memory before the step, pc[el] its previous
+choice (-1: none), pr the building's previous reward; H hidden units clamped to [-1, 1]:
+
+    x[0..7] = f32(raw[i]) * scale[i]      (raw as for mg_liftsim_policy)
+    for j in 0..H-1:
+        z = b[j]
+        for i in 0..7:  z = z + ws[j][i] * x[i]
+        z = z + we[j][el]
+        d = CurrentDispatchTarget;  if 0 <= d <= F:  z = z + wt[j][d]
+        for f in 1..F ascending, if f in ReservedTargetFloors[el]:   z = z + wr[j][f-1]
+        for f in 1..F ascending, if f in RequiringUpwardFloors:      z = z + wu[j][f-1]
+        for f in 1..F ascending, if f in RequiringDownwardFloors:    z = z + wd[j][f-1]
+        if pc[el] >= 0:  z = z + wc[j][pc[el]]
+        z = z + wq[j] * pr
+        for i in 0..H-1:  z = z + wh[j][i] * h[el][i]
+        hn[j] = z > 1 ? 1 : (z < -1 ? -1 : z)
+    h[el] = hn
+    for c in 0..A-1:  l[c] = bo[c];  for j in 0..H-1:  l[c] = l[c] + wo[c][j] * h[el][j]
+    choice = 0;  for c in 1..A-1:  if l[c] > l[choice]:  choice = c
+    pc[el] = choice
+
+The E elevators of a step are all evaluated on the same pre-step state and see the same pr; after the step pr = f32(reward),
+the value the reward record holds. wc is a lookup like the others: one add or none. An env that is frozen (`overflow` /
+`unsupported`) when a step begins evaluates nothing, records (0, 0) per elevator and keeps its carry as it stood; in the step
+in which it overflows the policy has run (h and pc are that step's) and pr is f32 of the 0 the reward record holds. There
+is no done input (LiftSim.step never returns done) and no exploration draw.
+
+    rpol = LiftRecurrentPolicy(ws, we, wt, wr, wu, wd, wc, wq, wh, b, wo, bo)     # wc [P,H,A], wq [P,H], wh [P,H,H]
+    out = env.rollout_policy(rpol, steps=300, policy_ids=ids)                    # out["state"]: the end carry
+    out = env.rollout_policy(rpol, steps=300, policy_ids=ids, state=out["state"])
 """
 import numpy as np
 
@@ -242,3 +274,201 @@ class LiftPolicy(PackedPolicySet):
         assert h.dtype == np.float32 and logits.dtype == np.float32
         actions = self.actions_of(choice, self.floors).reshape(n, 2 * self.elevators)
         return (actions, choice) if return_choices else actions
+
+
+# ---------------------------------------------------------------------------------------------- the recurrent form
+def recurrent_unit_groups(hidden, floors, elevators):
+    """(name, offset, length) of the groups of one hidden unit's record of a recurrent policy, and the record's length RU.
+    b[j] and wq[j] share the first group: floats 0 and 1."""
+    H, F, E = int(hidden), int(floors), int(elevators)
+    groups, o = [], 0
+    for name, n in (("b", 1), ("ws", N_SCALARS), ("we", E), ("wt", F + 1), ("wr", F), ("wu", F), ("wd", F), ("wc", 2 * F + 2),
+                    ("wh", H)):
+        groups.append((name, o, n))
+        o += pad4(n)
+    groups.insert(1, ("wq", 1, 1))
+    return groups, o
+
+
+def recurrent_param_count(hidden, floors, elevators):
+    """Floats per packed recurrent policy (what mg_liftsim_rpolicy_param_count returns)."""
+    H, F, E = _check_sizes(hidden, floors, elevators)
+    return H * recurrent_unit_groups(H, F, E)[1] + (2 * F + 2) * (4 + pad4(H))
+
+
+class LiftPolicyState(object):
+    """The carry of a recurrent LiftSim rollout, the memory of every elevator of every building: h float32 [N, E, H],
+    prev_choice int32 [N, E] (-1: none), prev_reward float32 [N]. Fresh: zeros, prev_choice = -1.
+
+    On a device the storage is lane-coalesced, the arena's convention (env index fastest): h as [E][H][N], prev_choice as
+    [E][N], prev_reward as [N]; the [N, ...] attributes are permuted views of it, no copies, and a launch updates them in
+    place. `numpy()` gives contiguous [N, ...] arrays, what `LiftRecurrentPolicy.reference` takes.
+
+    The carry sees `rollout_policy` steps only: a `step()` or `rollout(actions)` between two calls changes the arena and
+    not the carry, so prev_reward stays the last `rollout_policy` reward."""
+    __slots__ = ("h", "prev_choice", "prev_reward")
+
+    def __init__(self, h, prev_choice, prev_reward):
+        self.h, self.prev_choice, self.prev_reward = h, prev_choice, prev_reward
+
+    @classmethod
+    def zeros(cls, num_envs, elevators, hidden, device=None):
+        """The fresh carry. device None: numpy arrays."""
+        N, E, H = int(num_envs), int(elevators), int(hidden)
+        if N < 1 or not (1 <= E <= MAX_ELEVATORS) or not (1 <= H <= MAX_HIDDEN):
+            raise ValueError("a carry needs num_envs >= 1, elevators in [1, %d] and hidden in [1, %d], got %d, %d and %d"
+                             % (MAX_ELEVATORS, MAX_HIDDEN, N, E, H))
+        if device is None:
+            return cls(np.zeros((N, E, H), np.float32), np.full((N, E), -1, np.int32), np.zeros(N, np.float32))
+        import torch
+        return cls(torch.zeros(E, H, N, dtype=torch.float32, device=device).permute(2, 0, 1),
+                   torch.full((E, N), -1, dtype=torch.int32, device=device).t(),
+                   torch.zeros(N, dtype=torch.float32, device=device))
+
+    @property
+    def num_envs(self):
+        return int(self.h.shape[0])
+
+    @property
+    def elevators(self):
+        return int(self.h.shape[1])
+
+    @property
+    def hidden(self):
+        return int(self.h.shape[2])
+
+    @property
+    def device(self):
+        """The torch device of the arrays; None for a numpy carry."""
+        return self.h.device if hasattr(self.h, "detach") else None
+
+    def clone(self):
+        if self.device is None:
+            return type(self)(self.h.copy(), self.prev_choice.copy(), self.prev_reward.copy())
+        # clone the storage in its own order, then view it the same way
+        return type(self)(self.h.permute(1, 2, 0).clone().permute(2, 0, 1), self.prev_choice.t().clone().t(),
+                          self.prev_reward.clone())
+
+    def numpy(self):
+        """A host copy, contiguous [N, ...] numpy arrays."""
+        return type(self)(np.ascontiguousarray(to_numpy(self.h), np.float32), np.ascontiguousarray(to_numpy(self.prev_choice), np.int32),
+                          np.ascontiguousarray(to_numpy(self.prev_reward), np.float32).copy())
+
+    def observed(self, reward):
+        """The numpy carry after the env step that followed `reference`: prev_reward = float32(reward), the rest kept."""
+        out = self.numpy()
+        r = to_numpy(reward).astype(np.float32)
+        if r.shape != (self.num_envs,):
+            raise ValueError("reward must have shape (%d,), got %s" % (self.num_envs, r.shape))
+        out.prev_reward = r
+        return out
+
+
+class LiftRecurrentPolicy(LiftPolicy):
+    """P recurrent dispatcher networks: LiftPolicy's ws, we, wt, wr, wu, wd, b, wo, bo and wc [P, H, A] (the previous choice, a
+    lookup), wq [P, H] (the previous reward), wh [P, H, H] (the recurrence), all float32 and finite. The module docstring
+    defines the arithmetic."""
+    NAMES = ("ws", "we", "wt", "wr", "wu", "wd", "b", "wo", "bo", "wc", "wq", "wh")
+
+    def __init__(self, ws, we, wt, wr, wu, wd, wc, wq, wh, b, wo, bo, scale=None):
+        LiftPolicy.__init__(self, ws, we, wt, wr, wu, wd, b, wo, bo, scale)
+        wc, wq, wh = f32_array("wc", wc, 3), f32_array("wq", wq, 2), f32_array("wh", wh, 3)
+        P, H, A = self.num_policies, self.hidden, self.choices
+        for name, a, shape in (("wc", wc, (P, H, A)), ("wq", wq, (P, H)), ("wh", wh, (P, H, H))):
+            if a.shape != shape:
+                raise ValueError("shapes must be wc [P,H,A], wq [P,H], wh [P,H,H] with A = 2F + 2; %s is %s, not %s"
+                                 % (name, a.shape, shape))
+        self.wc, self.wq, self.wh = wc, wq, wh
+
+    @property
+    def param_count(self):
+        return recurrent_param_count(self.hidden, self.floors, self.elevators)
+
+    def pack(self):
+        """float32 [P, param_count]: the layout the kernel reads (include/metagym_hip.h, mg_liftsim_rpolicy). Per hidden unit
+        j a record of RU floats: b[j] wq[j] 0 0 | ws[j] | we[j] | wt[j] | wr[j] | wu[j] | wd[j] | wc[j] | wh[j], each group
+        zero-padded to a multiple of four floats; then per choice c the MLP's record of 4 + HP floats."""
+        P, H, F, E, A = self.num_policies, self.hidden, self.floors, self.elevators, self.choices
+        groups, ru = recurrent_unit_groups(H, F, E)
+        rc = 4 + pad4(H)
+        out = np.zeros((P, self.param_count), np.float32)
+        unit = out[:, :H * ru].reshape(P, H, ru)
+        for name, o, n in groups:
+            unit[:, :, o:o + n] = getattr(self, name).reshape(P, H, n)
+        choice = out[:, H * ru:].reshape(P, A, rc)
+        choice[:, :, 0] = self.bo
+        choice[:, :, 4:4 + H] = self.wo
+        return out
+
+    @classmethod
+    def unpack(cls, packed, hidden, floors, elevators, scale=None):
+        """The inverse of `pack`."""
+        packed = f32_array("packed", packed, 2)
+        H, F, E = _check_sizes(hidden, floors, elevators)
+        P, A = packed.shape[0], 2 * F + 2
+        if packed.shape[1] != recurrent_param_count(H, F, E):
+            raise ValueError("packed has shape %s, hidden=%d floors=%d elevators=%d need [P, %d]"
+                             % (packed.shape, H, F, E, recurrent_param_count(H, F, E)))
+        groups, ru = recurrent_unit_groups(H, F, E)
+        rc = 4 + pad4(H)
+        unit = packed[:, :H * ru].reshape(P, H, ru)
+        choice = packed[:, H * ru:].reshape(P, A, rc)
+        g = {name: unit[:, :, o:o + n].copy() for name, o, n in groups}
+        return cls(g["ws"], g["we"], g["wt"], g["wr"], g["wu"], g["wd"], g["wc"], g["wq"][:, :, 0].copy(), g["wh"],
+                   g["b"][:, :, 0].copy(), choice[:, :, 4:4 + H].copy(), choice[:, :, 0].copy(), scale)
+
+    def _gather(self, ids):
+        key = ids.tobytes()
+        if self._gathered is None or self._gathered[0] != key:
+            self._gathered = (key, tuple(getattr(self, name)[ids] for name in self.NAMES))
+        return self._gathered[1]
+
+    def reference(self, policy_ids, obs, state, return_choices=False):
+        """One step of the definition in numpy float32, vectorised over envs, elevators and units. policy_ids [n]; obs: the
+        arrays of `env.observation()` for n buildings; state: their `LiftPolicyState` (torch or numpy; not modified).
+        Returns the int32 [n, 2E] actions, ready for `env.step`, and the new numpy carry: h and prev_choice are this
+        step's, prev_reward is still the old one, since it comes from the env step that follows
+        (`LiftPolicyState.observed`). With `return_choices` also the int32 [n, E] choices, as a third value."""
+        ids = to_numpy(policy_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("policy_ids must be a vector of integers")
+        n = ids.shape[0]
+        if n and (int(ids.min()) < 0 or int(ids.max()) >= self.num_policies):
+            raise ValueError("policy_ids must be in [0, %d)" % self.num_policies)
+        ids = ids.astype(np.int64)
+        if not isinstance(state, LiftPolicyState):
+            raise TypeError("state must be a LiftPolicyState, got %s" % type(state).__name__)
+        E, H, A = self.elevators, self.hidden, self.choices
+        st = state.numpy()
+        if st.h.shape != (n, E, H) or st.prev_choice.shape != (n, E) or st.prev_reward.shape != (n,):
+            raise ValueError("state must hold h [%d, %d, %d], prev_choice [%d, %d] and prev_reward [%d]" % (n, E, H, n, E, n))
+        if n and (int(st.prev_choice.min()) < -1 or int(st.prev_choice.max()) >= A):
+            raise ValueError("state.prev_choice must be in [-1, %d)" % A)
+        x, d, reserved, up, down = self.inputs(obs)
+        if x.shape[0] != n:
+            raise ValueError("policy_ids holds %d ids, the observation %d buildings" % (n, x.shape[0]))
+        z = self.preactivations(ids, x, d, reserved, up, down)
+        wo, bo, wc, wq, wh = self._gather(ids)[7:]
+        one = np.float32(1.0)
+        pc, pr, h = st.prev_choice.astype(np.int64), st.prev_reward, st.h
+        with np.errstate(all="ignore"):
+            chosen = pc >= 0
+            looked = wc.transpose(0, 2, 1)[np.arange(n)[:, None], np.where(chosen, pc, 0)]       # [n, E, H]
+            z = np.where(chosen[:, :, None], z + looked, z)
+            z = z + wq[:, None, :] * pr[:, None, None]
+            for i in range(H):
+                z = z + wh[:, None, :, i] * h[:, :, i:i + 1]
+            hn = np.where(z > one, one, np.where(z < -one, -one, z))
+            logits = np.broadcast_to(bo[:, None, :], (n, E, A)).copy()
+            for j in range(H):
+                logits = logits + wo[:, None, :, j] * hn[:, :, j:j + 1]
+            choice = np.zeros((n, E), np.int32)
+            best = logits[:, :, 0].copy()
+            for c in range(1, A):
+                better = logits[:, :, c] > best
+                choice = np.where(better, np.int32(c), choice)
+                best = np.where(better, logits[:, :, c], best)
+        assert z.dtype == np.float32 and hn.dtype == np.float32 and logits.dtype == np.float32
+        actions = self.actions_of(choice, self.floors).reshape(n, 2 * E)
+        new = LiftPolicyState(np.ascontiguousarray(hn), choice.astype(np.int32), st.prev_reward.copy())
+        return (actions, new, choice) if return_choices else (actions, new)
