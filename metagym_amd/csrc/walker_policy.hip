@@ -1,14 +1,13 @@
 // walker_policy.hip — MetaLocomotion closed-loop rollouts: per-env MLP policies inside the launch (mg_walker_policy_*).
 //
-// A translation unit of its own, like quadrotor_policy.hip and for the same reason: it takes walker.hip's wave kernel, layout
-// and wave_plan by including it with MG_WALKER_POLICY_ONLY, and instantiates the third form of walker_step_wave_kernel
-// (WAVE_POLICY) for every shape wave_plan can pick. walker.hip itself compiles the step and the rollout forms from the text
-// they were compiled from before, and the two files build in parallel. Same flags (metagym_amd/build.py) and the same
-// contraction pragmas: walker.hip lets the compiler fuse a*b+c in the physics, which is one shared text, so the policy form's
-// physics is the step's bit for bit; wave_policy_action is compiled with contraction off, which is what makes the policy
-// definition of include/metagym_hip.h hold (one rounding per operation).
-#define MG_WALKER_POLICY_ONLY
-#include "walker.hip"
+// A translation unit of its own, like quadrotor_policy.hip and for the same reason: it takes the wave kernel, its layout and
+// wave_plan from walker_core.h, and wave_plan<WAVE_POLICY> instantiates the third form of walker_step_wave_kernel for every
+// shape it can pick, and no other form. walker.hip compiles the step and the rollout forms from the same header, and the files
+// build in parallel. Same flags (metagym_amd/build.py) and the same contraction pragmas: the header lets the compiler fuse
+// a*b+c in the physics, which is one shared text, so the policy form's physics is the step's bit for bit; wave_policy_action
+// is compiled with contraction off, which is what makes the policy definition of include/metagym_hip.h hold (one rounding
+// per operation).
+#include "walker_core.h"
 
 namespace {
 
@@ -22,11 +21,7 @@ int policy_count(int hidden, int obs_dim, int n_act) {
 }  // namespace
 
 extern "C" int32_t mg_walker_policy_param_count(int32_t hidden, int32_t obs_dim, int32_t n_act) {
-    if (hidden < 0 || hidden > WAVE_POLICY_MAX_HIDDEN)
-        return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d is outside [0, %d]", hidden, WAVE_POLICY_MAX_HIDDEN);
-    if (n_act < 1 || n_act > NJ || obs_dim < 1 || obs_dim > 8 + 2 * NJ + MG_WALKER_MAX_FEET)
-        return mg::set_error(MG_ERR_BAD_SIZE, "n_act=%d (want 1..%d), obs_dim=%d (want 1..%d)", n_act, NJ, obs_dim,
-                             8 + 2 * NJ + MG_WALKER_MAX_FEET);
+    if (int rc = check_walker_policy_sizes(hidden, 0, WAVE_POLICY_MAX_HIDDEN, obs_dim, n_act)) return rc;
     return policy_count(hidden, obs_dim, n_act);
 }
 
@@ -36,17 +31,9 @@ extern "C" int mg_walker_policy_rollout(const mg_walker_topology *tp, const mg_w
                                         double *ret_episode, int32_t *episode_len, float *actions, float *reward, float *rewards5,
                                         uint8_t *done, void *stream) {
     if (int rc = check_walker(tp, ms, prm, st, n)) return rc;
-    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_walker_policy_rollout: n_steps=%d (want >= 1)", n_steps);
-    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "mg_walker_policy_rollout: obs_every=%d (want 0 or k >= 1)", obs_every);
-    if (prm->mapping == 0)
-        return mg::set_error(MG_ERR_UNSUPPORTED, "mg_walker_policy_rollout: mapping = lane is the single-step cross-check path; "
-                             "rollouts need the wave mapping");
-    if (prm->actuation != 0)
-        return mg::set_error(MG_ERR_UNSUPPORTED, "mg_walker_policy_rollout: actuation = %d (the policy's output is a torque action, "
-                             "actuation = 0)", prm->actuation);
-    if (prm->substep_log != nullptr)
-        return mg::set_error(MG_ERR_BAD_CONFIG, "mg_walker_policy_rollout: substep_log holds one launch's sub-steps; leave it NULL");
-    if (int rc = check_walker_terrain(prm)) return rc;
+    if (int rc = check_walker_rollout("mg_walker_policy_rollout", prm, n_steps, obs_every,
+                                      "the policy's output is a torque action, actuation = 0"))
+        return rc;
     MG_REQUIRE_PTR(policy);
     if (policy->params_d == nullptr || policy->policy_id_d == nullptr)
         return mg::set_error(MG_ERR_NULL_POINTER, "mg_walker_policy has a NULL params_d or policy_id_d");
@@ -64,14 +51,14 @@ extern "C" int mg_walker_policy_rollout(const mg_walker_topology *tp, const mg_w
                              policy->obs_dim, obs_dim);
     if (policy->n_act != tp->n_joints || tp->n_joints < 1)
         return mg::set_error(MG_ERR_BAD_CONFIG, "mg_walker_policy: n_act=%d, the topology has %d joints", policy->n_act, tp->n_joints);
-    WaveLaunch w;
+    WaveLaunch<WAVE_POLICY> w;
     if (int rc = wave_plan(tp, prm, st, &w, policy->hidden)) return rc;
     mg::DeviceGuard guard(mg::device_of(st->pos));
     const WavePlanArgs a = pack(w.plan);
     const WaveRoll<WAVE_POLICY> roll{n_steps, obs_every, policy->params_d, policy->policy_id_d, policy->n_policies, policy->hidden,
                                      policy_count(policy->hidden, obs_dim, tp->n_joints), obs0, actions, ret_total, ret_episode,
                                      episode_len};
-    hipLaunchKernelGGL(w.policy, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan,
+    hipLaunchKernelGGL(w.kernel, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan,
                        (const float *)nullptr, obs, reward, rewards5, done, roll);
     return mg::check_launch("walker_step_wave_kernel (policy rollout)");
 }

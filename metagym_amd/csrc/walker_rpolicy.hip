@@ -1,15 +1,12 @@
 // walker_rpolicy.hip — MetaLocomotion closed-loop rollouts with recurrent policies and a carry (mg_walker_rpolicy_*).
 //
-// A translation unit of its own, like walker_policy.hip and for the same reason: it takes walker.hip's wave kernel, layout and
-// wave_plan by including it with MG_WALKER_POLICY_ONLY (none of the other kernels or entry points) and MG_WALKER_RPOLICY_ONLY
-// (wave_use picks the fourth form), and instantiates walker_step_wave_kernel<NMAX, SH, WAVE_RPOLICY> for every shape wave_plan
-// can pick. walker.hip and walker_policy.hip compile their forms from the text they were compiled from before, and the three
-// files build in parallel. Same flags (metagym_amd/build.py) and the same contraction pragmas: the physics is the one shared
-// text, fused as in the step; wave_rpolicy_action is compiled with contraction off, which is what makes the definition of
-// include/metagym_hip.h hold (one rounding per operation).
-#define MG_WALKER_POLICY_ONLY
-#define MG_WALKER_RPOLICY_ONLY
-#include "walker.hip"
+// A translation unit of its own, like walker_policy.hip and for the same reason: it takes the wave kernel, its layout and
+// wave_plan from walker_core.h, and wave_plan<WAVE_RPOLICY> instantiates walker_step_wave_kernel<NMAX, SH, WAVE_RPOLICY> for
+// every shape it can pick, and no other form. walker.hip and walker_policy.hip compile their forms from the same header, and
+// the three files build in parallel. Same flags (metagym_amd/build.py) and the same contraction pragmas: the physics is the
+// one shared text, fused as in the step; wave_rpolicy_action is compiled with contraction off, which is what makes the
+// definition of include/metagym_hip.h hold (one rounding per operation).
+#include "walker_core.h"
 
 namespace {
 
@@ -24,11 +21,7 @@ int rpolicy_count(int hidden, int obs_dim, int n_act) {
 }  // namespace
 
 extern "C" int32_t mg_walker_rpolicy_param_count(int32_t hidden, int32_t obs_dim, int32_t n_act) {
-    if (hidden < 1 || hidden > WAVE_RPOLICY_MAX_HIDDEN)
-        return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d is outside [1, %d]", hidden, WAVE_RPOLICY_MAX_HIDDEN);
-    if (n_act < 1 || n_act > NJ || obs_dim < 1 || obs_dim > 8 + 2 * NJ + MG_WALKER_MAX_FEET)
-        return mg::set_error(MG_ERR_BAD_SIZE, "n_act=%d (want 1..%d), obs_dim=%d (want 1..%d)", n_act, NJ, obs_dim,
-                             8 + 2 * NJ + MG_WALKER_MAX_FEET);
+    if (int rc = check_walker_policy_sizes(hidden, 1, WAVE_RPOLICY_MAX_HIDDEN, obs_dim, n_act)) return rc;
     return rpolicy_count(hidden, obs_dim, n_act);
 }
 
@@ -39,17 +32,9 @@ extern "C" int mg_walker_rpolicy_rollout(const mg_walker_topology *tp, const mg_
                                          int32_t *episode_len, float *actions, float *reward, float *rewards5, uint8_t *done,
                                          void *stream) {
     if (int rc = check_walker(tp, ms, prm, st, n)) return rc;
-    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_walker_rpolicy_rollout: n_steps=%d (want >= 1)", n_steps);
-    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "mg_walker_rpolicy_rollout: obs_every=%d (want 0 or k >= 1)", obs_every);
-    if (prm->mapping == 0)
-        return mg::set_error(MG_ERR_UNSUPPORTED, "mg_walker_rpolicy_rollout: mapping = lane is the single-step cross-check path; "
-                             "rollouts need the wave mapping");
-    if (prm->actuation != 0)
-        return mg::set_error(MG_ERR_UNSUPPORTED, "mg_walker_rpolicy_rollout: actuation = %d (the policy's output is a torque action, "
-                             "actuation = 0)", prm->actuation);
-    if (prm->substep_log != nullptr)
-        return mg::set_error(MG_ERR_BAD_CONFIG, "mg_walker_rpolicy_rollout: substep_log holds one launch's sub-steps; leave it NULL");
-    if (int rc = check_walker_terrain(prm)) return rc;
+    if (int rc = check_walker_rollout("mg_walker_rpolicy_rollout", prm, n_steps, obs_every,
+                                      "the policy's output is a torque action, actuation = 0"))
+        return rc;
     MG_REQUIRE_PTR(policy);
     if (policy->params_d == nullptr || policy->policy_id_d == nullptr)
         return mg::set_error(MG_ERR_NULL_POINTER, "mg_walker_policy has a NULL params_d or policy_id_d");
@@ -74,15 +59,15 @@ extern "C" int mg_walker_rpolicy_rollout(const mg_walker_topology *tp, const mg_
                              policy->obs_dim, obs_dim);
     if (policy->n_act != tp->n_joints || tp->n_joints < 1)
         return mg::set_error(MG_ERR_BAD_CONFIG, "mg_walker_policy: n_act=%d, the topology has %d joints", policy->n_act, tp->n_joints);
-    WaveLaunch w;
-    if (int rc = wave_plan(tp, prm, st, &w, policy->hidden, true)) return rc;
+    WaveLaunch<WAVE_RPOLICY> w;
+    if (int rc = wave_plan(tp, prm, st, &w, policy->hidden)) return rc;
     mg::DeviceGuard guard(mg::device_of(st->pos));
     const WavePlanArgs a = pack(w.plan);
     const WaveRoll<WAVE_RPOLICY> roll{n_steps, obs_every, policy->params_d, policy->policy_id_d, policy->n_policies, policy->hidden,
                                       rpolicy_count(policy->hidden, obs_dim, tp->n_joints), obs0, actions, ret_total, ret_episode,
                                       episode_len, carry->h, carry->prev_action, carry->prev_reward, carry->prev_done,
                                       episodic != 0 ? 1 : 0};
-    hipLaunchKernelGGL(w.rpolicy, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan,
+    hipLaunchKernelGGL(w.kernel, dim3(n), dim3(WV), w.lds, (hipStream_t)stream, *tp, *ms, *prm, *st, n, a.rows, a.scan,
                        (const float *)nullptr, obs, reward, rewards5, done, roll);
     return mg::check_launch("walker_step_wave_kernel (recurrent policy rollout)");
 }

@@ -246,7 +246,7 @@ def tangent_basis(nrm):
     return t1, np.cross(nrm, t1)
 
 
-MAX_CANDIDATES = 48     # contact candidates collected per sub-step before the selection (walker.hip W_MAXCAND): later ones are dropped
+MAX_CANDIDATES = 48     # contact candidates collected per sub-step before the selection (walker_core.h W_MAXCAND): later ones are dropped
 
 
 def contact_bias(depth, prm):

@@ -4,7 +4,7 @@
  *
  * PARITY UNPINNED like everything on this path: the reference calls pybullet.stepSimulation()
  * (metalocomotion/envs/utils/scene_bases.py:45-50), which is not in its tree. What is restated is this repo's own engine,
- * the algorithm of metagym_amd/csrc/walker.hip's wave kernel step for step — composite-rigid-body M and bias about the
+ * the algorithm of metagym_amd/csrc/walker_core.h's wave kernel step for step — composite-rigid-body M and bias about the
  * base origin, Cholesky, free motion, ground / self-collision / joint-limit rows, projected Gauss-Seidel in Cholesky-whitened
  * velocities, semi-implicit Euler — so the flop count is that of the algorithm the GPU executes (the kernel reaches the
  * same kinematics and subtree sums by parallel scans, which spend redundant lane-operations a serial count does not have:
@@ -186,7 +186,7 @@ int wo_substep(const wo_model *m, const wo_params *prm, wo_state *s, const doubl
     kin_t k;
     const int damped = prm->body_linear_damping != 0.0 || prm->body_angular_damping != 0.0;
     kinematics(m, s, &k, damped ? 2 : 1);
-    /* ---- M and h by the composite-rigid-body algorithm about the base origin O (walker.hip wave_substep) ---- */
+    /* ---- M and h by the composite-rigid-body algorithm about the base origin O (walker_core.h wave_substep) ---- */
     double comp[WO_MAX_BODIES][16];
     const v3 O = k.o[0];
     for (int b = 0; b < NB; ++b) {
@@ -203,7 +203,7 @@ int wo_substep(const wo_model *m, const wo_params *prm, wo_state *s, const doubl
         v3 F = vscale(mass, V(a_c.x, a_c.y, a_c.z + prm->gravity));
         v3 N = vadd(mulMv(Ic, al), vcross(w, mulMv(Ic, w)));
         if (damped) {   /* btMultiBody's velocity damping: force -m v_c (k + k |v_c|) at the centre of mass, torque -I w (k + k |w|);
-                         * their negatives join the bias wrench (walker.hip wave_substep, oracle/abd.py mass_matrix_and_bias) */
+                         * their negatives join the bias wrench (walker_core.h wave_substep, oracle/abd.py mass_matrix_and_bias) */
             const v3 vc = vadd(k.fvr[b], vcross(w, rx));
             const double kl = prm->body_linear_damping, ka = prm->body_angular_damping;
             FL(F_SQRT, 2); FL(F_MUL, 3); FL(F_ADD, 2);

@@ -11,7 +11,7 @@
 #define WO_MAX_GEOMS 24
 #define WO_MAX_PAIRS 128
 #define WO_MAX_CONTACTS 12
-#define WO_MAX_CANDIDATES 48       /* abd.MAX_CANDIDATES, walker.hip W_MAXCAND */
+#define WO_MAX_CANDIDATES 48       /* abd.MAX_CANDIDATES, walker_core.h W_MAXCAND */
 #define WO_MAX_ROWS (3 * WO_MAX_CONTACTS + WO_MAX_JOINTS)
 
 typedef struct wo_model {            /* topology (mg_walker_topology) + one row of the model table (mg_walker_models) */

@@ -4,7 +4,7 @@
     scripts/isa_diff.py OTHER_TREE [unit.hip ...] [--keep DIR]
 
 OTHER_TREE is a checkout of the commit to compare against (git worktree add --detach DIR REV). Every unit (default: the
-four env families and their closed-loop units) is compiled device-only to assembly in both trees, each with its own
+five env families and their closed-loop units) is compiled device-only to assembly in both trees, each with its own
 metagym_amd/build.py's flags for that file. A kernel's stream is the text between its label and its end label with
 comments stripped, local labels renumbered in order of appearance and whitespace squeezed. One line per kernel:
 
@@ -22,7 +22,7 @@ import tempfile
 
 UNITS = ["bandits.hip", "bandits_policy.hip", "bandits_learner.hip", "liftsim.hip", "liftsim_policy.hip", "maze.hip",
          "maze_policy.hip", "maze_expert.hip", "maze3d_policy.hip", "quadrotor.hip", "quadrotor_tasks.hip",
-         "quadrotor_policy.hip"]
+         "quadrotor_policy.hip", "walker.hip", "walker_policy.hip", "walker_rpolicy.hip"]
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 

@@ -13,7 +13,7 @@ import numpy as np
 
 from metagym_amd._policy import pad4 as _pad4
 
-GROUP = 32          # RP_H_GROUP (csrc/quadrotor_policy.hip) and MG_WALKER_RP_GROUP (csrc/walker.hip), their defaults
+GROUP = 32          # RP_H_GROUP (csrc/quadrotor_policy.hip) and MG_WALKER_RP_GROUP (csrc/walker_core.h), their defaults
 WAVE = 64
 N, P, T = 130, 3, 12          # two waves and a 2-lane tail; lanes 0..63 on one policy id, the rest mixed (layout_ids)
 WALKER_N, WALKER_T = 65, 6    # one workgroup per env

@@ -1,6 +1,6 @@
 """CPU: the two forms of the engine's projected Gauss-Seidel sweep give the same iterates.
 
-metagym_amd/csrc/walker.hip sweeps the constraint rows either in whitened VELOCITY space (row r: Jh_r . y by a reduction, the
+metagym_amd/csrc/walker_core.h sweeps the constraint rows either in whitened VELOCITY space (row r: Jh_r . y by a reduction, the
 projected multiplier update, y += Jh_r^T dlambda — what oracle/abd.py and oracle/walker_oracle.c restate) or, since round 4, in
 MULTIPLIER space in delta form (delassus_sweep: A = Jh Jh^T once, g = Jh y kept current by g += A[:, r] dlambda_r; every lane
 forms the change d of its own multiplier, projects it onto its own bounds — normal / joint-limit rows lambda >= 0, friction rows
@@ -13,7 +13,7 @@ import pytest
 
 
 def sweep_velocity_space(Jh, y, bias, mu, ncont, iters):
-    """walker.hip `row_step`: rows 3c, 3c+1, 3c+2 = contact c's normal and two friction rows, the rest joint limits."""
+    """walker_core.h `row_step`: rows 3c, 3c+1, 3c+2 = contact c's normal and two friction rows, the rest joint limits."""
     nr, n = Jh.shape
     y = y.copy()
     lam = np.zeros(nr)
@@ -41,7 +41,7 @@ def sweep_velocity_space(Jh, y, bias, mu, ncont, iters):
 
 
 def sweep_multiplier_space(Jh, y, bias, mu, ncont, iters, unroll=6):
-    """walker.hip `delassus_sweep` and the block around it: delta form, KR = the row count rounded up to a multiple of `unroll`."""
+    """walker_core.h `delassus_sweep` and the block around it: delta form, KR = the row count rounded up to a multiple of `unroll`."""
     nr, n = Jh.shape
     KR = (nr + unroll - 1) // unroll * unroll
     A = np.zeros((KR, KR))

@@ -1,4 +1,4 @@
-"""The kinematics-as-scans algorithm of the walker wave kernel (metagym_amd/csrc/walker.hip: wave_kinematics and the scan
+"""The kinematics-as-scans algorithm of the walker wave kernel (metagym_amd/csrc/walker_core.h: wave_kinematics and the scan
 tables its prologue builds), restated in numpy and checked against the plain serial recursion on random kinematic trees —
 no GPU needed. What is pinned here is the ALGORITHM and its table / round-count logic (the 2^r-th-ancestor tables over
 "hops", the joint tree, ceil(log2) round counts as mg_walker_step computes them); the device code itself is checked against

@@ -2,7 +2,7 @@
 numpy oracle's verdict on every table row) and tests/test_walker_edges_gpu.py (the HIP kernels on the same rows). Nothing here
 needs a GPU.
 
-The fused auto-reset draws the joint angles of a restarted env from Philox4x32-10 (csrc/walker.hip, reset_joint_noise):
+The fused auto-reset draws the joint angles of a restarted env from Philox4x32-10 (csrc/walker_core.h, reset_joint_noise):
     counter  c0 = gid lo, c1 = step lo, c2 = step hi ^ (gid hi << 8), c3 = 0x57414c4b + j / 4      (gid = env_id_base + e)
     key      seed lo, seed hi
     value    -0.1 + 0.2 * (word[j & 3] * 2^-32)        in float64
