@@ -1,7 +1,8 @@
-// mg_closed_loop.h — what the closed-loop translation units (maze_policy, maze_expert, maze3d_policy, liftsim_policy, liftsim_rpolicy) repeat
-// around their own arithmetic: an index clamp, the exploration draw, the staging of a wave's one policy in LDS, and on the
-// host the LDS limit and the opt-in above 64 KiB. bandits_policy takes the two host helpers only (its kernel keeps its own
-// staging and draw); bandits_learner does not include it. Not included by mg_common.h.
+// mg_closed_loop.h — what the closed-loop translation units (maze_policy, maze_expert, maze3d_policy, and liftsim_policy and
+// liftsim_rpolicy through liftsim_policy_core.h) repeat around their own arithmetic: an index clamp, the exploration draw,
+// the staging of a wave's one policy in LDS, and on the host the LDS limit and the opt-in above 64 KiB. bandits_policy takes
+// the two host helpers only (its kernel keeps its own staging and draw); bandits_learner does not include it. Not included
+// by mg_common.h.
 #pragma once
 #include "mg_common.h"
 #include "mg_philox.h"

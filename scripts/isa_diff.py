@@ -20,9 +20,9 @@ import subprocess
 import sys
 import tempfile
 
-UNITS = ["bandits.hip", "bandits_policy.hip", "bandits_learner.hip", "liftsim.hip", "liftsim_policy.hip", "maze.hip",
-         "maze_policy.hip", "maze_expert.hip", "maze3d_policy.hip", "quadrotor.hip", "quadrotor_tasks.hip",
-         "quadrotor_policy.hip", "walker.hip", "walker_policy.hip", "walker_rpolicy.hip"]
+UNITS = ["bandits.hip", "bandits_policy.hip", "bandits_learner.hip", "liftsim.hip", "liftsim_policy.hip",
+         "liftsim_rpolicy.hip", "maze.hip", "maze_policy.hip", "maze_expert.hip", "maze3d_policy.hip", "quadrotor.hip",
+         "quadrotor_tasks.hip", "quadrotor_policy.hip", "walker.hip", "walker_policy.hip", "walker_rpolicy.hip"]
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 

@@ -132,10 +132,10 @@ BANDITS_SEEDS = {(5, 2): 41, (4, 4): 42, (7, 6): 43, (63, 7): 44, (6, 63): 45}
 
 
 # ---------------------------------------------------------------------------------------------- liftsim
-# lp_eval: units four at a time (records clamped with min(j + u, hidden - 1), stores guarded with j + u < hidden); choices
-# four at a time (A = 2F + 2: A % 4 is 2 for an even F and 0 for an odd one, and every older case has an even F); inside,
-# the guarded quad over h. F and E pad the groups we | wt | wr | wu | wd, and F sets the words of the three floor sets
-# (nb = min(32, F - 32 w) bits each). size = (F, E, H).
+# lp_eval: units four at a time (unit_heads of liftsim_policy_core.h clamps the records with min(j + u, hidden - 1), lp_eval
+# guards the stores with j + u < hidden); argmax_choice of that header: choices four at a time (A = 2F + 2: A % 4 is 2 for an
+# even F and 0 for an odd one, and every older case has an even F); inside, the guarded quad over h. F and E pad the groups
+# we | wt | wr | wu | wd, and F sets the words of the three floor sets (nb = min(32, F - 32 w) bits each). size = (F, E, H).
 def liftsim_paths(size):
     F, E, H = size
     paths = _quad_walk(H, prefix="logit_")
