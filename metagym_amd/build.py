@@ -126,5 +126,49 @@ def build(force=False, verbose=True, extra_flags=()):
     return LIB_PATH
 
 
+# The host half of every translation unit (argument validation, plan folding, LDS sizing, topology checks) under ASan + UBSan:
+# -Xarch_host keeps the sanitizers off the device code, which is compiled as usual and never runs in this build.
+HOST_CHECK_FLAGS = ["-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"]
+HOST_CHECK_MAIN = os.path.join(os.path.dirname(HERE), "tests", "host_san", "host_paths.cpp")
+
+
+def build_host_checked(out_dir, verbose=False):
+    """Compile every csrc/*.hip with the normal flags (FILE_FLAGS kept) plus HOST_CHECK_FLAGS into `out_dir`/obj and link the
+    objects with tests/host_san/host_paths.cpp — a program with its own main that walks the library's host-only paths — into
+    `out_dir`/host_paths. Only stale objects are compiled again (object_is_stale; a change of flags recompiles all). Nothing
+    under metagym_amd/lib/ is read or written. Returns the executable's path."""
+    out_dir = os.path.abspath(out_dir)         # the compilers run in the sources' directories
+    obj_dir = os.path.join(out_dir, "obj")
+    os.makedirs(obj_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "host_paths")
+    recipe = os.path.abspath(__file__)
+    flags_file = os.path.join(obj_dir, "flags.txt")
+    flags_now = " ".join(COMPILE_FLAGS + HOST_CHECK_FLAGS) + " | " + repr(sorted(FILE_FLAGS.items()))
+    same_flags = os.path.exists(flags_file) and open(flags_file).read() == flags_now
+    units = [(src, COMPILE_FLAGS + FILE_FLAGS.get(os.path.basename(src), []), CSRC) for src in sources()]
+    units.append((HOST_CHECK_MAIN, ["--offload-arch=gfx950", "-std=c++17", "-Wall", "-I", os.path.join(os.path.dirname(HERE), "include")], os.path.dirname(HOST_CHECK_MAIN)))
+    jobs, objects = [], []
+    for src, flags, cwd in units:
+        obj = os.path.join(obj_dir, os.path.splitext(os.path.basename(src))[0] + ".o")
+        objects.append(obj)
+        if not same_flags or object_is_stale(obj, obj + ".d", cwd, recipe):
+            cmd = [HIPCC] + flags + HOST_CHECK_FLAGS + ["-MD", "-MF", obj + ".d", "-c", src, "-o", obj]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            jobs.append((cmd, subprocess.Popen(cmd, cwd=cwd)))
+    for cmd, proc in jobs:
+        if proc.wait() != 0:
+            raise subprocess.CalledProcessError(proc.returncode, cmd)
+    with open(flags_file, "w") as f:
+        f.write(flags_now)
+    if jobs or not os.path.exists(exe) or any(os.path.getmtime(o) > os.path.getmtime(exe) for o in objects):
+        cmd = [HIPCC, "--offload-arch=gfx950"] + HOST_CHECK_FLAGS[2:] + objects + ["-o", exe + ".tmp"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+        os.replace(exe + ".tmp", exe)
+    return exe
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)

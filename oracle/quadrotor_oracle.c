@@ -417,14 +417,21 @@ static void py_slice(long a, long b, long len, long *lo, long *hi) {
     *lo = a; *hi = b;
 }
 
+/* (long)x is undefined in C for a NaN and for values outside long's range (UBSan: float-cast-overflow). The reference raises there
+ * (math.floor of a NaN or an infinity); x86-64's conversion returns LONG_MIN, which is what this file has always computed for the
+ * state of an env whose position is no longer finite. Kept, as a defined result. */
+static long to_long(double x) {
+    return (x >= -9223372036854775808.0 && x < 9223372036854775808.0) ? (long)x : (long)(-9223372036854775807L - 1);
+}
+
 static int collision(const qo_consts *c, const double old_pos[3], const double new_pos[3]) {
     long mn[3], mx[3];
     for (int i = 0; i < 3; ++i) {
         double lo = old_pos[i] < new_pos[i] ? old_pos[i] : new_pos[i];  /* min(x[i], y[i]) */
         double hi = old_pos[i] > new_pos[i] ? old_pos[i] : new_pos[i];
         /* python min/max return the first argument on ties; values equal either way */
-        mn[i] = (long)floor(lo);
-        mx[i] = (long)ceil(hi);
+        mn[i] = to_long(floor(lo));
+        mx[i] = to_long(ceil(hi));
     }
     int any = 0;
     if (c->map) {

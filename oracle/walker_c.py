@@ -43,16 +43,27 @@ class Env(C.Structure):
 _libs = {}
 
 
+# the library's own flags (oracle/Makefile: FPFLAGS); sin / cos / fmin / fmax stay library calls there and here
+COUNT_FLAGS = ["-O2", "-fPIC", "-std=c11", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-fno-builtin-sin", "-fno-builtin-cos",
+               "-fno-builtin-fmin", "-fno-builtin-fmax", "-DWO_COUNT_FLOPS"]
+
+
+def build_count():
+    """Build libwalker_oracle_count.so (walker_oracle.c alone, -DWO_COUNT_FLOPS) if it is older than its source or than this
+    file, which holds its flags; returns its path."""
+    out = os.path.join(_HERE, "libwalker_oracle_count.so")
+    src = os.path.join(_HERE, "walker_oracle.c")
+    if not os.path.exists(out) or max(os.path.getmtime(src), os.path.getmtime(os.path.abspath(__file__))) > os.path.getmtime(out):
+        subprocess.check_call(["gcc"] + COUNT_FLAGS + ["-shared", "-o", out, src, "-lm"])
+    return out
+
+
 def load(count_flops=False):
     """The oracle library (built with the other *_oracle.c files); `count_flops=True`: a second build of walker_oracle.c
     alone with -DWO_COUNT_FLOPS (every arithmetic helper bumps a counter)."""
     if count_flops not in _libs:
         if count_flops:
-            out = os.path.join(_HERE, "libwalker_oracle_count.so")
-            src = os.path.join(_HERE, "walker_oracle.c")
-            if not os.path.exists(out) or os.path.getmtime(src) > os.path.getmtime(out):
-                subprocess.check_call(["gcc", "-O2", "-fPIC", "-std=c11", "-mfma", "-ffp-contract=off", "-DWO_COUNT_FLOPS", "-shared",
-                                       "-o", out, src, "-lm"])
+            out = build_count()
             lib = C.CDLL(out)
         else:
             lib = C.CDLL(_q.build())

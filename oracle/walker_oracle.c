@@ -27,6 +27,16 @@ unsigned long long wo_flop_count[9];      /* add/sub, mul, fma (counts once), di
 #else
 #define FL(k, n) ((void)0)
 #endif
+#ifdef WO_COUNT_CAPS
+unsigned long long wo_cap_count[4];       /* how close the fixed-size contact tables came to their caps (oracle/replay_main.c prints them): [0] most
+                                           * candidates in one sub-step, [1] ground candidates dropped because the candidate table was full,
+                                           * [2] self-collision pairs left untested for the same reason, [3] most contacts kept in one sub-step */
+#define CAP(k, n) (wo_cap_count[k] += (unsigned long long)(n))
+#define CAP_MAX(k, n) (wo_cap_count[k] = wo_cap_count[k] > (unsigned long long)(n) ? wo_cap_count[k] : (unsigned long long)(n))
+#else
+#define CAP(k, n) ((void)0)
+#define CAP_MAX(k, n) ((void)0)
+#endif
 enum { F_ADD = 0, F_MUL = 1, F_FMA = 2, F_DIV = 3, F_SQRT = 4, F_TRIG = 5 };
 
 typedef struct { double x, y, z; } v3;
@@ -313,11 +323,12 @@ int wo_substep(const wo_model *m, const wo_params *prm, wo_state *s, const doubl
                 qx[ncand][0] = xw.x; qx[ncand][1] = xw.y; qx[ncand][2] = depth;
                 qid[ncand][0] = g; qid[ncand][1] = -1; qdepth[ncand] = depth;
                 ++ncand;
-            }
+            } else CAP(1, 1);
         }
     }
     if (prm->self_collision)
-        for (int pr = 0; pr < m->npairs && ncand < WO_MAX_CANDIDATES; ++pr) {
+        for (int pr = 0; pr < m->npairs; ++pr) {
+            if (ncand >= WO_MAX_CANDIDATES) { CAP(2, m->npairs - pr); break; }
             const int ga = m->pair_a[pr], gb = m->pair_b[pr], ba = m->geom_body[ga], bb = m->geom_body[gb];
             v3 ca, cb;
             segment_closest(vadd(k.o[ba], mulMv(k.R[ba], ld3(t_geom_p0(m) + 3 * ga))), vadd(k.o[ba], mulMv(k.R[ba], ld3(t_geom_p1(m) + 3 * ga))),
@@ -354,6 +365,7 @@ int wo_substep(const wo_model *m, const wo_params *prm, wo_state *s, const doubl
         bias[3 * ncont + 2] = 0.0; kind[3 * ncont + 2] = fk == 1 ? 2 : 3; partner[3 * ncont + 2] = 3 * ncont;
         ++ncont;
     }
+    CAP_MAX(0, ncand); CAP_MAX(3, ncont);
     int nr = 3 * ncont;
     for (int c = 0; c < ncont; ++c)
         for (int d = 0; d < n; ++d) {
