@@ -687,6 +687,38 @@ int mg_maze2d_policy_rollout(const mg_maze_tasks *tasks, int32_t task_type, int3
                              int32_t *episodes, int32_t *actions, float *reward, double *reward64, uint8_t *done,
                              float *obs, void *stream);
 
+/* Softmax-sampled policies (csrc/mg_sample.h): the action of the policy above drawn from softmax(l / temperature) by a
+ * Gumbel-max draw that is defined bit for bit, so a recorded trajectory has a likelihood and the closed loop still replays
+ * exactly. A policy set carries temperature[p] (float32, finite, > 0); the HOST computes inv_t[p] = float32(1) /
+ * float32(temperature[p]) in float32 and refuses a set whose inv_t is not finite or not > 0; the kernel receives inv_t.
+ * The logits l[k] are exactly those of the greedy definition, in its order. For env e at carry step n (the counter of the
+ * exploration draw) and action k:
+ *   out = philox4x32_10(c0 = e, c1 = n & 0xFFFFFFFF, c2 = n >> 32, c3 = 0x53000000 | (k >> 2), k0 = seed & 0xFFFFFFFF,
+ *                       k1 = seed >> 32)
+ *   u = u01(out[k & 3]);  g = -log32(-log32(u));  score[k] = l[k] * inv_t + g     (one float32 multiply, then one float32
+ *                                                                                   add, each rounded once, never fused)
+ *   action = 0; best = score[0]; for k >= 1: if score[k] > best: action = k, best = score[k]
+ * with u01 and log32 those of the bandit learners below (u01(word) = (float)(((word >> 9) << 1) | 1) * 2^-24; log32 fdlibm's
+ * single-precision log, one operation at a time). u lies in [2^-24, 1 - 2^-24], so -log32(u) is a positive normal float in
+ * [5.96e-8, 16.64] and g is finite, in [-2.8116, 16.6356], monotone in u and within 5.32e-7 of the float64 Gumbel value
+ * (all 2^23 values of u checked on the host): log32's precondition holds for both applications. Ties and NaN scores resolve
+ * as the greedy argmax does. The 2-D maze has four actions and draws one block per step; the bandits draw ceil(K / 4). The
+ * tag 0x53000000 | q (q <= 15) differs from every other c3 in use: 0x4241 (bandits exploration), 0x4D5A (maze), 0x4D33
+ * (3-D maze), 0x4C000000 | ... (the Thompson sampler's gammas). With eps_threshold set, the exploration draw is made as
+ * above and overrides the sampled action.
+ *
+ * mg_maze2d_policy_rollout_sampled is mg_maze2d_policy_rollout with inv_temperature (DEVICE f32 [n_policies], read-only)
+ * after `carry`: the same step, records, results, carry and refusals, plus MG_ERR_NULL_POINTER for a NULL inv_temperature,
+ * all before anything is launched; hipGraph-capturable as it stands. mg_maze2d_policy_rollout itself is unchanged. Additive
+ * entry point; MG_ABI_VERSION is unchanged. */
+int mg_maze2d_policy_rollout_sampled(const mg_maze_tasks *tasks, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                                     int32_t auto_reset, int32_t n_envs, const mg_maze_state *state, int32_t n_steps,
+                                     int32_t obs_every, const mg_maze_policy *policy, const int32_t *policy_ids,
+                                     const mg_maze_policy_carry *carry, const float *inv_temperature, uint64_t seed,
+                                     uint64_t step0, int32_t episodic, float *obs_last, double *ret_total,
+                                     double *ret_episode, int32_t *episode_len, int32_t *episodes, int32_t *actions,
+                                     float *reward, double *reward64, uint8_t *done, float *obs, void *stream);
+
 /* MetaMaze shortest-path fields and the expert that descends them (csrc/maze_expert.hip). The reference has no such
  * function; the numbers are defined here and by metamaze/expert.py (distance_field_reference, expert_action_reference).
  *
@@ -1590,6 +1622,20 @@ int mg_bandits_policy_rollout(const mg_bandits_config *cfg, int32_t n_envs, cons
                               double *ret_total, double *ret_episode, int32_t *episode_len, int32_t *episodes,
                               double *regret, int32_t *actions, float *reward, uint8_t *done, int32_t *info_steps,
                               double *expected_gain, double *best_gain, uint8_t *invalid, void *stream);
+
+/* The softmax-sampled form: mg_bandits_policy_rollout with the action drawn from softmax(l / temperature) by the Gumbel-max
+ * draw defined at mg_maze2d_policy_rollout_sampled (score[k] = l[k] * inv_t + g[k], one Philox block with c3 = 0x53000000 |
+ * (k >> 2) per four arms, ceil(K / 4) blocks per step; the scores, like the logits, are never stored). inv_temperature
+ * (DEVICE f32 [n_policies], read-only) comes after `carry`. The same step, records, results, carry and refusals, plus
+ * MG_ERR_NULL_POINTER for a NULL inv_temperature, all before anything is launched; hipGraph-capturable as it stands.
+ * mg_bandits_policy_rollout itself is unchanged. Additive entry point; MG_ABI_VERSION is unchanged. */
+int mg_bandits_policy_rollout_sampled(const mg_bandits_config *cfg, int32_t n_envs, const mg_bandits_state *state,
+                                      int32_t n_steps, const mg_bandits_policy *policy, const int32_t *policy_ids,
+                                      const mg_bandits_policy_carry *carry, const float *inv_temperature, uint64_t seed,
+                                      uint64_t step0, int32_t episodic, double *ret_total, double *ret_episode,
+                                      int32_t *episode_len, int32_t *episodes, double *regret, int32_t *actions,
+                                      float *reward, uint8_t *done, int32_t *info_steps, double *expected_gain,
+                                      double *best_gain, uint8_t *invalid, void *stream);
 
 /* Closed-loop rollouts with a classical learner inside the launch (csrc/bandits_learner.hip): greedy on a Beta prior, UCB, an
  * index table (Gittins) and Thompson sampling, the baselines a learned bandit policy is reported against.

@@ -428,6 +428,10 @@ SIGNATURES = {
                                            C.POINTER(MazeState), C.c_int32, C.c_int32, C.POINTER(MazePolicyDesc), _P,
                                            C.POINTER(MazePolicyCarry), C.c_uint64, C.c_uint64, C.c_int32,
                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mg_maze2d_policy_rollout_sampled": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.POINTER(MazeState), C.c_int32, C.c_int32, C.POINTER(MazePolicyDesc), _P,
+                                                   C.POINTER(MazePolicyCarry), _P, C.c_uint64, C.c_uint64, C.c_int32,
+                                                   _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mg_maze_distance_field": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, _P, _P, _P]),
     "mg_maze_distance_queue_capacity": (C.c_int32, []),
     "mg_maze_expert_action": (C.c_int, [C.POINTER(MazeTasks), C.c_int32, _P, C.c_int32, C.POINTER(MazeState), _P, _P]),
@@ -502,6 +506,10 @@ SIGNATURES = {
     "mg_bandits_policy_rollout": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), C.c_int32,
                                             C.POINTER(BanditsPolicyDesc), _P, C.POINTER(BanditsPolicyCarry), C.c_uint64,
                                             C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mg_bandits_policy_rollout_sampled": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), C.c_int32,
+                                                    C.POINTER(BanditsPolicyDesc), _P, C.POINTER(BanditsPolicyCarry), _P,
+                                                    C.c_uint64, C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                    _P, _P, _P]),
     "mg_bandits_learner_rollout": (C.c_int, [C.POINTER(BanditsConfig), C.c_int32, C.POINTER(BanditsState), C.c_int32,
                                              C.POINTER(BanditsLearnerDesc), _P, C.POINTER(BanditsLearnerCarry), C.c_uint64,
                                              C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

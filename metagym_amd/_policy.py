@@ -1,5 +1,6 @@
 """What the Python front ends of the closed-loop rollouts share (quadrotor, MetaLocomotion, MetaMaze 2-D, bandits, LiftSim):
-the argument helpers, Philox and the exploration threshold, the upload-once cache of a packed policy set, the carry of the
+the argument helpers, Philox and the exploration threshold, the exact float32 `log32` / `u01` and the Gumbel-max draw of the
+softmax-sampled policies built on them, the upload-once cache of a packed policy set, the carry of the
 continuous-action recurrent policies, the validator and cache of `policy_ids`, and the carry checks of `rollout_policy`.
 LiftSim's recurrent form (`LiftRecurrentPolicy`, `liftsim/policy.py`) takes the argument helpers, `PackedPolicySet` and
 `policy_ids`; its carry (`LiftPolicyState`: a memory per elevator, stored env index fastest) and that carry's checks stay
@@ -51,6 +52,101 @@ def philox4x32_10(c0, c1, c2, c3, k0, k1):
     return tuple(v.astype(np.uint32) for v in (c0, c1, c2, c3))
 
 
+F = np.float32
+SAMPLE_TAG = 0x53000000      # c3 of a sampling block: tag | (action >> 2)
+
+# the constants of log32, by their float32 bits
+LG1, LG2, LG3, LG4 = (np.array([b], np.uint32).view(F)[0] for b in (0x3f2aaaaa, 0x3eccce13, 0x3e91e9ee, 0x3e789e26))
+LN2_HI, LN2_LO = (np.array([b], np.uint32).view(F)[0] for b in (0x3f317180, 0x3717f7d1))
+
+
+def log32(x):
+    """fdlibm's single-precision log, one operation at a time (written out in bandits/learner.py), on a float32 array of
+    positive normal numbers (any shape), in numpy float32."""
+    x = np.asarray(x)
+    if x.dtype != F:
+        raise TypeError("log32 takes float32, got %s" % x.dtype)
+    shape = x.shape
+    i = np.ascontiguousarray(x).reshape(-1).view(np.uint32) + np.uint32(0x3f800000 - 0x3f3504f3)
+    k = (i >> np.uint32(23)).astype(np.int32) - np.int32(127)
+    m = ((i & np.uint32(0x007fffff)) + np.uint32(0x3f3504f3)).view(F)
+    one, two, half = F(1.0), F(2.0), F(0.5)
+    with np.errstate(all="ignore"):
+        f = m - one
+        s = f / (two + f)
+        z = s * s
+        w = z * z
+        t1 = w * (LG2 + w * LG4)
+        t2 = z * (LG1 + w * LG3)
+        R = t2 + t1
+        hfsq = (half * f) * f
+        dk = k.astype(F)
+        out = (((s * (hfsq + R) + dk * LN2_LO) - hfsq) + f) + dk * LN2_HI
+    assert out.dtype == F
+    return out.reshape(shape)
+
+
+def u01(word):
+    """(float)(((word >> 9) << 1) | 1) * 2^-24 on uint32 words: an odd 24-bit integer, so exact, never 0 and never 1."""
+    w = np.asarray(word, np.uint32)
+    return (((w >> np.uint32(9)) << np.uint32(1)) | np.uint32(1)).astype(F) * F(2.0 ** -24)
+
+
+def gumbel32(words):
+    """g = -log32(-log32(u01(word))) on uint32 words, float32: the standard Gumbel value of the sampled policies. -log32(u)
+    is a positive normal float for every u that u01 returns, so both applications meet log32's precondition; g is finite."""
+    return -log32(-log32(u01(words)))
+
+
+def check_temperature(temperature, P):
+    """The temperatures of P policies as a contiguous float32 [P] array, finite and > 0, whose float32 inverse
+    float32(1) / temperature is finite and > 0 too."""
+    t = to_numpy(temperature)
+    if t.dtype != F:
+        raise TypeError("temperature must be float32, got %s" % t.dtype)
+    if t.shape != (P,):
+        raise ValueError("temperature must have shape (%d,), got %s" % (P, t.shape))
+    if not (np.isfinite(t) & (t > 0)).all():
+        raise ValueError("temperature must be finite and > 0")
+    inv = inverse_temperature(t)
+    if not (np.isfinite(inv) & (inv > 0)).all():
+        raise ValueError("1 / temperature must be a finite float32 > 0")
+    return np.ascontiguousarray(t)
+
+
+def inverse_temperature(temperature):
+    """inv_t = float32(1) / float32(temperature), elementwise in numpy float32: what the kernel receives."""
+    with np.errstate(all="ignore"):
+        return (F(1.0) / np.asarray(temperature, F)).astype(F)
+
+
+def sample_actions(logits, inv_t, env_ids, step, seed):
+    """The Gumbel-max draw of include/metagym_hip.h on float32 logits [N, K]: score[k] = logits[k] * inv_t + g[k] (one float32
+    multiply, then one float32 add), g[k] from word k & 3 of the Philox block with c3 = SAMPLE_TAG | (k >> 2) of env
+    env_ids[e] at carry step `step`; the lowest index among the maxima. inv_t float32 [N]. Returns int32 [N]."""
+    logits, inv_t = np.asarray(logits), np.asarray(inv_t)
+    assert logits.dtype == F and inv_t.dtype == F
+    N, K = logits.shape
+    e = np.asarray(env_ids).astype(np.uint64)
+    n, s = int(step), int(seed)
+    action = np.zeros(N, np.int32)
+    best = None
+    with np.errstate(all="ignore"):
+        for k in range(K):
+            if k % 4 == 0:
+                out = philox4x32_10(e, n & 0xFFFFFFFF, (n >> 32) & 0xFFFFFFFF, SAMPLE_TAG | (k >> 2), s & 0xFFFFFFFF,
+                                    (s >> 32) & 0xFFFFFFFF)
+            score = logits[:, k] * inv_t + gumbel32(out[k & 3])
+            assert score.dtype == F
+            if k == 0:
+                best = score
+            else:
+                better = score > best
+                action = np.where(better, np.int32(k), action)
+                best = np.where(better, score, best)
+    return action
+
+
 def check_epsilon(epsilon, P):
     """The exploration rates of P policies as a contiguous float64 [P] array in [0, 1]."""
     eps = to_numpy(epsilon)
@@ -84,6 +180,25 @@ class PackedPolicySet(object):
     def _host(self):
         """What `to` uploads: one numpy array, or a tuple of arrays and Nones. Here the packed parameters alone."""
         return self.pack()
+
+    temperature = None       # float32 [P] on a set that samples its actions (the discrete-action policies), else None
+
+    @property
+    def inv_temperature(self):
+        """float32 [P]: float32(1) / temperature[p], what the sampled kernels multiply the logits with; None without."""
+        return None if self.temperature is None else inverse_temperature(self.temperature)
+
+    def inv_temperature_on(self, device):
+        """`inv_temperature` as a torch tensor on `device`, uploaded once per device and kept apart from what `to` returns."""
+        import torch
+        from . import _lib
+        if self.temperature is None:
+            return None
+        cache = self.__dict__.setdefault("_inv_t_device", {})
+        key = str(_lib.canonical_device(device))
+        if key not in cache:
+            cache[key] = torch.from_numpy(self.inv_temperature).to(_lib.canonical_device(device)).contiguous()
+        return cache[key]
 
     def to(self, device):
         """The arrays of `_host` as contiguous torch tensors on `device` (uploaded once per device), None staying None."""

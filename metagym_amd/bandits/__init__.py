@@ -2,6 +2,7 @@
 from .bandits_env import DISTRIBUTIONS, Bandits, classical_lo_hi
 from .learner import BanditLearner, BanditLearnerState, BanditsLearnerRollout, gittins_index_table, log32
 from .policy import BanditPolicy, BanditPolicyState, BanditsPolicyRollout
+from .policy_net import BanditPolicyNet, log_prob
 
 __all__ = ["Bandits", "DISTRIBUTIONS", "classical_lo_hi", "BanditPolicy", "BanditPolicyState", "BanditsPolicyRollout",
-           "BanditLearner", "BanditLearnerState", "BanditsLearnerRollout", "gittins_index_table", "log32"]
+           "BanditLearner", "BanditLearnerState", "BanditsLearnerRollout", "gittins_index_table", "log32", "BanditPolicyNet", "log_prob"]

@@ -254,7 +254,8 @@ class Bandits(object):
         `policy_ids=None` = e % P) on its previous action, reward and done inside the kernel and pulls the arm it chooses
         (bandits/policy.py defines the arithmetic exactly). `state` is the carry of the previous call (a `BanditPolicyState`;
         None = a fresh one); it is not written, the end carry comes back as `.state` of the result with `step` advanced by
-        `steps`. `seed` keys the exploration draws of a policy with epsilon. The step is `rollout`'s, draw for draw, with
+        `steps`. `seed` keys the exploration draws of a policy with epsilon and the sampling draws of a policy with a
+        temperature (which goes through mg_bandits_policy_rollout_sampled; everything else here is the same). The step is `rollout`'s, draw for draw, with
         `auto_reset` and `resample_task` as the env was built. The policy's memory survives a done (the next step sees
         prev_done = 1 and the ending step's reward and action); `episodic=True` clears the carry at a done with auto_reset
         instead. An env that is over when a step begins (never reset, or finished without auto_reset) does nothing in that
@@ -276,6 +277,7 @@ class Bandits(object):
         state, seed = _policy.check_discrete_carry(state, BanditPolicyState, N, H, T, seed, dev)
         ids_d = _policy.policy_ids(self, policy_ids, P)
         params, thr = policy.to(dev)
+        inv_t = policy.inv_temperature_on(dev)
         # everything is checked: from here on the env and the new carry are written
         carry = BanditPolicyState(*[v.to(dev).clone().contiguous() for v in (state.h, state.prev_action, state.prev_reward,
                                                                              state.prev_done)], step=state.step + T)
@@ -284,13 +286,16 @@ class Bandits(object):
                                           carry.prev_done.data_ptr())
         res = self._rollout_results(T, record, carry)
         cfg = self._cfg(*(self.resample_task or (None,)))
-        rc = self._lib.mg_bandits_policy_rollout(cfg, N, self._state, T, desc, _lib.ptr(ids_d), carry_c, seed, state.step,
-                                                 int(bool(episodic)), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
-                                                 _lib.ptr(res.episode_len), _lib.ptr(res.episodes), _lib.ptr(res.regret),
-                                                 _lib.ptr(res.actions), _lib.ptr(res.reward), _lib.ptr(res.done),
-                                                 _lib.ptr(res.info_steps), _lib.ptr(res.expected_gain), _lib.ptr(res.best_gain),
-                                                 _lib.ptr(res.invalid), self._stream())
-        _lib.check(rc, "mg_bandits_policy_rollout")
+        head = (cfg, N, self._state, T, desc, _lib.ptr(ids_d), carry_c)
+        tail = (seed, state.step, int(bool(episodic)), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
+                _lib.ptr(res.episode_len), _lib.ptr(res.episodes), _lib.ptr(res.regret), _lib.ptr(res.actions),
+                _lib.ptr(res.reward), _lib.ptr(res.done), _lib.ptr(res.info_steps), _lib.ptr(res.expected_gain),
+                _lib.ptr(res.best_gain), _lib.ptr(res.invalid), self._stream())
+        if inv_t is None:
+            _lib.check(self._lib.mg_bandits_policy_rollout(*(head + tail)), "mg_bandits_policy_rollout")
+        else:
+            _lib.check(self._lib.mg_bandits_policy_rollout_sampled(*(head + (_lib.ptr(inv_t),) + tail)),
+                       "mg_bandits_policy_rollout_sampled")
         return res
 
     def _rollout_results(self, T, record, carry):

@@ -45,7 +45,8 @@ Nothing here needs a GPU to import.
 """
 import numpy as np
 
-from .._policy import PackedPolicySet, check_epsilon, f32_array, philox4x32_10, to_numpy
+from .._policy import (LG1, LG2, LG3, LG4, LN2_HI, LN2_LO, PackedPolicySet, check_epsilon, f32_array, log32,  # noqa: F401
+                       philox4x32_10, to_numpy, u01)
 from .policy import MAX_ARMS, PHILOX_TAG, BanditsPolicyRollout
 
 F = np.float32
@@ -54,47 +55,12 @@ MAX_CAP = 1023
 MAX_ATTEMPTS = 64
 GAMMA_TAG = 0x4C000000       # c3 of a sampler draw: tag | arm << 17 | which << 16 | attempt
 
-# the constants of log32, by their float32 bits
-LG1, LG2, LG3, LG4 = (np.array([b], np.uint32).view(F)[0] for b in (0x3f2aaaaa, 0x3eccce13, 0x3e91e9ee, 0x3e789e26))
-LN2_HI, LN2_LO = (np.array([b], np.uint32).view(F)[0] for b in (0x3f317180, 0x3717f7d1))
-
 BanditsLearnerRollout = BanditsPolicyRollout   # the same fields; .state is a BanditLearnerState
 
 
 def table_cells(cap):
     """Cells of one table row: (C + 1)(C + 2) / 2."""
     return (int(cap) + 1) * (int(cap) + 2) // 2
-
-
-def log32(x):
-    """The log32 of the module docstring on a float32 array of positive normal numbers (any shape), in numpy float32."""
-    x = np.asarray(x)
-    if x.dtype != F:
-        raise TypeError("log32 takes float32, got %s" % x.dtype)
-    shape = x.shape
-    i = np.ascontiguousarray(x).reshape(-1).view(np.uint32) + np.uint32(0x3f800000 - 0x3f3504f3)
-    k = (i >> np.uint32(23)).astype(np.int32) - np.int32(127)
-    m = ((i & np.uint32(0x007fffff)) + np.uint32(0x3f3504f3)).view(F)
-    one, two, half = F(1.0), F(2.0), F(0.5)
-    with np.errstate(all="ignore"):
-        f = m - one
-        s = f / (two + f)
-        z = s * s
-        w = z * z
-        t1 = w * (LG2 + w * LG4)
-        t2 = z * (LG1 + w * LG3)
-        R = t2 + t1
-        hfsq = (half * f) * f
-        dk = k.astype(F)
-        out = (((s * (hfsq + R) + dk * LN2_LO) - hfsq) + f) + dk * LN2_HI
-    assert out.dtype == F
-    return out.reshape(shape)
-
-
-def u01(word):
-    """(float)(((word >> 9) << 1) | 1) * 2^-24 on uint32 words: an odd 24-bit integer, so exact, never 0 and never 1."""
-    w = np.asarray(word, np.uint32)
-    return (((w >> np.uint32(9)) << np.uint32(1)) | np.uint32(1)).astype(F) * F(2.0 ** -24)
 
 
 def gamma32(a, e, n, arm, which, seed, max_attempts=MAX_ATTEMPTS):

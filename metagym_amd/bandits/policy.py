@@ -22,6 +22,20 @@ index. Exploration is integer arithmetic only: thr[p] = min(floor(epsilon[p] * 2
 out = philox4x32_10(c0 = e, c1 = n & 0xFFFFFFFF, c2 = n >> 32, c3 = 0x4241, k0 = seed & 0xFFFFFFFF, k1 = seed >> 32) and
 action = (out[0] < thr) ? (out[1] % K) : greedy, with an unsigned modulo.
 
+A set with `temperature` (float32 [P], finite and > 0) SAMPLES its action from softmax(l / temperature) instead of taking the
+argmax, by a Gumbel-max draw that is defined bit for bit (so a recorded trajectory has a likelihood, and still replays). The
+host computes inv_t[p] = float32(1) / float32(temperature[p]) in numpy float32 (a set whose inv_t is not finite or not > 0 is
+refused); the kernel receives inv_t. The logits are exactly the ones above, in that order. For env e at carry step n and arm k:
+
+    out = philox4x32_10(c0 = e, c1 = n & 0xFFFFFFFF, c2 = n >> 32, c3 = 0x53000000 | (k >> 2), k0, k1 as above)
+    u = u01(out[k & 3]);  g = -log32(-log32(u));  score[k] = l[k] * inv_t + g      (one multiply, then one add)
+    action = 0; best = score[0]; for k >= 1: if score[k] > best: action = k, best = score[k]
+
+with `u01` and `log32` the bandit learners' (learner.py writes them out; _policy.py holds them). One Philox block serves four
+arms, so K arms draw ceil(K / 4) blocks. g is finite, in [-2.8116, 16.6356], and within 5.32e-7 of the float64 Gumbel value.
+With `epsilon` as well, the exploration draw is made as above and overrides the sampled action. Without `temperature` nothing
+changes. `BanditPolicyNet` (policy_net.py) is the same network as a torch module, for the gradient of a recorded rollout.
+
 `BanditPolicy.reference` evaluates exactly this in numpy float32 and numpy integers. Nothing here needs a GPU to import. The
 carry is the maze policies' (metamaze/policy.py); the Philox function and the threshold rule are shared (_policy.py).
 
@@ -31,7 +45,7 @@ carry is the maze policies' (metamaze/policy.py); the Philox function and the th
 """
 import numpy as np
 
-from .._policy import PackedPolicySet, check_epsilon, f32_array, pad4, philox4x32_10, to_numpy
+from .._policy import PackedPolicySet, check_epsilon, check_temperature, f32_array, pad4, philox4x32_10, sample_actions, to_numpy
 from ..metamaze.policy import MazePolicyState
 
 MAX_HIDDEN = 64
@@ -53,9 +67,10 @@ def param_count(hidden, arms):
 
 class BanditPolicy(PackedPolicySet):
     """P recurrent policies: wa [P, H, K], wr [P, H], wd [P, H], wh [P, H, H], b [P, H], wo [P, K, H], bo [P, K], all float32
-    and finite; epsilon float64 [P] in [0, 1] or None (no exploration). 1 <= H <= 64, 2 <= K <= 64."""
+    and finite; epsilon float64 [P] in [0, 1] or None (no exploration); temperature float32 [P], finite and > 0, or None (the
+    greedy action, not a sampled one). 1 <= H <= 64, 2 <= K <= 64."""
 
-    def __init__(self, wa, wr, wd, wh, b, wo, bo, epsilon=None):
+    def __init__(self, wa, wr, wd, wh, b, wo, bo, epsilon=None, temperature=None):
         wa, wr, wd, wh = f32_array("wa", wa, 3), f32_array("wr", wr, 2), f32_array("wd", wd, 2), f32_array("wh", wh, 3)
         b, wo, bo = f32_array("b", b, 2), f32_array("wo", wo, 3), f32_array("bo", bo, 2)
         P, H, K = wa.shape
@@ -71,6 +86,7 @@ class BanditPolicy(PackedPolicySet):
                              "got %s %s %s %s %s %s %s" % (wa.shape, wr.shape, wd.shape, wh.shape, b.shape, wo.shape, bo.shape))
         self.wa, self.wr, self.wd, self.wh, self.b, self.wo, self.bo = wa, wr, wd, wh, b, wo, bo
         self.epsilon = None if epsilon is None else check_epsilon(epsilon, P)
+        self.temperature = None if temperature is None else check_temperature(temperature, P)
         self.num_policies, self.hidden, self.arms = P, H, K
 
     @property
@@ -97,7 +113,7 @@ class BanditPolicy(PackedPolicySet):
         return out
 
     @classmethod
-    def unpack(cls, packed, hidden, arms, epsilon=None):
+    def unpack(cls, packed, hidden, arms, epsilon=None, temperature=None):
         """The inverse of `pack`."""
         packed = f32_array("packed", packed, 2)
         P, H, K = packed.shape[0], int(hidden), int(arms)
@@ -108,20 +124,22 @@ class BanditPolicy(PackedPolicySet):
         unit = packed[:, :H * ru].reshape(P, H, ru)
         arm = packed[:, H * ru:].reshape(P, K, ra)
         return cls(unit[:, :, 4:4 + K].copy(), unit[:, :, 1].copy(), unit[:, :, 2].copy(), unit[:, :, 4 + kp:4 + kp + H].copy(),
-                   unit[:, :, 0].copy(), arm[:, :, 4:4 + H].copy(), arm[:, :, 0].copy(), epsilon)
+                   unit[:, :, 0].copy(), arm[:, :, 4:4 + H].copy(), arm[:, :, 0].copy(), epsilon, temperature)
 
     def _host(self):
         """`to(device)` gives (packed parameters, thresholds or None); the thresholds travel as the int32 tensor with the
         uint32's bits."""
         return self.pack(), self._threshold_bits()
 
-    def reference(self, policy_ids, state, seed=0, env_ids=None, return_explored=False):
+    def reference(self, policy_ids, state, seed=0, env_ids=None, return_explored=False, return_logits=False):
         """One step of the definition above in numpy float32 (and numpy integers for the exploration), with exactly that
         association: the sums run over i and j one term at a time, each term an array over the envs (and the units or arms,
         which are independent of each other). policy_ids [N]; state: a `BanditPolicyState` (its h, prev_action, prev_reward,
         prev_done and step are read; nothing is written); env e draws with counter c0 = env_ids[e] (default e). Returns
         (actions int32 [N], next h float32 [N, H]), and with `return_explored` also the bool [N] mask of the envs whose
-        action was the exploratory draw. The oracle of the policy half of a closed-loop rollout."""
+        action was the exploratory draw, and with `return_logits` last the float32 [N, K] logits. A set with a temperature
+        draws the action from its scores (the module docstring) where a set without takes the greedy one. The oracle of the
+        policy half of a closed-loop rollout."""
         P, H, K = self.num_policies, self.hidden, self.arms
         ids = to_numpy(policy_ids)
         if ids.ndim != 1 or ids.dtype.kind not in "iu":
@@ -163,10 +181,12 @@ class BanditPolicy(PackedPolicySet):
         thr = self.thresholds[ids]
         e = np.arange(N, dtype=np.uint64) if env_ids is None else to_numpy(env_ids).astype(np.uint64)
         n, s = int(state.step), int(seed)
+        if self.temperature is not None:
+            greedy = sample_actions(logits, self.inv_temperature[ids], e, n, s)
         out = philox4x32_10(e, n & 0xFFFFFFFF, (n >> 32) & 0xFFFFFFFF, PHILOX_TAG, s & 0xFFFFFFFF, (s >> 32) & 0xFFFFFFFF)
         explored = out[0] < thr
         actions = np.where(explored, (out[1] % np.uint32(K)).astype(np.int32), greedy).astype(np.int32)
-        return (actions, hn, explored) if return_explored else (actions, hn)
+        return (actions, hn) + ((explored,) if return_explored else ()) + ((logits,) if return_logits else ())
 
 
 class BanditsPolicyRollout(object):

@@ -12,9 +12,14 @@
 // over (arm, draw, attempt) has a length of its own in every lane and holds no collective. The refill inside Streams::next is a
 // workgroup-collective (__syncthreads): the env half of a step is reached by all 64 lanes at every step, with act = false
 // for the lanes that draw nothing. Table rows are read per lane from global memory; lanes sharing a row hit in cache.
+//
+// log32 and u01 live in mg_sample.h (mg::log32, mg::u01), shared with the softmax-sampled policies; their operation sequence
+// is the one this unit was written with. log32's constants by their bits, as the header defines them: Lg1 0x3f2aaaaau,
+// Lg2 0x3eccce13u, Lg3 0x3e91e9eeu, Lg4 0x3e789e26u, ln2_hi 0x3f317180u, ln2_lo 0x3717f7d1u, sqrt(1/2) 0x3f3504f3u.
 #include "bandits_core.h"
 
 #include "mg_philox.h"
+#include "mg_sample.h"
 
 namespace {
 
@@ -50,27 +55,6 @@ __host__ __device__ constexpr int bl_counts_bytes(int arms) { return 2 * arms * 
 __host__ __device__ constexpr int bl_lds_bytes(int arms) { return bl_counts_bytes(arms) + MTN * (int)sizeof(uint32_t); }
 __host__ __device__ constexpr int64_t bl_cells(int cap) { return ((int64_t)cap + 1) * ((int64_t)cap + 2) / 2; }
 
-// fdlibm's single-precision log for a positive normal x, one operation at a time (the definition of the header)
-__device__ __forceinline__ float bl_log32(float x) {
-    uint32_t i = __float_as_uint(x);
-    i += 0x3f800000u - 0x3f3504f3u;
-    const int k = (int)(i >> 23) - 127;
-    const float m = __uint_as_float((i & 0x007fffffu) + 0x3f3504f3u);
-    const float f = m - 1.0f;
-    const float s = f / (2.0f + f);
-    const float z = s * s;
-    const float w = z * z;
-    const float t1 = w * (__uint_as_float(0x3eccce13u) + w * __uint_as_float(0x3e789e26u));   // Lg2, Lg4
-    const float t2 = z * (__uint_as_float(0x3f2aaaaau) + w * __uint_as_float(0x3e91e9eeu));   // Lg1, Lg3
-    const float R = t2 + t1;
-    const float hfsq = (0.5f * f) * f;
-    const float dk = (float)k;
-    return (((s * (hfsq + R) + dk * __uint_as_float(0x3717f7d1u)) - hfsq) + f) + dk * __uint_as_float(0x3f317180u);
-}
-
-// an odd 24-bit integer times 2^-24: exact, never 0, never 1
-__device__ __forceinline__ float bl_u01(uint32_t word) { return (float)(((word >> 9) << 1) | 1u) * 5.9604644775390625e-08f; }
-
 // Thompson sampling for one env: K scores X / (X + Y) from 2 K gammas (Marsaglia-Tsang with a polar normal, a >= 1), and
 // the lowest index among their maxima. ONE loop runs over the lane's own sequence of (arm, which, attempt): a lane that
 // rejects tries again while its neighbours go on to their next draw, so a wave runs for its longest lane's total number of
@@ -94,17 +78,17 @@ __device__ __forceinline__ int bl_thompson(const int32_t *cnt, int K, float a0, 
         philox4x32_10(e, (uint32_t)n, (uint32_t)(n >> 32), BL_GAMMA_TAG | ((uint32_t)k << 17) | (which << 16) | (uint32_t)i,
                       (uint32_t)seed, (uint32_t)(seed >> 32), o);
         ++i;
-        const float v1 = 2.0f * bl_u01(o[0]) - 1.0f;
-        const float v2 = 2.0f * bl_u01(o[1]) - 1.0f;
+        const float v1 = 2.0f * mg::u01(o[0]) - 1.0f;
+        const float v2 = 2.0f * mg::u01(o[1]) - 1.0f;
         const float s = v1 * v1 + v2 * v2;
         bool accepted = false;
         float value = d;                                                   // the fallback
         if (s < 1.0f) {
-            const float x = v1 * sqrtf((-2.0f * bl_log32(s)) / s);
+            const float x = v1 * sqrtf((-2.0f * mg::log32(s)) / s);
             const float v = 1.0f + c * x;
             if (v > 0.0f) {
                 const float v3 = (v * v) * v;
-                accepted = bl_log32(bl_u01(o[2])) < (((0.5f * x) * x + d) - d * v3) + d * bl_log32(v3);
+                accepted = mg::log32(mg::u01(o[2])) < (((0.5f * x) * x + d) - d * v3) + d * mg::log32(v3);
                 if (accepted) value = d * v3;
             }
         }
@@ -147,7 +131,7 @@ __device__ __forceinline__ int bl_choose(const int32_t *cnt, int K, float a0, fl
                 for (int k = 0; k < K; ++k) scores[k] = cnt[2 * k * BL_BLOCK] == 0 ? __uint_as_float(0x7f800000u) : 0.0f;
             return first;
         }
-        lt = c * bl_log32((float)t);
+        lt = c * mg::log32((float)t);
     }
     int g = 0;
     float best = 0.0f;

@@ -14,6 +14,7 @@
 #include "maze_core.h"
 
 #include "mg_closed_loop.h"
+#include "mg_sample.h"
 
 namespace {
 
@@ -55,9 +56,11 @@ struct MpPolicy {
 // or from global memory (each lane its own block). h and hn are the lane's columns of the two LDS state buffers. The j loop
 // runs at run time; the x loop is unrolled, the h loop reads four recurrent weights per 16-byte read and skips the padding
 // (0 * h added to a pre-activation of -0 would turn it into +0). hn[j] goes into the four logits as soon as it is known: for
-// every k that is the sum over j in ascending order, as defined. Returns the greedy action.
-template <int D>
-__device__ __forceinline__ int policy_eval(const float *__restrict__ p, int hidden, const float *x, const float *h, float *hn) {
+// every k that is the sum over j in ascending order, as defined. Returns the greedy action; SAMPLED: the Gumbel-max draw, the
+// same argmax over score[k] = l[k] * inv_t + g[k] (mg_sample.h), the four words of one Philox block.
+template <int D, bool SAMPLED>
+__device__ __forceinline__ int policy_eval(const float *__restrict__ p, int hidden, const float *x, const float *h, float *hn,
+                                           float inv_t, uint32_t env, uint64_t step, uint64_t seed) {
     static_assert((D + 1) % 4 == 0, "the x part of a record is read in 16-byte pieces");
     const int hp = mp_hidden_pad(hidden), rec = mp_record(hidden, D);
     const mp_v4f bo = *reinterpret_cast<const mp_v4f *>(p);
@@ -88,6 +91,14 @@ __device__ __forceinline__ int policy_eval(const float *__restrict__ p, int hidd
         const mp_v4f wo = *reinterpret_cast<const mp_v4f *>(rh + hp);
         l0 = l0 + wo.x * a; l1 = l1 + wo.y * a; l2 = l2 + wo.z * a; l3 = l3 + wo.w * a;
     }
+    if (SAMPLED) {
+        uint32_t o[4];
+        mg::sample_block(env, step, 0u, seed, o);
+        l0 = mg::sample_score(l0, inv_t, o[0]);
+        l1 = mg::sample_score(l1, inv_t, o[1]);
+        l2 = mg::sample_score(l2, inv_t, o[2]);
+        l3 = mg::sample_score(l3, inv_t, o[3]);
+    }
     int g = 0;                                                           // ties and NaN logits: the lowest index
     float best = l0;
     if (l1 > best) { g = 1; best = l1; }
@@ -99,13 +110,14 @@ __device__ __forceinline__ int policy_eval(const float *__restrict__ p, int hidd
 // maze2d_rollout_kernel's step (move_2d, step_tail) with the action load replaced by the policy. x is computed from the state
 // the lane holds (observe_2d into registers) before the loop and after every step: the observation buffer is never read.
 // Inside the step loop the kernel stores only what `rec` asks for; the agent, the carry, the four per-env results and the
-// last window go out once, at the end.
-template <int VG>
+// last window go out once, at the end. SAMPLED: the action is drawn from softmax(l / temperature) (inv_t [n_policies], read
+// once per env); an exploratory draw still overrides it. The greedy instantiations read no inv_t (they are passed NULL).
+template <int VG, bool SAMPLED>
 __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze_tasks T, mg_maze_state st, int task_type,
                                                                          int max_steps, int auto_reset, int n_envs, int n_steps,
                                                                          int obs_every, MpPolicy pa, mg_maze_policy_carry ca,
                                                                          uint64_t seed, uint64_t step0, int episodic, RolloutOut po,
-                                                                         RolloutRec rec) {
+                                                                         RolloutRec rec, const float *__restrict__ inv_temperature) {
     constexpr int W = 2 * VG + 1, WW = W * W, D = WW + 6;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int H = pa.hidden;
@@ -127,6 +139,7 @@ __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze
     const bool staged = sp.staged;
     const float *__restrict__ own = sp.own;
     const uint32_t thr = pa.thr != nullptr ? pa.thr[sp.pid] : 0u;
+    const float inv_t = SAMPLED ? inv_temperature[sp.pid] : 0.0f;
 
     const Task t = load_task(T, st.task_id[el]);
     Agent a = load_agent(st, n_envs, el);
@@ -148,7 +161,8 @@ __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze
         for (int k = 0; k < 4; ++k) x[WW + k] = prev_action == k ? 1.0f : 0.0f;
         x[WW + 4] = prev_reward;
         x[WW + 5] = prev_done ? 1.0f : 0.0f;
-        int act = staged ? policy_eval<D>(policy_lds, H, x, hc, hx) : policy_eval<D>(own, H, x, hc, hx);
+        int act = staged ? policy_eval<D, SAMPLED>(policy_lds, H, x, hc, hx, inv_t, (uint32_t)el, step0 + (uint64_t)s, seed)
+                         : policy_eval<D, SAMPLED>(own, H, x, hc, hx, inv_t, (uint32_t)el, step0 + (uint64_t)s, seed);
         { float *sw = hc; hc = hx; hx = sw; }                              // h = hn
         uint32_t word;
         if (mg::explore_draw((uint32_t)el, step0 + (uint64_t)s, MP_PHILOX_TAG, seed, thr, word)) act = (int)(word & 3u);
@@ -198,12 +212,12 @@ __global__ __launch_bounds__(MP_BLOCK) void maze2d_policy_rollout_kernel(mg_maze
     ret.store(po, e);
 }
 
-typedef decltype(&maze2d_policy_rollout_kernel<1>) MpKernel;
+typedef decltype(&maze2d_policy_rollout_kernel<1, false>) MpKernel;
+template <bool SAMPLED>
 MpKernel pick_policy_kernel(int vg) {
-    return vg == 1 ? maze2d_policy_rollout_kernel<1> : (vg == 2 ? maze2d_policy_rollout_kernel<2> : maze2d_policy_rollout_kernel<3>);
+    return vg == 1 ? maze2d_policy_rollout_kernel<1, SAMPLED>
+                   : (vg == 2 ? maze2d_policy_rollout_kernel<2, SAMPLED> : maze2d_policy_rollout_kernel<3, SAMPLED>);
 }
-
-}  // namespace
 
 extern "C" int32_t mg_maze2d_policy_param_count(int32_t hidden, int32_t view_grid) {
     if (hidden < 1 || hidden > MP_MAX_HIDDEN) return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d is outside [1, %d]", hidden, MP_MAX_HIDDEN);
@@ -211,18 +225,20 @@ extern "C" int32_t mg_maze2d_policy_param_count(int32_t hidden, int32_t view_gri
     return mp_count(hidden, mp_input_dim(view_grid));
 }
 
-extern "C" int mg_maze2d_policy_rollout(const mg_maze_tasks *T, int32_t task_type, int32_t max_steps, int32_t view_grid,
-                                        int32_t auto_reset, int32_t n, const mg_maze_state *st, int32_t n_steps,
-                                        int32_t obs_every, const mg_maze_policy *policy, const int32_t *policy_ids,
-                                        const mg_maze_policy_carry *carry, uint64_t seed, uint64_t step0, int32_t episodic,
-                                        float *obs_last, double *ret_total, double *ret_episode, int32_t *episode_len,
-                                        int32_t *episodes, int32_t *actions, float *reward, double *reward64, uint8_t *done,
-                                        float *obs, void *stream) {
+// The two entry points: every check, then the launch of a greedy or a sampled instantiation. `name` is the entry point's.
+template <bool SAMPLED>
+int maze2d_policy_rollout(const char *name, const mg_maze_tasks *T, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                          int32_t auto_reset, int32_t n, const mg_maze_state *st, int32_t n_steps, int32_t obs_every,
+                          const mg_maze_policy *policy, const int32_t *policy_ids, const mg_maze_policy_carry *carry,
+                          const float *inv_temperature, uint64_t seed, uint64_t step0, int32_t episodic, float *obs_last,
+                          double *ret_total, double *ret_episode, int32_t *episode_len, int32_t *episodes, int32_t *actions,
+                          float *reward, double *reward64, uint8_t *done, float *obs, void *stream) {
     MG_REQUIRE_PTR(T);
     MG_REQUIRE_PTR(st);
     MG_REQUIRE_PTR(policy);
     MG_REQUIRE_PTR(policy_ids);
     MG_REQUIRE_PTR(carry);
+    if (SAMPLED) MG_REQUIRE_PTR(inv_temperature);
     MG_REQUIRE_PTR(obs_last);
     MG_REQUIRE_PTR(ret_total);
     MG_REQUIRE_PTR(ret_episode);
@@ -232,10 +248,10 @@ extern "C" int mg_maze2d_policy_rollout(const mg_maze_tasks *T, int32_t task_typ
     if (!carry->h || !carry->prev_action || !carry->prev_reward || !carry->prev_done)
         return mg::set_error(MG_ERR_NULL_POINTER, "mg_maze_policy_carry has a NULL array");
     if (n <= 0) return mg::set_error(MG_ERR_BAD_SIZE, "n_envs=%d", n);
-    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze2d_policy_rollout: n_steps=%d (at least 1)", n_steps);
-    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "mg_maze2d_policy_rollout: obs_every=%d (0 = the last step only, k >= 1 = every k-th)", obs_every);
+    if (n_steps < 1) return mg::set_error(MG_ERR_BAD_SIZE, "%s: n_steps=%d (at least 1)", name, n_steps);
+    if (obs_every < 0) return mg::set_error(MG_ERR_BAD_SIZE, "%s: obs_every=%d (0 = the last step only, k >= 1 = every k-th)", name, obs_every);
     if (view_grid < 1 || view_grid > 3)
-        return mg::set_error(MG_ERR_BAD_CONFIG, "mg_maze2d_policy_rollout: view_grid=%d is outside [1, 3]", view_grid);
+        return mg::set_error(MG_ERR_BAD_CONFIG, "%s: view_grid=%d is outside [1, 3]", name, view_grid);
     if (policy->n_policies < 1) return mg::set_error(MG_ERR_BAD_SIZE, "n_policies=%d", policy->n_policies);
     if (policy->hidden < 1 || policy->hidden > MP_MAX_HIDDEN)
         return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d is outside [1, %d]", policy->hidden, MP_MAX_HIDDEN);
@@ -249,7 +265,7 @@ extern "C" int mg_maze2d_policy_rollout(const mg_maze_tasks *T, int32_t task_typ
     const MpLds lds = mp_lds_layout(policy->hidden, view_grid, obs != nullptr);
     if ((size_t)lds.bytes > mg::LDS_LIMIT)
         return mg::set_error(MG_ERR_BAD_SIZE, "hidden=%d view_grid=%d needs %d B of LDS (> 160 KiB)", policy->hidden, view_grid, lds.bytes);
-    const MpKernel kernel = pick_policy_kernel(view_grid);
+    const MpKernel kernel = pick_policy_kernel<SAMPLED>(view_grid);
     mg::DeviceGuard guard(mg::device_of(st->grid));
     if (int rc = mg::opt_in_dynamic_lds(kernel, lds.bytes, "maze2d_policy_rollout_kernel")) return rc;
     MpPolicy pa{policy->params, policy->eps_threshold, policy_ids, policy->n_policies, policy->hidden};
@@ -257,6 +273,33 @@ extern "C" int mg_maze2d_policy_rollout(const mg_maze_tasks *T, int32_t task_typ
     RolloutRec rec{actions, reward, reward64, done, obs};
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + MP_BLOCK - 1) / MP_BLOCK)), dim3(MP_BLOCK), (size_t)lds.bytes,
                        (hipStream_t)stream, *T, *st, task_type, max_steps, auto_reset, n, n_steps, obs_every, pa, *carry, seed, step0,
-                       episodic, po, rec);
+                       episodic, po, rec, inv_temperature);
     return mg::check_launch("maze2d_policy_rollout_kernel");
+}
+
+}  // namespace
+
+extern "C" int mg_maze2d_policy_rollout(const mg_maze_tasks *T, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                                        int32_t auto_reset, int32_t n, const mg_maze_state *st, int32_t n_steps,
+                                        int32_t obs_every, const mg_maze_policy *policy, const int32_t *policy_ids,
+                                        const mg_maze_policy_carry *carry, uint64_t seed, uint64_t step0, int32_t episodic,
+                                        float *obs_last, double *ret_total, double *ret_episode, int32_t *episode_len,
+                                        int32_t *episodes, int32_t *actions, float *reward, double *reward64, uint8_t *done,
+                                        float *obs, void *stream) {
+    return maze2d_policy_rollout<false>("mg_maze2d_policy_rollout", T, task_type, max_steps, view_grid, auto_reset, n, st, n_steps,
+                                        obs_every, policy, policy_ids, carry, nullptr, seed, step0, episodic, obs_last, ret_total,
+                                        ret_episode, episode_len, episodes, actions, reward, reward64, done, obs, stream);
+}
+
+extern "C" int mg_maze2d_policy_rollout_sampled(const mg_maze_tasks *T, int32_t task_type, int32_t max_steps, int32_t view_grid,
+                                                int32_t auto_reset, int32_t n, const mg_maze_state *st, int32_t n_steps,
+                                                int32_t obs_every, const mg_maze_policy *policy, const int32_t *policy_ids,
+                                                const mg_maze_policy_carry *carry, const float *inv_temperature, uint64_t seed,
+                                                uint64_t step0, int32_t episodic, float *obs_last, double *ret_total,
+                                                double *ret_episode, int32_t *episode_len, int32_t *episodes, int32_t *actions,
+                                                float *reward, double *reward64, uint8_t *done, float *obs, void *stream) {
+    return maze2d_policy_rollout<true>("mg_maze2d_policy_rollout_sampled", T, task_type, max_steps, view_grid, auto_reset, n, st,
+                                       n_steps, obs_every, policy, policy_ids, carry, inv_temperature, seed, step0, episodic,
+                                       obs_last, ret_total, ret_episode, episode_len, episodes, actions, reward, reward64, done,
+                                       obs, stream);
 }

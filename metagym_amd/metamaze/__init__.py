@@ -4,8 +4,9 @@ from .expert import MazeDistanceField, distance_field_reference, expert_action_r
 from .maze_env import MetaMaze2D, MetaMazeDiscrete3D, MetaMazeContinuous3D, rollout_obs_steps
 from .maze_task import MAZE_TASK_MANAGER, DeviceTaskTable, MazeTaskManager, MazeTaskSampler, TaskConfig
 from .policy import Maze3DPolicy, Maze3DPolicyState, Maze3DSteerPolicy, MazePolicy, MazePolicyRollout, MazePolicyState
+from .policy_net import MazePolicyNet, log_prob
 
 __all__ = ["MetaMaze2D", "MetaMazeDiscrete3D", "MetaMazeContinuous3D", "MazeTaskSampler", "MazeTaskManager",
            "MAZE_TASK_MANAGER", "TaskConfig", "DeviceTaskTable", "rollout_obs_steps", "MazePolicy", "MazePolicyState",
            "MazePolicyRollout", "MazeDistanceField", "distance_field_reference", "expert_action_reference", "Maze3DPolicy",
-           "Maze3DSteerPolicy", "Maze3DPolicyState"]
+           "Maze3DSteerPolicy", "Maze3DPolicyState", "MazePolicyNet", "log_prob"]

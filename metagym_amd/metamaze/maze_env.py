@@ -457,7 +457,9 @@ class MetaMaze2D(_MazeBatch):
         `policy_ids=None` = e % P) on its own window, previous action, reward and done inside the kernel and steps with the
         result (metamaze/policy.py defines the arithmetic exactly). `state` is the carry of the previous call (a
         `MazePolicyState`; None = a fresh one); it is not written, the end carry comes back as `.state` of the result with
-        `step` advanced by `steps`. `seed` keys the exploration draws of a policy with epsilon. With `auto_reset` the policy's
+        `step` advanced by `steps`. `seed` keys the exploration draws of a policy with epsilon and the sampling draws of a
+        policy with a temperature (which goes through mg_maze2d_policy_rollout_sampled; everything else here is the same).
+        With `auto_reset` the policy's
         memory survives a done (the step after it sees the next episode's first window, prev_done = 1 and the ending step's
         reward and action); `episodic=True` clears the carry at a done instead. Returns a `MazePolicyRollout`: ret_total,
         ret_episode, episode_len, episodes and state always; actions, reward, reward64, done [steps, N] when `record=True`,
@@ -482,6 +484,7 @@ class MetaMaze2D(_MazeBatch):
         state, seed = _policy.check_discrete_carry(state, MazePolicyState, N, H, T, seed, dev)
         ids_d = _policy.policy_ids(self, policy_ids, P)
         params, thr = policy.to(dev)
+        inv_t = policy.inv_temperature_on(dev)
         # everything is checked: from here on the env and the new carry are written
         carry = MazePolicyState(*[v.to(dev).clone().contiguous() for v in (state.h, state.prev_action, state.prev_reward,
                                                                            state.prev_done)], step=state.step + T)
@@ -490,14 +493,17 @@ class MetaMaze2D(_MazeBatch):
                                        carry.prev_done.data_ptr())
         res = self._rollout_results(T, idx, obs_every, record, carry)
         obs = res.obs
-        rc = self._lib.mg_maze2d_policy_rollout(self._tasks_c, self._tt, self.max_steps, self.view_grid, int(self.auto_reset), N,
-                                                self._state_c, T, int(obs_every), desc, _lib.ptr(ids_d), carry_c, seed, state.step,
-                                                int(bool(episodic)), _lib.ptr(self._obs), _lib.ptr(res.ret_total),
-                                                _lib.ptr(res.ret_episode), _lib.ptr(res.episode_len), _lib.ptr(res.episodes),
-                                                _lib.ptr(res.actions), _lib.ptr(res.reward), _lib.ptr(res.reward64),
-                                                _lib.ptr(res.done), _lib.ptr(obs) if int(obs_every) > 0 else None,
-                                                _lib.current_stream(dev))
-        _lib.check(rc, "mg_maze2d_policy_rollout")
+        head = (self._tasks_c, self._tt, self.max_steps, self.view_grid, int(self.auto_reset), N, self._state_c, T, int(obs_every),
+                desc, _lib.ptr(ids_d), carry_c)
+        tail = (seed, state.step, int(bool(episodic)), _lib.ptr(self._obs), _lib.ptr(res.ret_total), _lib.ptr(res.ret_episode),
+                _lib.ptr(res.episode_len), _lib.ptr(res.episodes), _lib.ptr(res.actions), _lib.ptr(res.reward),
+                _lib.ptr(res.reward64), _lib.ptr(res.done), _lib.ptr(obs) if int(obs_every) > 0 else None,
+                _lib.current_stream(dev))
+        if inv_t is None:
+            _lib.check(self._lib.mg_maze2d_policy_rollout(*(head + tail)), "mg_maze2d_policy_rollout")
+        else:
+            _lib.check(self._lib.mg_maze2d_policy_rollout_sampled(*(head + (_lib.ptr(inv_t),) + tail)),
+                       "mg_maze2d_policy_rollout_sampled")
         return res
 
     def rollout_expert(self, steps, field=None, record=False, obs_every=0):

@@ -22,6 +22,13 @@ arithmetic only: thr[p] = min(floor(epsilon[p] * 2^32), 2^32 - 1); for env e at 
 out = philox4x32_10(c0 = e, c1 = n & 0xFFFFFFFF, c2 = n >> 32, c3 = 0x4D5A, k0 = seed & 0xFFFFFFFF, k1 = seed >> 32) and
 action = (out[0] < thr) ? (out[1] & 3) : greedy.
 
+A set with `temperature` (float32 [P], finite and > 0) SAMPLES its action from softmax(l / temperature) instead, by the
+Gumbel-max draw bandits/policy.py defines bit for bit: inv_t[p] = float32(1) / float32(temperature[p]) on the host (refused
+when not finite or not > 0), one Philox block with c3 = 0x53000000 for the four moves, u = u01(out[k]), g = -log32(-log32(u)),
+score[k] = l[k] * inv_t + g (one multiply, then one add), the lowest index among the maxima of the scores. With `epsilon` as
+well, the exploration draw is made as above and overrides the sampled action. Without `temperature` nothing changes.
+`MazePolicyNet` (policy_net.py) is the same network as a torch module, for the gradient of a recorded rollout.
+
 `MazePolicy.reference` evaluates exactly this in numpy float32 and numpy integers. Nothing here needs a GPU to import.
 
     pol = MazePolicy(wx, wh, b, wo, bo)                     # wx [P, H, D], wh [P, H, H], b [P, H], wo [P, 4, H], bo [P, 4]
@@ -30,7 +37,8 @@ action = (out[0] < thr) ? (out[1] & 3) : greedy.
 """
 import numpy as np
 
-from .._policy import ContinuousPolicyState, PackedPolicySet, check_epsilon, eps_threshold, f32_array, philox4x32_10, to_numpy  # noqa: F401
+from .._policy import (ContinuousPolicyState, PackedPolicySet, check_epsilon, check_temperature, eps_threshold, f32_array,  # noqa: F401
+                       philox4x32_10, sample_actions, to_numpy)
 
 MAX_HIDDEN = 64
 VIEW_GRIDS = (1, 2, 3)
@@ -98,9 +106,10 @@ class MazePolicyState(object):
 
 class MazePolicy(PackedPolicySet):
     """P recurrent policies: wx [P, H, D], wh [P, H, H], b [P, H], wo [P, 4, H], bo [P, 4], all float32 and finite; epsilon
-    float64 [P] in [0, 1] or None (no exploration). 1 <= H <= 64, D = (2 view_grid + 1)^2 + 6 with view_grid in {1, 2, 3}."""
+    float64 [P] in [0, 1] or None (no exploration); temperature float32 [P], finite and > 0, or None (the greedy action, not
+    a sampled one). 1 <= H <= 64, D = (2 view_grid + 1)^2 + 6 with view_grid in {1, 2, 3}."""
 
-    def __init__(self, wx, wh, b, wo, bo, epsilon=None):
+    def __init__(self, wx, wh, b, wo, bo, epsilon=None, temperature=None):
         wx, wh, b = f32_array("wx", wx, 3), f32_array("wh", wh, 3), f32_array("b", b, 2)
         wo, bo = f32_array("wo", wo, 3), f32_array("bo", bo, 2)
         P, H, D = wx.shape
@@ -115,6 +124,7 @@ class MazePolicy(PackedPolicySet):
                              % (wx.shape, wh.shape, b.shape, wo.shape, bo.shape))
         self.wx, self.wh, self.b, self.wo, self.bo = wx, wh, b, wo, bo
         self.epsilon = None if epsilon is None else check_epsilon(epsilon, P)
+        self.temperature = None if temperature is None else check_temperature(temperature, P)
         self.num_policies, self.hidden, self.input_dim, self.view_grid = P, H, D, _VIEW_OF_DIM[D]
 
     @property
@@ -137,7 +147,7 @@ class MazePolicy(PackedPolicySet):
         return out
 
     @classmethod
-    def unpack(cls, packed, hidden, view_grid, epsilon=None):
+    def unpack(cls, packed, hidden, view_grid, epsilon=None, temperature=None):
         """The inverse of `pack`."""
         packed = f32_array("packed", packed, 2)
         P, H, D = packed.shape[0], int(hidden), input_dim(view_grid)
@@ -147,19 +157,21 @@ class MazePolicy(PackedPolicySet):
         R = _record(H, D)
         rec = packed[:, 4:].reshape(P, H, R)
         return cls(rec[:, :, :D].copy(), rec[:, :, D + 1:D + 1 + H].copy(), rec[:, :, D].copy(),
-                   rec[:, :, R - 4:].transpose(0, 2, 1).copy(), packed[:, :4].copy(), epsilon)
+                   rec[:, :, R - 4:].transpose(0, 2, 1).copy(), packed[:, :4].copy(), epsilon, temperature)
 
     def _host(self):
         """`to(device)` gives (packed parameters, thresholds or None); the thresholds travel as the int32 tensor with the
         uint32's bits."""
         return self.pack(), self._threshold_bits()
 
-    def reference(self, obs, policy_ids, state, seed=0, env_ids=None, return_explored=False):
+    def reference(self, obs, policy_ids, state, seed=0, env_ids=None, return_explored=False, return_logits=False):
         """One step of the definition above in numpy float32 (and numpy integers for the exploration), with exactly that
         association. obs: the windows, float32 [N, w, w] (or [N, w*w]); policy_ids [N]; state: a `MazePolicyState` (its h,
         prev_action, prev_reward, prev_done and step are read; nothing is written); env e draws with counter c0 =
         env_ids[e] (default e). Returns (actions int32 [N], next h float32 [N, H]), and with `return_explored` also the bool
-        [N] mask of the envs whose action was the exploratory draw. The oracle of the policy half of a closed-loop rollout."""
+        [N] mask of the envs whose action was the exploratory draw, and with `return_logits` last the float32 [N, 4] logits.
+        A set with a temperature draws the action from its scores (the module docstring) where a set without takes the
+        greedy one. The oracle of the policy half of a closed-loop rollout."""
         P, H, D = self.num_policies, self.hidden, self.input_dim
         ww = D - 6
         win = to_numpy(obs)
@@ -208,10 +220,12 @@ class MazePolicy(PackedPolicySet):
         thr = self.thresholds[ids]
         e = np.arange(N, dtype=np.uint64) if env_ids is None else to_numpy(env_ids).astype(np.uint64)
         n, s = int(state.step), int(seed)
+        if self.temperature is not None:
+            greedy = sample_actions(logits, self.inv_temperature[ids], e, n, s)
         out = philox4x32_10(e, n & 0xFFFFFFFF, (n >> 32) & 0xFFFFFFFF, PHILOX_TAG, s & 0xFFFFFFFF, (s >> 32) & 0xFFFFFFFF)
         explored = out[0] < thr
         actions = np.where(explored, (out[1] & np.uint32(3)).astype(np.int32), greedy).astype(np.int32)
-        return (actions, hn, explored) if return_explored else (actions, hn)
+        return (actions, hn) + ((explored,) if return_explored else ()) + ((logits,) if return_logits else ())
 
 
 class MazePolicyRollout(object):
